@@ -9,6 +9,12 @@ min id of its component, written to HBM). Edges are generated into HBM before th
 timed region (each rank its own contiguous 1/N shard of the 2^30-edge stream).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--scale 26] [--log-batch 20]
+                  [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the line: only what the
+headline figure needs. `--full` adds, outside the timed region, everything else the line
+can carry: the self-checks against the oracle and the committed digests, the roofline's
+serialised pass, the exchange phases, the PCIe-inclusive figure and the CPU baselines.
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy.
 N > 1 runs one process per GPU (RCCL). Under torch.distributed.run the ranks come
 from the environment; without WORLD_SIZE, `--gpus N` starts the N ranks itself as a
 child torch.distributed.run (before anything touches the GPU) and relays rank 0's
@@ -131,11 +137,59 @@ def replica_digest_checks(digest, world, expected, device):
     return out
 
 
+DUMP_ROWS = 1 << 20   # rows kept of a longer output: 4 files x 2^20 x 8 B = 32 MB for a (vertex, label) table
+DUMP_SEED = 0x0D0B5EED
+
+
+def dump_outputs(dirname, cols, scalars=None, sort=True, rank=0, world=1):
+    """--dump-outputs: the arrays a caller of the timed path receives, as float64 .npy files.
+    `cols` maps names to int64 arrays (torch or numpy) of equal length whose rows belong
+    together, e.g. vertex and label. The library emits a table in slot order, which is not
+    part of its contract, so with `sort` the rows are ordered by the first column (unique
+    keys) before anything else. Of more than DUMP_ROWS rows a fixed sample is kept: row
+    indices drawn once from DUMP_SEED, the same for the same row count. 64-bit ids do not fit
+    a float64, so column `c` becomes c_hi32.npy and c_lo32.npy (the unsigned halves, exact);
+    rows.npy holds the full row count and `scalars` one value each. Ranks of an N > 1 run
+    write <name>_rank<r>.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    sfx = "_rank%d" % rank if world > 1 else ""
+
+    def save(name, a):
+        np.save(os.path.join(dirname, name + sfx + ".npy"), np.asarray(a, dtype=np.float64))
+
+    names = list(cols)
+    t = [torch.as_tensor(cols[k]) for k in names]
+    n = int(t[0].numel()) if t else 0
+    sel = None
+    if sort and n:
+        sel = torch.argsort(t[0])
+    if n > DUMP_ROWS:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_ROWS))
+        idx = torch.from_numpy(idx).to(t[0].device)
+        sel = idx if sel is None else sel[idx]
+    for k, x in zip(names, t):
+        x = (x if sel is None else x[sel]).cpu().numpy().astype(np.int64).view(np.uint64)
+        save(k + "_hi32", x >> np.uint64(32))
+        save(k + "_lo32", x & np.uint64(0xFFFFFFFF))
+    if t:
+        save("rows", [n])
+    for k, v in (scalars or {}).items():
+        save(k, [v])
+
+
 def parse():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=3)
     p.add_argument("--warmup", type=int, default=1)
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run everything beside the headline figure (rmat-cc, bip, ingest): "
+                        "self-checks against the oracle and the committed digests, the roofline's serialised pass, "
+                        "the exchange phases, the PCIe-inclusive figure, the CPU baselines. er-latency and dropin "
+                        "time their whole protocol and print the same line with or without it")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last timed step computed as DIR/<name>.npy (float64; "
+                        "see dump_outputs)")
     p.add_argument("--workload", choices=["rmat-cc", "bip", "er-latency", "ingest", "dropin"], default="rmat-cc",
                    help="rmat-cc: BASELINE config 3 (the headline line); bip: config 4 (bipartiteness, "
                         "2x2^19 vertices, 2^24 edges); er-latency: config 5 (ER G(2^22, 2^26), 2^16-edge windows, "
@@ -403,8 +457,12 @@ def bench_bip(args):
     # roofline of the signed k_fold (one GPU): HIP events around every launch over one extra
     # serialised step, the same 48 B/edge algorithmic bytes as the CC fold (the parity rides
     # in the link word); traffic from the workload's PMC profile of this build
+    if args.dump_outputs:  # the last timed step's verdict, and the colouring that stands behind it
+        _, comp, cv, sign = summ.colouring()
+        dump_outputs(args.dump_outputs, {"vertex": cv, "component": comp, "sign": sign}, {"bipartite": float(ok[0])},
+                     rank=rank, world=world)
     roof = None
-    if group is None and not args.no_profile_pass:
+    if args.full and group is None and not args.no_profile_pass:
         summ.set_profiling(True)
         one_step()
         summ.sync()
@@ -428,7 +486,16 @@ def bench_bip(args):
         col = summ.colouring()
         roof["atomic_floor"] = atomic_floor(summ.num_vertices(), len(np.unique(col[1])) if col[0] else 0,
                                             el * 1e3 / args.steps)
-    if args.profile_only:  # profiling run: the timed steps only
+    if args.profile_only or not args.full:  # profiling run, or a plain one: the timed steps only
+        if rank == 0 and not args.profile_only:
+            print(json.dumps({
+                "metric": "edges/sec for streaming bipartiteness (config 4)", "value": round(E * args.steps / el, 1),
+                "unit": "edges/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+                "ms_per_step": round(el * 1e3 / args.steps, 3), "higher_is_better": True, "scaling": "strong",
+                "vs_baseline": None, "dtype": "int64", "data": "synthetic",
+                "config": {"workload": "bip-config4", "side_vertices": 1 << logside, "edges": E, "micro_batch": B,
+                           "clean_stream_bipartite": bool(ok[0]), "checks": "none (plain run; --full runs them)"},
+                "roofline": None, "cpu_baseline": None}), flush=True)
         if group is not None:
             group.close()
         summ.close()
@@ -701,7 +768,19 @@ def bench_ingest(args):
     for _ in range(args.steps):
         n, bad = gs.parse_edges_device(text, ps, pd)
     el = (time.perf_counter() - t0) / args.steps
+    if args.dump_outputs:  # the last timed parse: its edge arrays in stream order, count and first bad line
+        dump_outputs(args.dump_outputs, {"src": ps[:n], "dst": pd[:n]}, {"edges": n, "bad_line": bad}, sort=False)
     if args.profile_only:  # profiling run: the device-resident parses only
+        return
+    if not args.full:  # plain run: the timed parses only
+        print(json.dumps({
+            "metric": "text edge ingest: edges/sec parsed from device-resident text", "value": round(E / el, 1),
+            "unit": "edges/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(el * 1e3, 3), "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+            "dtype": "u8", "data": "synthetic",
+            "config": {"workload": "ingest-rmat26-text", "edges": E, "text_bytes": int(text.numel()),
+                       "edges_parsed": int(n), "checks": "none (plain run; --full runs them)"},
+            "roofline": None, "cpu_baseline": None}), flush=True)
         return
     ok = n == E and bad == -1 and bool(torch.equal(ps, src)) and bool(torch.equal(pd, dst))
     nbytes = int(text.numel())
@@ -962,6 +1041,9 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and args.steps + args.warmup > 0:  # the last timed step's label pass
+        k = nlabels[0]
+        dump_outputs(args.dump_outputs, {"vertex": out_v[:k], "label": out_l[:k]}, rank=rank, world=world)
     if args.profile_only:  # profiling / tracing run: the timed steps only
         if args.profile_serial and not grouped:  # (+ the roofline's serialised pass)
             summ.set_profiling(True)
@@ -979,55 +1061,59 @@ def main():
         return
     total_edges = E * args.steps
     value = total_edges / elapsed
-    labelled = nlabels[0]
-    checks = {}
-    # every replica's (v, label) set -- not only its size -- against the single-GPU
-    # summary's committed digest
-    stream_key = "rmat%d-ef%d-seed%#x" % (args.scale, args.edge_factor, args.seed)
-    if isinstance(xch, PartExchange):
-        checks.update(slice_digest_checks(gs.digest_rows(out_v[:labelled], out_l[:labelled]), world,
-                                          KNOWN_DIGESTS.get(stream_key), dev))
-    else:
-        checks.update(replica_digest_checks(summ.digest(), world, KNOWN_DIGESTS.get(stream_key), dev))
-    checks["digest_stream"] = stream_key
-    if isinstance(xch, (NativeExchange, PartExchange)):  # the world RCCL formed (ncclCommCount, both communicators)
-        cc, dc = xch.g.comm_ranks()
-        checks["rccl_comm_ranks"] = [cc, dc]
-        checks["rccl_world_ok"] = cc == dc == world
+    own_labelled = labelled = nlabels[0]
     if world > 1:  # vertices labelled by all ranks' slices (outside the timed region)
         c = torch.tensor([labelled], dtype=torch.int64, device=dev)
         dist.all_reduce(c)
         labelled = int(c.item())
-        if not part:  # every replica holds the same vertex count, and the slices cover it exactly
-            nv = summ.num_vertices()
-            lo = torch.tensor([nv], dtype=torch.int64, device=dev)
-            hi = torch.tensor([nv], dtype=torch.int64, device=dev)
-            dist.all_reduce(lo, op=dist.ReduceOp.MIN)
-            dist.all_reduce(hi, op=dist.ReduceOp.MAX)
-            checks["replicas_same_vertex_count"] = int(lo.item()) == int(hi.item()) == labelled
-    else:  # the label pass covers every distinct endpoint of the stream (4 slices of the id space)
-        distinct = 0
-        for lo_bits in range(4):
-            parts = [x[(x & 3) == lo_bits] for x in (src, dst)]
-            distinct += int(torch.unique(torch.cat(parts)).numel())
-            del parts
-        checks["vertices_equal_distinct_endpoints"] = distinct == labelled
-    if rank == 0:  # the stream's first 2^24 edges (rank 0's shard starts there) vs the oracle
-        import oracle  # checker leg only
-        m = min(1 << 24, per)
-        with gs.Summary("cc", device=local, capacity_hint=1 << 20) as chk:
-            for o in range(0, m, 1 << 20):
-                chk.fold_device(src[o:], dst[o:], n=min(1 << 20, m - o))
-            cv, cl = chk.labels()
-        ov, olab = oracle.cc_labels(src[:m].cpu().numpy(), dst[:m].cpu().numpy())
-        checks["prefix_%d_edges_oracle_exact" % m] = bool(np.array_equal(cv, ov) and np.array_equal(cl, olab))
+    full = args.full  # everything below that is not the line itself: outside the timed region, --full only
+    checks = None
+    if full:
+        checks = {}
+        # every replica's (v, label) set -- not only its size -- against the single-GPU
+        # summary's committed digest
+        stream_key = "rmat%d-ef%d-seed%#x" % (args.scale, args.edge_factor, args.seed)
+        if isinstance(xch, PartExchange):
+            checks.update(slice_digest_checks(gs.digest_rows(out_v[:own_labelled], out_l[:own_labelled]), world,
+                                              KNOWN_DIGESTS.get(stream_key), dev))
+        else:
+            checks.update(replica_digest_checks(summ.digest(), world, KNOWN_DIGESTS.get(stream_key), dev))
+        checks["digest_stream"] = stream_key
+        if isinstance(xch, (NativeExchange, PartExchange)):  # the world RCCL formed (ncclCommCount, both communicators)
+            cc, dc = xch.g.comm_ranks()
+            checks["rccl_comm_ranks"] = [cc, dc]
+            checks["rccl_world_ok"] = cc == dc == world
+        if world > 1:
+            if not part:  # every replica holds the same vertex count, and the slices cover it exactly
+                nv = summ.num_vertices()
+                lo = torch.tensor([nv], dtype=torch.int64, device=dev)
+                hi = torch.tensor([nv], dtype=torch.int64, device=dev)
+                dist.all_reduce(lo, op=dist.ReduceOp.MIN)
+                dist.all_reduce(hi, op=dist.ReduceOp.MAX)
+                checks["replicas_same_vertex_count"] = int(lo.item()) == int(hi.item()) == labelled
+        else:  # the label pass covers every distinct endpoint of the stream (4 slices of the id space)
+            distinct = 0
+            for lo_bits in range(4):
+                parts = [x[(x & 3) == lo_bits] for x in (src, dst)]
+                distinct += int(torch.unique(torch.cat(parts)).numel())
+                del parts
+            checks["vertices_equal_distinct_endpoints"] = distinct == labelled
+        if rank == 0:  # the stream's first 2^24 edges (rank 0's shard starts there) vs the oracle
+            import oracle  # checker leg only
+            m = min(1 << 24, per)
+            with gs.Summary("cc", device=local, capacity_hint=1 << 20) as chk:
+                for o in range(0, m, 1 << 20):
+                    chk.fold_device(src[o:], dst[o:], n=min(1 << 20, m - o))
+                cv, cl = chk.labels()
+            ov, olab = oracle.cc_labels(src[:m].cpu().numpy(), dst[:m].cpu().numpy())
+            checks["prefix_%d_edges_oracle_exact" % m] = bool(np.array_equal(cv, ov) and np.array_equal(cl, olab))
 
     # Roofline of the dominant kernel (k_fold). Per launch: HIP events around every
     # launch on the stream it runs on, over one extra full step (profiling serialises
     # the folds, so each event pair brackets one kernel alone). Per step: the same
     # algorithmic bytes over the timed wall clock (pipelined folds, exchange, label pass).
     roof = None
-    if not args.no_profile_pass:
+    if full and not args.no_profile_pass:
         summ.set_profiling(True)
         one_step()
         summ.sync()
@@ -1064,7 +1150,7 @@ def main():
     # step with timing events around each phase (gs_group_set_phase_timing): the N > 1
     # line explains its own scaling. Max over ranks.
     phases = None
-    if isinstance(xch, PartExchange) and not args.profile_only:
+    if full and isinstance(xch, PartExchange):
         xch.g.set_phase_timing(True)
         t0p = time.perf_counter()
         one_step()
@@ -1083,7 +1169,7 @@ def main():
                        "label_forest_vertices": stp["label_forest_vertices"],
                        "note": "max over ranks, one untimed step with HIP timing events around every combine phase; "
                                "alltoall and pair_gather include the wait for the other ranks"})
-    if isinstance(xch, NativeExchange) and not args.profile_only:
+    if full and isinstance(xch, NativeExchange):
         xch.g.set_phase_timing(True)
         t0p = time.perf_counter()
         one_step()
@@ -1109,7 +1195,7 @@ def main():
     # DMA straight from the caller's buffer, then the fold) into a fresh summary, outside
     # the timed region. Never `value`.
     pcie = None
-    if rank == 0 and world == 1 and xch is None and not args.profile_only:
+    if full and rank == 0 and world == 1 and xch is None:
         m = min(1 << 27, per)
         hs = torch.empty(m, dtype=torch.int64, pin_memory=True)
         hd = torch.empty(m, dtype=torch.int64, pin_memory=True)
@@ -1132,7 +1218,7 @@ def main():
         del hs, hd, ns_, nd_
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         import oracle  # CPU baseline leg only
         m = 1 << args.cpu_sample_log2
         hs = src[:m].cpu().numpy()

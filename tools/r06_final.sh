@@ -9,7 +9,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/final_$TAG
 mkdir -p $O
 cd $R
-timeout -k 10 300 python -u bench.py --exchange --combine partitioned --steps 5 --warmup 2 --no-cpu-baseline \
+timeout -k 10 300 python -u bench.py --full --exchange --combine partitioned --steps 5 --warmup 2 --no-cpu-baseline \
   > $O/bench_part1.out 2> $O/bench_part1.err || { echo "bench_part1 failed rc=$?"; exit 1; }
 echo "bench_part1 ok"
 cd /tmp && export TMPDIR=/tmp
