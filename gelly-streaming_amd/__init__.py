@@ -62,7 +62,12 @@ EXPORTED_SYMBOLS = (
     "gs_group_create_partitioned", "gs_group_part_fold_device", "gs_group_part_combine",
     "gs_group_part_labels_device", "gs_group_part_status", "gs_group_part_reset", "gs_group_part_stats",
     "gs_group_part_phase_stats",
+    "gs_num_components", "gs_export_components_device", "gs_export_components",
 )
+
+# Pairs per workgroup of the component export's radix-sort kernels (csrc/gs_sort.hpp kSortTile):
+# sizes around it are where a tile fills exactly.
+SORT_TILE = 2048
 
 FAIL_BIT = 1 << 62  # count words: a failed signed verdict (GS_FAIL_BIT)
 DIGEST_FAILED = (1 << 64) - 1  # gs_digest of a signed summary whose verdict failed (GS_DIGEST_FAILED)
@@ -180,6 +185,10 @@ def lib():
     L.gs_group_part_phase_stats.argtypes = [_vp, ctypes.POINTER(ctypes.c_double)]
     L.gs_hbm_bytes.argtypes = [ctypes.c_int, ctypes.POINTER(_u64)]
     L.gs_create_bytes.argtypes = [ctypes.c_int, _u64, ctypes.POINTER(_u64)]
+    L.gs_num_components.argtypes = [_vp, ctypes.POINTER(_u64)]
+    L.gs_export_components_device.argtypes = [_vp, _vp, _vp, _vp, _vp, _sz, _sz, ctypes.POINTER(_sz),
+                                              ctypes.POINTER(_sz)]
+    L.gs_export_components.argtypes = [_vp, _vp, _vp, _vp, _vp, _sz, _sz, ctypes.POINTER(_sz), ctypes.POINTER(_sz)]
     L.gs_testing_set.argtypes = [ctypes.c_int, _i64]
     L.gs_testing_get.argtypes = [ctypes.c_int]
     L.gs_testing_get.restype = _i64
@@ -479,6 +488,48 @@ class Summary:
         comp, v, sign = comp[:k], v[:k], sign[:k]
         o = np.lexsort((v, comp))
         return self.ok(), comp[o], v[o], sign[o]
+
+    def num_components(self):
+        """gs_num_components: the number of components (0 for a failed signed summary)."""
+        n = _u64()
+        _check(lib().gs_num_components(self._h, ctypes.byref(n)))
+        return n.value
+
+    def components_device(self, comp, offset, member, sign=None):
+        """gs_export_components_device: the summary grouped and ordered as CSR into DEVICE
+        arrays (comp int64[cap_c], offset uint64/int64[cap_c + 1], member int64[cap_v], sign
+        uint8[cap_v] or None); returns (nv, nc). Raises GSError(GS_ERR_TRUNCATED) when a
+        capacity is too small (nothing written)."""
+        nv, nc = _sz(), _sz()
+        cap_v = member.numel() if hasattr(member, "numel") else len(member)
+        cap_c = comp.numel() if hasattr(comp, "numel") else len(comp)
+        n_off = offset.numel() if hasattr(offset, "numel") else len(offset)
+        assert n_off >= cap_c + 1, "offset holds one entry more than comp"
+        _check(lib().gs_export_components_device(self._h, _ptr(comp), _ptr(offset), _ptr(member), _ptr(sign),
+                                                 cap_v, cap_c, ctypes.byref(nv), ctypes.byref(nc)))
+        return nv.value, nc.value
+
+    def components(self):
+        """(ok, comp, offset, member, sign) numpy arrays through gs_export_components: comp
+        ascending, offset[nc + 1] into member, member ordered by (label, vertex), sign = 1
+        for the colour of the component's minimum (all 0 for kind 'cc'). A failed signed
+        verdict gives ok False and empty arrays with offset == [0]."""
+        nv, nc = _sz(), _sz()
+        n = self.num_vertices()
+        k = n  # at most one component per vertex: no count pass before the export
+        while True:
+            comp = np.empty(k, np.int64)
+            offset = np.zeros(k + 1, np.uint64)
+            member = np.empty(n, np.int64)
+            sign = np.empty(n, np.uint8)
+            rc = lib().gs_export_components(self._h, comp.ctypes.data, offset.ctypes.data, member.ctypes.data,
+                                            sign.ctypes.data, n, k, ctypes.byref(nv), ctypes.byref(nc))
+            if rc != GS_ERR_TRUNCATED:
+                break
+            n, k = nv.value, nc.value  # (the summary grew between the count and the export)
+        _check(rc)
+        ok = self.ok() if self.kind == KIND_SIGNED else True
+        return ok, comp[: nc.value], offset[: nc.value + 1], member[: nv.value], sign[: nv.value]
 
     def serialize(self):
         ln = _sz()

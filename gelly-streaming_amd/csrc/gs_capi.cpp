@@ -935,7 +935,9 @@ int gs_destroy(gs_handle h) {
                   (void*)h->vlist, (void*)h->drec, (void*)h->nxt, (void*)h->chg_scratch, (void*)h->chg_ov,
                   (void*)h->chg_ol, (void*)h->chg_op, (void*)h->d_stage,
                   (void*)h->d_wstage, (void*)h->d_scratch, (void*)h->x_v, (void*)h->x_l, (void*)h->x_p,
-                  (void*)h->x_cnt})
+                  (void*)h->x_cnt, (void*)h->cs_key[0], (void*)h->cs_key[1], (void*)h->cs_pay[0], (void*)h->cs_pay[1],
+                  (void*)h->cs_table, (void*)h->cs_ctl, (void*)h->co_comp, (void*)h->co_off, (void*)h->co_member,
+                  (void*)h->co_sign})
     (void)dfree(p);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
@@ -1339,6 +1341,201 @@ int gs_export_colouring(gs_handle h, int64_t* comp, int64_t* v, uint8_t* sign, s
   if (sign)
     for (size_t i = 0; i < *n; ++i) sign[i] = sign[i] ? 0 : 1;  // parity 0 <=> same colour as the minimum
   return GS_OK;
+}
+
+// ---- grouped component export (canonical CSR of the summary) -----------------------------
+// Rows are gathered unordered into the combine scratch (export_device_impl: the read-only
+// finds, the vertex-list fallback and the reserved slot of INT64_MIN come with it), sorted by
+// vertex and then stably by label with the radix sort of gs_sort_k.hip, and compacted into
+// comp / offset. The host reads two things before the sort: the row count (with the export)
+// and the control words of k_sort_digits (root count for the capacity check, and the digit
+// histograms that say which passes are identities).
+
+// Unordered rows of the whole summary in x_v / x_l / x_p; *n rows. A failed signed verdict
+// and an empty summary give *n = 0 without an export.
+static int gather_rows(gs_handle h, uint64_t* n) {
+  *n = 0;
+  if (h->kind == GS_KIND_SIGNED) {
+    int ok = 1;
+    if (int rc = gs_bip_status(h, &ok)) return rc;
+    if (!ok) return GS_OK;  // (false,{})
+  }
+  uint64_t nv = 0;
+  if (int rc = read_nv(h, &nv)) return rc;
+  if (int rc = check_flags_now(h)) return rc;
+  if (nv == 0) return GS_OK;
+  if (int rc = ensure_x(h, nv + 1)) return rc;
+  if (int rc = wait_x_consumer(h)) return rc;
+  size_t got = 0;
+  if (int rc = export_device_impl(h, h->x_v, h->x_l, h->x_p, h->x_cap, &got)) return rc;
+  *n = got;
+  return GS_OK;
+}
+
+// Sort scratch for `rows` rows: allocated on growth only, with a quarter of headroom so
+// that a summary exported every window does not reallocate every window.
+static int ensure_sort_scratch(gs_handle h, uint64_t rows) {
+  if (!h->cs_ctl) GS_HIP(dmalloc(&h->cs_ctl, gs::kSortCtlWords * 4));
+  if (h->cs_rows >= rows) return GS_OK;
+  GS_HIP(hipStreamSynchronize(h->stream));
+  for (int i = 0; i < 2; ++i) {
+    (void)dfree(h->cs_key[i]);
+    (void)dfree(h->cs_pay[i]);
+    h->cs_key[i] = nullptr;
+    h->cs_pay[i] = nullptr;
+  }
+  (void)dfree(h->cs_table);
+  h->cs_table = nullptr;
+  h->cs_rows = 0;
+  const uint64_t c = gs::sort_blocks(rows + rows / 4) * gs::kSortTile;
+  for (int i = 0; i < 2; ++i) {
+    GS_HIP(dmalloc(&h->cs_key[i], c * 8));
+    GS_HIP(dmalloc(&h->cs_pay[i], c * 4));
+  }
+  GS_HIP(dmalloc(&h->cs_table, gs::kSortRadix * gs::sort_row_stride(gs::sort_blocks(c)) * 4));
+  h->cs_rows = c;
+  return GS_OK;
+}
+
+// Device staging of the host-array form: nv members / signs, nc components.
+static int ensure_comp_staging(gs_handle h, uint64_t nv, uint64_t nc) {
+  if (h->co_vcap < nv) {
+    GS_HIP(hipStreamSynchronize(h->stream));
+    (void)dfree(h->co_member);
+    (void)dfree(h->co_sign);
+    h->co_member = nullptr;
+    h->co_sign = nullptr;
+    h->co_vcap = 0;
+    const uint64_t c = nv + nv / 4;
+    GS_HIP(dmalloc(&h->co_member, c * 8));
+    GS_HIP(dmalloc(&h->co_sign, c));
+    h->co_vcap = c;
+  }
+  if (h->co_ccap < nc) {
+    GS_HIP(hipStreamSynchronize(h->stream));
+    (void)dfree(h->co_comp);
+    (void)dfree(h->co_off);
+    h->co_comp = nullptr;
+    h->co_off = nullptr;
+    h->co_ccap = 0;
+    const uint64_t c = nc + nc / 4;
+    GS_HIP(dmalloc(&h->co_comp, c * 8));
+    GS_HIP(dmalloc(&h->co_off, (c + 1) * 8));
+    h->co_ccap = c;
+  }
+  return GS_OK;
+}
+
+static int components_impl(gs_handle h, int64_t* comp, uint64_t* offset, int64_t* member, uint8_t* sign, size_t cap_v,
+                           size_t cap_c, size_t* nv, size_t* nc, bool to_host) {
+  *nv = *nc = 0;
+  uint64_t n = 0;
+  if (int rc = gather_rows(h, &n)) return rc;
+  if (n == 0) {  // empty, or a failed signed verdict: no components, offset[0] = 0
+    if (offset && to_host) offset[0] = 0;
+    if (offset && !to_host) {
+      GS_HIP(hipMemsetAsync(offset, 0, 8, h->stream));
+      GS_HIP(hipStreamSynchronize(h->stream));
+    }
+    return GS_OK;
+  }
+  if (int rc = ensure_sort_scratch(h, n)) return rc;
+  std::vector<uint32_t> ctl(gs::kSortCtlWords);
+  GS_HIP(hipMemsetAsync(h->cs_ctl, 0, gs::kSortCtlWords * 4, h->stream));
+  gs::launch_sort_digits(h->x_v, h->x_l, n, h->cs_ctl, h->stream);
+  GS_HIP(hipGetLastError());
+  GS_HIP(hipMemcpyAsync(ctl.data(), h->cs_ctl, gs::kSortCtlWords * 4, hipMemcpyDeviceToHost, h->stream));
+  GS_HIP(hipStreamSynchronize(h->stream));
+  const uint64_t roots = ctl[gs::kSortCtlRoots];
+  *nv = n;
+  *nc = roots;
+  if (cap_v < n || cap_c < roots)
+    return fail(GS_ERR_TRUNCATED, "output capacity " + std::to_string(cap_v) + " vertices / " + std::to_string(cap_c) +
+                                      " components < " + std::to_string(n) + " / " + std::to_string(roots));
+  if (!comp || !offset || !member) return fail(GS_ERR_INVALID, "null arrays");
+  int64_t* d_comp = comp;
+  unsigned long long* d_off = reinterpret_cast<unsigned long long*>(offset);
+  int64_t* d_member = member;
+  uint8_t* d_sign = sign;
+  uint64_t d_cap_c = cap_c;
+  if (to_host) {
+    if (int rc = ensure_comp_staging(h, n, roots)) return rc;
+    d_comp = h->co_comp;
+    d_off = h->co_off;
+    d_member = h->co_member;
+    d_sign = sign ? h->co_sign : nullptr;
+    d_cap_c = h->co_ccap;
+  }
+  // sort 1 by vertex (payload = row), sort 2 stably by the row's label: ordered by (label,
+  // vertex). A digit with one bin holding every key is an identity pass and is skipped.
+  gs::SortSrc cur;
+  cur.ids = h->x_v;
+  cur.rows = n;
+  int side = 0;
+  for (int s = 0; s < 2; ++s) {
+    if (s == 1) {
+      cur.key = nullptr;  // keys of sort 2: the label of row cur.pay[i] (row i when sort 1 had no pass to run)
+      cur.ids = h->x_l;
+    }
+    for (int p = 0; p < (int)gs::kSortPasses; ++p) {
+      const uint32_t* gh = ctl.data() + (s * gs::kSortPasses + p) * gs::kSortRadix;
+      if (*std::max_element(gh, gh + gs::kSortRadix) == n) continue;
+      gs::launch_sort_pass(cur, n, p, h->cs_table, h->cs_ctl + (gh - ctl.data()), h->cs_key[side], h->cs_pay[side],
+                           h->stream);
+      GS_HIP(hipGetLastError());
+      cur.key = h->cs_key[side];
+      cur.pay = h->cs_pay[side];
+      cur.ids = nullptr;
+      side ^= 1;
+    }
+  }
+  if (!cur.key) cur.ids = h->x_l;
+  gs::launch_comp_csr(cur, n, h->x_v, h->x_p, h->kind == GS_KIND_SIGNED, h->cs_table, d_comp, d_off, d_member, d_sign,
+                      d_cap_c, h->stream);
+  GS_HIP(hipGetLastError());
+  if (to_host) {
+    GS_HIP(hipMemcpyAsync(comp, d_comp, roots * 8, hipMemcpyDeviceToHost, h->stream));
+    GS_HIP(hipMemcpyAsync(offset, d_off, (roots + 1) * 8, hipMemcpyDeviceToHost, h->stream));
+    GS_HIP(hipMemcpyAsync(member, d_member, n * 8, hipMemcpyDeviceToHost, h->stream));
+    if (sign) GS_HIP(hipMemcpyAsync(sign, d_sign, n, hipMemcpyDeviceToHost, h->stream));
+  }
+  GS_HIP(hipStreamSynchronize(h->stream));
+  return check_flags_now(h);
+}
+
+int gs_num_components(gs_handle h, uint64_t* n) {
+  if (int rc = check(h)) return rc;
+  if (!n) return fail(GS_ERR_INVALID, "n is null");
+  *n = 0;
+  DeviceGuard g(h->device);
+  uint64_t rows = 0;
+  if (int rc = gather_rows(h, &rows)) return rc;
+  if (rows == 0) return GS_OK;
+  unsigned long long* d = reinterpret_cast<unsigned long long*>(h->d_scratch);
+  unsigned long long out = 0;
+  GS_HIP(hipMemsetAsync(d, 0, 8, h->stream));
+  gs::launch_comp_roots(h->x_v, h->x_l, rows, d, h->stream);
+  GS_HIP(hipGetLastError());
+  GS_HIP(hipMemcpyAsync(&out, d, 8, hipMemcpyDeviceToHost, h->stream));
+  GS_HIP(hipStreamSynchronize(h->stream));
+  *n = out;
+  return check_flags_now(h);
+}
+
+int gs_export_components_device(gs_handle h, int64_t* comp, uint64_t* offset, int64_t* member, uint8_t* sign,
+                                size_t cap_v, size_t cap_c, size_t* nv, size_t* nc) {
+  if (int rc = check(h)) return rc;
+  if (!nv || !nc) return fail(GS_ERR_INVALID, "nv or nc is null");
+  DeviceGuard g(h->device);
+  return components_impl(h, comp, offset, member, sign, cap_v, cap_c, nv, nc, false);
+}
+
+int gs_export_components(gs_handle h, int64_t* comp, uint64_t* offset, int64_t* member, uint8_t* sign, size_t cap_v,
+                         size_t cap_c, size_t* nv, size_t* nc) {
+  if (int rc = check(h)) return rc;
+  if (!nv || !nc) return fail(GS_ERR_INVALID, "nv or nc is null");
+  DeviceGuard g(h->device);
+  return components_impl(h, comp, offset, member, sign, cap_v, cap_c, nv, nc, true);
 }
 
 // CombineCC.reduce / combineFunction.reduce: export `src` into its own scratch on

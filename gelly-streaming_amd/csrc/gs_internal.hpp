@@ -9,6 +9,7 @@
 
 #include "gs_ingest.hpp"
 #include "gs_kernels.hpp"
+#include "gs_sort.hpp"
 #include "gs_summary.h"
 #include "gs_testing.h"
 
@@ -150,6 +151,19 @@ struct gs_summary {
   unsigned long long* x_cnt = nullptr;  // device: exported rows (u64) + failure flag (u32 at word 1)
   hipEvent_t x_ready = nullptr, x_used = nullptr;
   bool x_pending = false;  // x_used recorded by a consumer not yet waited for
+  // grouped component export (gs_export_components*): the radix sort's ping-pong pair buffers,
+  // per-workgroup histogram table and control words, sized by the first call that needs them;
+  // co_*: device staging of the host-array form
+  unsigned long long* cs_key[2] = {nullptr, nullptr};
+  uint32_t* cs_pay[2] = {nullptr, nullptr};
+  uint32_t* cs_table = nullptr;
+  uint32_t* cs_ctl = nullptr;
+  uint64_t cs_rows = 0;
+  int64_t* co_comp = nullptr;
+  unsigned long long* co_off = nullptr;
+  int64_t* co_member = nullptr;
+  uint8_t* co_sign = nullptr;
+  uint64_t co_vcap = 0, co_ccap = 0;
   // text ingest (gs_fold_text): pinned + device text chunks, parsed edges, scratch
   char* h_text = nullptr;
   uint64_t* h_tres = nullptr;

@@ -1,0 +1,61 @@
+// gs_sort.hpp -- host-side launchers of the grouped component export's kernels
+// (gs_sort_k.hip): a stable LSD radix sort of (uint64 key, uint32 payload) pairs with
+// 8-bit digits, and the tail that turns rows sorted by (label, vertex) into the CSR of
+// gs_export_components*. Every launch is queued on the given stream; kernel boundaries
+// carry all ordering between workgroups (no workgroup waits on another inside a launch).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace gs {
+
+constexpr uint32_t kSortBS = 256;                         // threads of a hist / scatter workgroup
+constexpr uint32_t kSortItems = 8;                        // pairs per thread
+constexpr uint32_t kSortTile = kSortBS * kSortItems;      // pairs per workgroup (gs_sort_tile)
+constexpr uint32_t kSortRadix = 256;                      // 8-bit digits
+constexpr uint32_t kSortPasses = 8;                       // digits of a 64-bit key
+constexpr uint32_t kSortScanBS = 1024;                    // threads of a k_sort_scan workgroup (4 entries each)
+constexpr uint32_t kCompTile = 1024;                      // rows per k_comp_heads / k_comp_write workgroup
+constexpr unsigned long long kSortSignBit = 1ull << 63;   // key = id ^ sign bit: unsigned digit order = signed order
+
+// Control words (uint32): the digit histograms of the whole input, one 256-bin row per
+// (sort, pass) -- sort 0 keyed by vertex, sort 1 by label -- then the count of roots.
+constexpr uint32_t kSortCtlRoots = 2 * kSortPasses * kSortRadix;
+constexpr uint32_t kSortCtlWords = kSortCtlRoots + 4;
+
+__host__ __device__ constexpr uint64_t sort_blocks(uint64_t n) { return (n + kSortTile - 1) / kSortTile; }
+// row stride of the per-workgroup histogram table (digit-major; 16-B aligned rows)
+__host__ __device__ constexpr uint64_t sort_row_stride(uint64_t blocks) { return (blocks + 3) & ~3ull; }
+__host__ __device__ constexpr uint64_t comp_blocks(uint64_t n) { return (n + kCompTile - 1) / kCompTile; }
+
+// Where a pass reads its pairs. pay == nullptr: payload i of pair i is i. key == nullptr:
+// the key is ids[payload] ^ kSortSignBit (the first pass of a sort gathers its keys from the
+// exported rows: vertices for sort 1, labels through sort 1's permutation for sort 2).
+struct SortSrc {
+  const unsigned long long* key = nullptr;
+  const uint32_t* pay = nullptr;
+  const int64_t* ids = nullptr;
+  uint64_t rows = 0;  // entries of ids (a payload is a row index below it)
+};
+
+// ctl[0 .. kSortCtlRoots) += digit histograms of v (rows 0..7) and label (rows 8..15);
+// ctl[kSortCtlRoots] += rows with v == label. ctl must be zero before.
+void launch_sort_digits(const int64_t* v, const int64_t* label, uint64_t n, uint32_t* ctl, hipStream_t st);
+// rows with v == label added into *out (gs_num_components)
+void launch_comp_roots(const int64_t* v, const int64_t* label, uint64_t n, unsigned long long* out, hipStream_t st);
+
+// One pass over digit `pass` (bits 8*pass .. 8*pass+7): table[digit * stride + workgroup]
+// counts, their exclusive scan in (digit, workgroup) order from the digit's global base
+// (ghist: the 256-bin row of this pass in ctl), the stable scatter into (okey, opay).
+void launch_sort_pass(const SortSrc& src, uint64_t n, int pass, uint32_t* table, const uint32_t* ghist,
+                      unsigned long long* okey, uint32_t* opay, hipStream_t st);
+
+// Tail over rows sorted by (label, vertex): src gives label key and row index of position i.
+// member[i] = v[row], sign[i] = !parity[row] (signed kind) or 0, comp / offset = the heads
+// (label differs from the position before) in order; offset[number of heads] = n. `table`
+// holds comp_blocks(n) words of scratch. Writes are bounded by cap_c heads.
+void launch_comp_csr(const SortSrc& src, uint64_t n, const int64_t* v, const uint8_t* parity, bool sign_kind,
+                     uint32_t* table, int64_t* comp, unsigned long long* offset, int64_t* member, uint8_t* sign,
+                     uint64_t cap_c, hipStream_t st);
+
+}  // namespace gs

@@ -217,6 +217,39 @@ int gs_bip_status(gs_handle h, int* ok);
  * (the reference's fail() state is (false,{}), Candidates.java:194-196). */
 int gs_export_colouring(gs_handle h, int64_t* comp, int64_t* v, uint8_t* sign, size_t cap, size_t* n);
 
+/* ---- grouped component export (sinks that read the summary grouped and ordered) ----
+ * Number of components (roots), what DisjointSet.toString's grouping map
+ * (DisjointSet.java:134-150) or Candidates.getMap().size() (Candidates.java:48-50) would
+ * count, without an ordered export: one unordered label pass and a count of the rows
+ * with v == label. 0 for a GS_KIND_SIGNED summary whose verdict failed -- its output is
+ * (false,{}) (Candidates.java:194-196). Synchronises. */
+int gs_num_components(gs_handle h, uint64_t* n);
+
+/* The summary grouped and ordered, as CSR, into DEVICE arrays -- the canonical form of
+ * DisjointSet.toString() (DisjointSet.java:134-150: vertices grouped by root) and of
+ * Candidates.getMap() (Candidates.java:48-50: a TreeMap of components, each an ordered map
+ * of SignedVertex, SignedVertex.java:23-40), sorted on the device instead of by the sink:
+ *   comp[0..nc)      component labels (= minimum id), ascending in SIGNED int64 order
+ *   offset[0..nc]    uint64 start of each component in member[]; offset[nc] = nv
+ *   member[0..nv)    vertices, ordered by (label ascending, vertex ascending), signed order
+ *   sign[0..nv)      optional (may be NULL): 1 when the vertex has the colour of its
+ *                    component's minimum (gs_export_colouring's sign); 0 for GS_KIND_CC
+ * cap_v / cap_c are the capacities of member/sign and of comp (offset holds cap_c + 1).
+ * *nv, *nc on the host (synchronises). GS_ERR_TRUNCATED with *nv, *nc set and nothing
+ * written if either capacity is too small. A failed signed verdict gives nv = nc = 0
+ * (Candidates.java:194-196). An empty summary gives nv = nc = 0 and offset[0] = 0.
+ * Read-only on the summary (gs_digest, delta and change tracking are unaffected). The
+ * sort's scratch (24 bytes per vertex and a histogram table) is allocated by the first
+ * call, kept in the handle and counted by gs_hbm_bytes. */
+int gs_export_components_device(gs_handle h, int64_t* comp, uint64_t* offset, int64_t* member, uint8_t* sign,
+                                size_t cap_v, size_t cap_c, size_t* nv, size_t* nc);
+
+/* Same into HOST arrays: what a JVM sink or the C++ mirror formats toString() /
+ * getMap() from without sorting (DisjointSet.java:134-150, Candidates.java:48-50,
+ * ConnectedComponentsExample.FlattenSet :143-156). */
+int gs_export_components(gs_handle h, int64_t* comp, uint64_t* offset, int64_t* member, uint8_t* sign, size_t cap_v,
+                         size_t cap_c, size_t* nv, size_t* nc);
+
 /* Checkpoint: compact (vertex, label, parity) image of the summary plus the
  * verdict, for Merger.snapshotState/restoreState (SummaryAggregation.java:127-135).
  * Call with buf = NULL to get *len. gs_deserialize replaces the summary. */
