@@ -28,6 +28,11 @@ if os.environ.get("GS_LIB_VARIANT"):  # debug-counter build (Makefile target `de
 
 KIND_CC = 0
 KIND_SIGNED = 1
+KIND_DEGREE = 2
+
+DEGREE_ALL = 0  # gs_degree_dir (DegreeTypeSeparator, SimpleEdgeStream.java:440-459)
+DEGREE_IN = 1
+DEGREE_OUT = 2
 
 GS_OK = 0
 GS_ERR_INVALID = -1
@@ -63,11 +68,17 @@ EXPORTED_SYMBOLS = (
     "gs_group_part_labels_device", "gs_group_part_status", "gs_group_part_reset", "gs_group_part_stats",
     "gs_group_part_phase_stats",
     "gs_num_components", "gs_export_components_device", "gs_export_components",
+    "gs_degree_fold", "gs_degree_fold_device", "gs_degree_find_device", "gs_degree_export_device",
+    "gs_degree_export", "gs_degree_distribution_device", "gs_degree_distribution",
 )
 
 # Pairs per workgroup of the component export's radix-sort kernels (csrc/gs_sort.hpp kSortTile):
 # sizes around it are where a tile fills exactly.
 SORT_TILE = 2048
+
+# Edges per workgroup of the degree fold (csrc/gs_degree.hpp DEGREE_TILE): the tile whose
+# endpoint occurrences are combined on chip; sizes around it are where a tile fills exactly.
+DEGREE_TILE = 2048
 
 FAIL_BIT = 1 << 62  # count words: a failed signed verdict (GS_FAIL_BIT)
 DIGEST_FAILED = (1 << 64) - 1  # gs_digest of a signed summary whose verdict failed (GS_DIGEST_FAILED)
@@ -189,6 +200,13 @@ def lib():
     L.gs_export_components_device.argtypes = [_vp, _vp, _vp, _vp, _vp, _sz, _sz, ctypes.POINTER(_sz),
                                               ctypes.POINTER(_sz)]
     L.gs_export_components.argtypes = [_vp, _vp, _vp, _vp, _vp, _sz, _sz, ctypes.POINTER(_sz), ctypes.POINTER(_sz)]
+    L.gs_degree_fold.argtypes = [_vp, _vp, _vp, _vp, _sz, ctypes.c_int]
+    L.gs_degree_fold_device.argtypes = [_vp, _vp, _vp, _vp, _sz, _sz, ctypes.c_int]
+    L.gs_degree_find_device.argtypes = [_vp, _vp, _sz, _vp, _vp]
+    L.gs_degree_export_device.argtypes = [_vp, _vp, _vp, _sz, ctypes.POINTER(_sz), ctypes.c_int]
+    L.gs_degree_export.argtypes = [_vp, _vp, _vp, _sz, ctypes.POINTER(_sz), ctypes.c_int]
+    L.gs_degree_distribution_device.argtypes = [_vp, _vp, _vp, _sz, ctypes.POINTER(_sz)]
+    L.gs_degree_distribution.argtypes = [_vp, _vp, _vp, _sz, ctypes.POINTER(_sz)]
     L.gs_testing_set.argtypes = [ctypes.c_int, _i64]
     L.gs_testing_get.argtypes = [ctypes.c_int]
     L.gs_testing_get.restype = _i64
@@ -207,7 +225,7 @@ def hbm_bytes(device=0):
 def create_bytes(kind, capacity_hint):
     """gs_create_bytes: the device bytes gs_create(kind, capacity_hint) allocates."""
     b = _u64()
-    k = {"cc": KIND_CC, "signed": KIND_SIGNED}[kind] if isinstance(kind, str) else int(kind)
+    k = {"cc": KIND_CC, "signed": KIND_SIGNED, "degree": KIND_DEGREE}[kind] if isinstance(kind, str) else int(kind)
     _check(lib().gs_create_bytes(k, int(capacity_hint), ctypes.byref(b)))
     return b.value
 
@@ -235,7 +253,7 @@ def digest_rows(v, label, parity=None):
 # ---------------------------------------------------------------- test controls
 # include/gs_testing.h: private knobs the tests use (the product reads no environment)
 TESTING_KNOBS = {"server_idle_us": 0, "changes_walk_max": 1, "parse_lb_timeout_us": 2, "group_self_apply": 3,
-                 "group_data_lag": 4}
+                 "group_data_lag": 4, "degree_variant": 5}
 
 
 def testing_set(knob, value):
@@ -702,6 +720,154 @@ class Summary:
         ms = ctypes.c_double()
         _check(lib().gs_capacity_stats(self._h, ctypes.byref(w), ctypes.byref(s_), ctypes.byref(ms)))
         return {"waits": w.value, "syncs": s_.value, "wait_ms": ms.value}
+
+
+# ---------------------------------------------------------------- degree summary
+class Degrees:
+    """Streaming vertex degrees and their distribution (GS_KIND_DEGREE; the gs_degree_*
+    section of include/gs_summary.h): SimpleEdgeStream.getDegrees / getInDegrees /
+    getOutDegrees for direction "all" / "in" / "out", with optional edge deletions
+    (example/DegreeDistribution.java). Owns a gs_handle."""
+
+    DIRECTIONS = {"all": DEGREE_ALL, "in": DEGREE_IN, "out": DEGREE_OUT}
+
+    def __init__(self, direction="all", device=0, capacity_hint=1 << 20):
+        self.dir = self.DIRECTIONS[direction] if isinstance(direction, str) else int(direction)
+        self.device = device
+        h = _vp()
+        _check(lib().gs_create(ctypes.byref(h), device, KIND_DEGREE, capacity_hint))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().gs_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def stream(self):
+        s = _vp()
+        _check(lib().gs_get_stream(self._h, ctypes.byref(s)))
+        return s.value
+
+    def reset(self):
+        _check(lib().gs_reset(self._h))
+
+    def sync(self):
+        _check(lib().gs_sync(self._h))
+
+    def num_vertices(self):
+        """Table entries: every vertex ever collected, those whose net count is <= 0 included."""
+        n = _u64()
+        _check(lib().gs_num_vertices(self._h, ctypes.byref(n)))
+        return n.value
+
+    def table_capacity(self):
+        n = _u64()
+        _check(lib().gs_table_capacity(self._h, ctypes.byref(n)))
+        return n.value
+
+    def wait_stream(self, stream="torch"):
+        if isinstance(stream, str):
+            import torch
+            stream = torch.cuda.current_stream(self.device)
+        raw = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
+        _check(lib().gs_wait_stream(self._h, raw))
+
+    # --- fold / combine
+    def fold(self, src, dst, deletions=None):
+        """Fold host edges (int64 arrays); deletions: optional uint8 per edge, bit 0 = deletion."""
+        s = np.ascontiguousarray(np.asarray(src, dtype=np.int64))
+        d = np.ascontiguousarray(np.asarray(dst, dtype=np.int64))
+        assert s.shape == d.shape
+        e = None
+        if deletions is not None:
+            e = np.ascontiguousarray(np.asarray(deletions, dtype=np.uint8))
+            assert e.shape == s.shape
+        _check(lib().gs_degree_fold(self._h, s.ctypes.data, d.ctypes.data, _ptr(e), len(s), self.dir))
+
+    def fold_device(self, src, dst, n=None, stride=1, deletions=None, after=None):
+        """Fold device-resident edges (torch tensors on this device or raw pointers), queued on
+        the summary's stream; `after`: a stream the edges were written on (Summary.fold_device)."""
+        if n is None:
+            n = src.numel() // (stride if stride > 1 else 1)
+        if after is not None:
+            self.wait_stream(after)
+        _check(lib().gs_degree_fold_device(self._h, _ptr(src), _ptr(dst), _ptr(deletions), int(n), int(stride),
+                                           self.dir))
+
+    def combine(self, other):
+        """self += other (other unchanged)."""
+        _check(lib().gs_combine(self._h, other._h))
+
+    def serialize(self):
+        ln = _sz()
+        _check(lib().gs_serialize(self._h, None, 0, ctypes.byref(ln)))
+        buf = ctypes.create_string_buffer(max(ln.value, 1))
+        _check(lib().gs_serialize(self._h, buf, ln.value, ctypes.byref(ln)))
+        return buf.raw[: ln.value]
+
+    def deserialize(self, data):
+        buf = ctypes.create_string_buffer(bytes(data), len(data))
+        _check(lib().gs_deserialize(self._h, buf, len(data)))
+
+    # --- queries
+    def find_device(self, v, degree, found=None, n=None):
+        """degree[i] = degree of the DEVICE id v[i] (0 when absent), found[i] = 1 when > 0.
+        Asynchronous on self.stream."""
+        n = v.numel() if n is None else n
+        _check(lib().gs_degree_find_device(self._h, _ptr(v), int(n), _ptr(degree), _ptr(found)))
+
+    def degrees(self, sorted=True):
+        """(vertex, degree) numpy int64 arrays of the vertices with degree > 0; sorted: ascending
+        by vertex (on the device)."""
+        got = _sz()
+        n = max(self.num_vertices(), 1)  # the rows are a subset of the table entries
+        v = np.empty(n, np.int64)
+        d = np.empty(n, np.int64)
+        _check(lib().gs_degree_export(self._h, v.ctypes.data, d.ctypes.data, n, ctypes.byref(got),
+                                      1 if sorted else 0))
+        return v[: got.value].copy(), d[: got.value].copy()
+
+    def degrees_device(self, v, degree, sorted=False):
+        """The same rows into DEVICE arrays (capacity v.numel()); returns the row count."""
+        got = _sz()
+        cap = v.numel() if hasattr(v, "numel") else len(v)
+        _check(lib().gs_degree_export_device(self._h, _ptr(v), _ptr(degree), cap, ctypes.byref(got),
+                                             1 if sorted else 0))
+        return got.value
+
+    def distribution(self):
+        """(degree, count) numpy int64 arrays: the distinct degrees ascending and the number of
+        vertices of each (the final state of DegreeDistributionMap)."""
+        got = _sz()
+        n = max(self.num_vertices(), 1)  # at most one distinct degree per vertex
+        d = np.empty(n, np.int64)
+        c = np.empty(n, np.int64)
+        _check(lib().gs_degree_distribution(self._h, d.ctypes.data, c.ctypes.data, n, ctypes.byref(got)))
+        return d[: got.value].copy(), c[: got.value].copy()
+
+    def distribution_device(self, degree, count):
+        """The distribution into DEVICE int64 arrays (capacity degree.numel()); returns its length."""
+        got = _sz()
+        cap = degree.numel() if hasattr(degree, "numel") else len(degree)
+        _check(lib().gs_degree_distribution_device(self._h, _ptr(degree), _ptr(count), cap, ctypes.byref(got)))
+        return got.value
 
 
 # ---------------------------------------------------------------- native multi-GPU group

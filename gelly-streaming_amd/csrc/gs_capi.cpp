@@ -69,7 +69,7 @@ hipError_t dfree(void* p) {
 }
 
 // include/gs_testing.h: process-wide test knobs, -1 = unset (the product value)
-std::atomic<int64_t> g_testing[GS_TESTING_KNOBS] = {{-1}, {-1}, {-1}, {-1}, {-1}};
+std::atomic<int64_t> g_testing[GS_TESTING_KNOBS] = {{-1}, {-1}, {-1}, {-1}, {-1}, {-1}};
 
 int64_t testing_value(int knob, int64_t product) {
   const int64_t v = g_testing[knob].load(std::memory_order_relaxed);
@@ -394,10 +394,18 @@ int ensure_capacity(gs_summary* h, size_t n) {
   return GS_OK;
 }
 
-int check(gs_handle h) {
+// Entry points every kind serves (lifecycle, ordering, counts, combine, checkpoint).
+int check_any(gs_handle h) {
   if (!h) return fail(GS_ERR_INVALID, "null handle");
   ++h->api_calls;  // (a group orders its own-fold lanes behind the handle stream after any call)
   return GS_OK;
+}
+
+// Entry points of the forest kinds: a degree summary has no forest (its link words are counters).
+int check(gs_handle h) {
+  if (h && h->kind == GS_KIND_DEGREE)
+    return fail(GS_ERR_INVALID, "not available on a degree summary (use the gs_degree_* calls)");
+  return check_any(h);
 }
 
 }  // namespace
@@ -857,7 +865,8 @@ int gs_version(void) { return 20000; }
 int gs_create(gs_handle* out, int device, int kind, uint64_t capacity_hint) {
   if (!out) return fail(GS_ERR_INVALID, "out is null");
   *out = nullptr;
-  if (kind != GS_KIND_CC && kind != GS_KIND_SIGNED) return fail(GS_ERR_INVALID, "unknown kind");
+  if (kind != GS_KIND_CC && kind != GS_KIND_SIGNED && kind != GS_KIND_DEGREE)
+    return fail(GS_ERR_INVALID, "unknown kind");
   int ndev = 0;
   GS_HIP(hipGetDeviceCount(&ndev));
   if (device < 0 || device >= ndev) return fail(GS_ERR_HIP, "no HIP device " + std::to_string(device));
@@ -945,7 +954,7 @@ int gs_destroy(gs_handle h) {
 }
 
 int gs_reset(gs_handle h) {
-  if (int rc = check(h)) return rc;
+  if (int rc = check_any(h)) return rc;
   DeviceGuard g(h->device);
   if (int rc_ = join_lanes(h)) return rc_;
   const bool by_list = use_vertex_list(h, h->nv_ub);
@@ -969,11 +978,12 @@ int gs_reset(gs_handle h) {
   h->vlist_ok = true;
   reset_capacity_tracking(h, 0);
   for (uint64_t& f : h->delta_fill_ub) f = 0;
+  h->deg_total = 0;
   return GS_OK;
 }
 
 int gs_reset_config(gs_handle h) {
-  if (int rc = check(h)) return rc;
+  if (int rc = check_any(h)) return rc;
   if (h->side) return fail(GS_ERR_INVALID, "the summary belongs to an exchange group: destroy the group first");
   DeviceGuard g(h->device);
   if (int rc = join_lanes(h)) return rc;
@@ -1132,7 +1142,7 @@ int gs_fold_device(gs_handle h, const int64_t* src, const int64_t* dst, const ui
 // handle stream: a wait stops it first, so the next window starts a new
 // server launch queued behind the wait.
 int gs_wait_event(gs_handle h, void* event) {
-  if (int rc = check(h)) return rc;
+  if (int rc = check_any(h)) return rc;
   if (!event) return fail(GS_ERR_INVALID, "null event");
   DeviceGuard g(h->device);
   if (int rc = server_stop(h)) return rc;
@@ -1146,7 +1156,7 @@ int gs_wait_event(gs_handle h, void* event) {
 }
 
 int gs_wait_stream(gs_handle h, void* stream) {
-  if (int rc = check(h)) return rc;
+  if (int rc = check_any(h)) return rc;
   DeviceGuard g(h->device);
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (st == h->stream) return GS_OK;
@@ -1195,14 +1205,14 @@ int gs_fold_records_counted_device(gs_handle h, const int64_t* rec, size_t cap, 
 }
 
 int gs_sync(gs_handle h) {
-  if (int rc = check(h)) return rc;
+  if (int rc = check_any(h)) return rc;
   DeviceGuard g(h->device);
   if (int rc_ = join_lanes(h)) return rc_;
   return check_device_flags(h);  // its one stream sync completes all queued work
 }
 
 int gs_num_vertices(gs_handle h, uint64_t* n) {
-  if (int rc = check(h)) return rc;
+  if (int rc = check_any(h)) return rc;
   if (!n) return fail(GS_ERR_INVALID, "n is null");
   DeviceGuard g(h->device);
   int rc = read_nv(h, n);
@@ -1544,10 +1554,11 @@ int gs_export_components(gs_handle h, int64_t* comp, uint64_t* offset, int64_t* 
 // count and src's verdict on the device: no host synchronisation and no allocation
 // once the scratch is sized.
 int gs_combine(gs_handle dst, gs_handle src) {
-  if (int rc = check(dst)) return rc;
-  if (int rc = check(src)) return rc;
+  if (int rc = check_any(dst)) return rc;
+  if (int rc = check_any(src)) return rc;
   if (dst == src) return GS_OK;
   if (dst->kind != src->kind) return fail(GS_ERR_INVALID, "summaries of different kinds");
+  if (dst->kind == GS_KIND_DEGREE) return degree_combine(dst, src);
   const bool sign = dst->kind == GS_KIND_SIGNED;
   uint64_t bound = 0;
   {
@@ -1617,8 +1628,9 @@ int gs_combine_exported_device(gs_handle h, const int64_t* v, const int64_t* lab
 
 // Serialized image: u32 magic 'GSS1', u32 kind, u32 ok, u32 0, u64 n, int64 v[n], int64 label[n], u8 parity[n]
 int gs_serialize(gs_handle h, void* buf, size_t cap, size_t* len) {
-  if (int rc = check(h)) return rc;
+  if (int rc = check_any(h)) return rc;
   if (!len) return fail(GS_ERR_INVALID, "len is null");
+  if (h->kind == GS_KIND_DEGREE) return degree_serialize(h, buf, cap, len);
   DeviceGuard g(h->device);
   uint64_t nv = 0;
   int rc = read_nv(h, &nv);
@@ -1650,7 +1662,7 @@ int gs_serialize(gs_handle h, void* buf, size_t cap, size_t* len) {
 }
 
 int gs_deserialize(gs_handle h, const void* buf, size_t len) {
-  if (int rc = check(h)) return rc;
+  if (int rc = check_any(h)) return rc;
   if (!buf || len < 24) return fail(GS_ERR_INVALID, "truncated image");
   const uint8_t* b = static_cast<const uint8_t*>(buf);
   uint32_t hdr[4];
@@ -1662,6 +1674,7 @@ int gs_deserialize(gs_handle h, const void* buf, size_t len) {
   if (len < 24 + n * 17) return fail(GS_ERR_INVALID, "truncated image");
   int rc = gs_reset(h);
   if (rc) return rc;
+  if (h->kind == GS_KIND_DEGREE) return degree_deserialize(h, buf, n, hdr[3]);
   DeviceGuard g(h->device);
   if (!hdr[2]) {
     GS_HIP(hipMemsetAsync(h->ctr + gs::ctr_index(gs::CTR_FAIL), 1, 1, h->stream));
@@ -1870,7 +1883,7 @@ int gs_fold_exchange_device(gs_handle h, const int64_t* recv, const uint64_t* co
 }
 
 int gs_get_stream(gs_handle h, void** stream) {
-  if (int rc = check(h)) return rc;
+  if (int rc = check_any(h)) return rc;
   if (!stream) return fail(GS_ERR_INVALID, "stream is null");
   {
     DeviceGuard g(h->device);
@@ -2049,13 +2062,35 @@ int gs_set_pipelining(gs_handle h, int depth) {
 }
 
 int gs_table_capacity(gs_handle h, uint64_t* slots) {
-  if (int rc = check(h)) return rc;
+  if (int rc = check_any(h)) return rc;
   if (!slots) return fail(GS_ERR_INVALID, "slots is null");
   *slots = h->cap;
   return GS_OK;
 }
 
 }  // extern "C"
+
+// gs_internal.hpp: what gs_degree.cpp shares with this file
+namespace gsi {
+
+int x_scratch(gs_summary* h, uint64_t rows) {
+  if (int rc = ensure_x(h, rows)) return rc;
+  return wait_x_consumer(h);
+}
+
+void exact_count(gs_summary* h, uint64_t nv) { note_exact_count(h, nv); }
+
+int rebuild_table(gs_summary* h, uint64_t cap) {
+  (void)dfree(h->tab);
+  h->tab = nullptr;
+  return alloc_table(h, cap, /*keep_delta=*/true);
+}
+
+int sort_scratch(gs_summary* h, uint64_t rows) { return ensure_sort_scratch(h, rows); }
+int comp_staging(gs_summary* h, uint64_t nv, uint64_t nc) { return ensure_comp_staging(h, nv, nc); }
+int dev_stage(gs_summary* h, size_t edges) { return ensure_dev_stage(h, edges); }
+
+}  // namespace gsi
 
 extern "C" int gs_testing_set(int knob, int64_t value) {
   if (knob < 0 || knob >= GS_TESTING_KNOBS) return gsi::fail(GS_ERR_INVALID, "unknown test knob");
@@ -2065,7 +2100,7 @@ extern "C" int gs_testing_set(int knob, int64_t value) {
 
 extern "C" int64_t gs_testing_get(int knob) {
   if (knob < 0 || knob >= GS_TESTING_KNOBS) return -1;
-  static const int64_t product[GS_TESTING_KNOBS] = {2000, 1 << 16, 50000, 0, 2};
+  static const int64_t product[GS_TESTING_KNOBS] = {2000, 1 << 16, 50000, 0, 2, 0};
   return gsi::testing_value(knob, product[knob]);
 }
 
@@ -2078,7 +2113,8 @@ extern "C" int gs_hbm_bytes(int device, uint64_t* bytes) {
 
 extern "C" int gs_create_bytes(int kind, uint64_t capacity_hint, uint64_t* bytes) {
   if (!bytes) return gsi::fail(GS_ERR_INVALID, "bytes is null");
-  if (kind != GS_KIND_CC && kind != GS_KIND_SIGNED) return gsi::fail(GS_ERR_INVALID, "unknown kind");
+  if (kind != GS_KIND_CC && kind != GS_KIND_SIGNED && kind != GS_KIND_DEGREE)
+    return gsi::fail(GS_ERR_INVALID, "unknown kind");
   *bytes = gsi::create_bytes(gsi::create_capacity(capacity_hint));
   return GS_OK;
 }

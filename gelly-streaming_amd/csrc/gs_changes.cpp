@@ -97,6 +97,7 @@ extern "C" {
 
 int gs_set_change_tracking(gs_handle h, int on) {
   if (!h) return fail(GS_ERR_INVALID, "null handle");
+  if (h->kind == GS_KIND_DEGREE) return fail(GS_ERR_INVALID, "not available on a degree summary");
   DeviceGuard g(h->device);
   if (int rc = join_lanes(h)) return rc;
   if (!on) {
@@ -127,6 +128,7 @@ int gs_set_change_tracking(gs_handle h, int on) {
 
 int gs_take_changes_device(gs_handle h, int64_t* v, int64_t* label, uint8_t* parity, size_t cap, uint64_t* n) {
   if (!h) return fail(GS_ERR_INVALID, "null handle");
+  if (h->kind == GS_KIND_DEGREE) return fail(GS_ERR_INVALID, "not available on a degree summary");
   if (!n || (cap && (!v || !label))) return fail(GS_ERR_INVALID, "null argument");
   if (!h->changes) return fail(GS_ERR_INVALID, "change tracking is off");
   DeviceGuard g(h->device);
@@ -182,6 +184,7 @@ int gs_take_changes_device(gs_handle h, int64_t* v, int64_t* label, uint8_t* par
 // grow-only device scratch of the handle, then copied out (synchronises).
 int gs_take_changes(gs_handle h, int64_t* v, int64_t* label, uint8_t* parity, size_t cap, uint64_t* n) {
   if (!h) return fail(GS_ERR_INVALID, "null handle");
+  if (h->kind == GS_KIND_DEGREE) return fail(GS_ERR_INVALID, "not available on a degree summary");
   if (!n || (cap && (!v || !label))) return fail(GS_ERR_INVALID, "null argument");
   if (!h->changes) return fail(GS_ERR_INVALID, "change tracking is off");
   DeviceGuard g(h->device);

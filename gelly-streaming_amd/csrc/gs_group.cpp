@@ -412,6 +412,7 @@ int gs_group_create(gs_group_t* out, gs_handle h, const void* id, int nranks, in
   if (!out || !id) return fail(GS_ERR_INVALID, "null argument");
   *out = nullptr;
   if (!h) return fail(GS_ERR_INVALID, "null handle");
+  if (h->kind == GS_KIND_DEGREE) return fail(GS_ERR_INVALID, "not available on a degree summary");
   if (nranks < 1 || rank < 0 || rank >= nranks) return fail(GS_ERR_INVALID, "bad group shape");
   if (batch_edges > kMaxGroupBatch) return fail(GS_ERR_INVALID, "batch_edges above 2^26");
   gs_comm_api api;
@@ -906,6 +907,7 @@ int gs_group_create_partitioned(gs_group_t* out, gs_handle h, const void* id, in
   if (!out || !id) return fail(GS_ERR_INVALID, "null argument");
   *out = nullptr;
   if (!h) return fail(GS_ERR_INVALID, "null handle");
+  if (h->kind == GS_KIND_DEGREE) return fail(GS_ERR_INVALID, "not available on a degree summary");
   if (nranks < 1 || nranks > gs::kPartMaxRanks || rank < 0 || rank >= nranks)
     return fail(GS_ERR_INVALID, "bad group shape (1..64 ranks)");
   if (window_edges > kMaxGroupBatch) return fail(GS_ERR_INVALID, "window_edges above 2^26");

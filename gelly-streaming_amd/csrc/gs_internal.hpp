@@ -164,6 +164,9 @@ struct gs_summary {
   int64_t* co_member = nullptr;
   uint8_t* co_sign = nullptr;
   uint64_t co_vcap = 0, co_ccap = 0;
+  // degree summary (GS_KIND_DEGREE, gs_degree.cpp): endpoint occurrences folded since reset --
+  // the host-side bound that keeps every 32-bit counter below 2^31
+  uint64_t deg_total = 0;
   // text ingest (gs_fold_text): pinned + device text chunks, parsed edges, scratch
   char* h_text = nullptr;
   uint64_t* h_tres = nullptr;
@@ -302,5 +305,17 @@ bool use_vertex_list(gs_summary* h, uint64_t nv_bound);
 // gs_changes.cpp, after a reset (mode 0: vertex-list reset, 1: full table init) or a
 // rebuild into a new table (mode 2)
 int change_tracking_reset(gs_summary* h, int mode);
+// gs_capi.cpp internals the degree summary (gs_degree.cpp) shares
+int x_scratch(gs_summary* h, uint64_t rows);     // combine scratch x_v / x_l / x_p of >= rows rows, free to write
+void exact_count(gs_summary* h, uint64_t nv);    // an exact vertex count read with every queued fold complete
+int rebuild_table(gs_summary* h, uint64_t cap);  // free the table, allocate and initialise one of cap slots
+int sort_scratch(gs_summary* h, uint64_t rows);  // the radix sort's ping-pong buffers and tables
+int comp_staging(gs_summary* h, uint64_t nv, uint64_t nc);  // co_member / co_sign (nv), co_comp / co_off (nc)
+int dev_stage(gs_summary* h, size_t edges);      // device staging of host folds (d_stage, d_wstage)
+// gs_degree.cpp, called by the shared entry points of gs_capi.cpp on a degree summary
+int degree_grow(gs_summary* h, uint64_t new_cap);
+int degree_combine(gs_summary* dst, gs_summary* src);
+int degree_serialize(gs_summary* h, void* buf, size_t cap, size_t* len);
+int degree_deserialize(gs_summary* h, const void* buf, uint64_t n, uint32_t total);
 
 }  // namespace gsi

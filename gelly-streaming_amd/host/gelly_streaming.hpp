@@ -68,6 +68,15 @@ struct Edge {
   EV getValue() const { return f2; }
 };
 
+// Vertex<K, VV> is a Tuple2 (f0 = id, f1 = value).
+template <typename K, typename VV>
+struct Vertex {
+  K f0;
+  VV f1;
+  K getId() const { return f0; }
+  VV getValue() const { return f1; }
+};
+
 // EdgesFold.java:47 -- T foldEdges(T accum, K vertexID, K neighborID, EV edgeValue)
 template <typename K, typename EV, typename T>
 struct EdgesFold {
@@ -718,7 +727,61 @@ class SimpleEdgeStream {
     return summaryAggregation.run(edges_);
   }
 
+  // getDegrees / getInDegrees / getOutDegrees (SimpleEdgeStream.java:406-459): the reference
+  // emits a running Vertex<K, Long> per endpoint occurrence; these return the last value it
+  // emits per key -- the final degree of every vertex with one, ascending by id. The stream's
+  // edges are folded through a degree summary (gs_summary.h, GS_KIND_DEGREE) on `device`.
+  std::vector<Vertex<K, long>> getDegrees(int device = 0) const { return degrees(GS_DEGREE_ALL, device); }
+  std::vector<Vertex<K, long>> getInDegrees(int device = 0) const { return degrees(GS_DEGREE_IN, device); }
+  std::vector<Vertex<K, long>> getOutDegrees(int device = 0) const { return degrees(GS_DEGREE_OUT, device); }
+
+  // numberOfVertices (SimpleEdgeStream.java:366-386): the last value of the running count of
+  // distinct endpoints.
+  long numberOfVertices(int device = 0) const {
+    DegreeHandle d(device, edges_.edges.size());
+    fold_degrees(d.h, GS_DEGREE_ALL);
+    uint64_t n = 0;
+    gs_check(gs_num_vertices(d.h, &n));
+    return (long)n;
+  }
+
+  // numberOfEdges (SimpleEdgeStream.java:388-404): a host count.
+  long numberOfEdges() const { return (long)edges_.edges.size(); }
+
  private:
+  struct DegreeHandle {
+    gs_handle h = nullptr;
+    DegreeHandle(int device, size_t edges) {
+      gs_check(gs_create(&h, device, GS_KIND_DEGREE, std::max<size_t>(2 * edges, 16)));
+    }
+    ~DegreeHandle() { gs_destroy(h); }
+    DegreeHandle(const DegreeHandle&) = delete;
+    DegreeHandle& operator=(const DegreeHandle&) = delete;
+  };
+
+  void fold_degrees(gs_handle h, int dir) const {
+    const size_t n = edges_.edges.size();
+    std::vector<int64_t> src(n), dst(n);
+    for (size_t i = 0; i < n; ++i) {
+      src[i] = (int64_t)edges_.edges[i].getSource();
+      dst[i] = (int64_t)edges_.edges[i].getTarget();
+    }
+    gs_check(gs_degree_fold(h, src.data(), dst.data(), nullptr, n, dir));
+  }
+
+  std::vector<Vertex<K, long>> degrees(int dir, int device) const {
+    DegreeHandle d(device, edges_.edges.size());
+    fold_degrees(d.h, dir);
+    uint64_t nv = 0;
+    gs_check(gs_num_vertices(d.h, &nv));
+    std::vector<int64_t> v(nv + 1), deg(nv + 1);
+    size_t got = 0;
+    gs_check(gs_degree_export(d.h, v.data(), deg.data(), v.size(), &got, /*sorted=*/1));
+    std::vector<Vertex<K, long>> out(got);
+    for (size_t i = 0; i < got; ++i) out[i] = Vertex<K, long>{(K)v[i], (long)deg[i]};
+    return out;
+  }
+
   EdgeStream<K, EV> edges_;
 };
 

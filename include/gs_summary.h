@@ -46,7 +46,8 @@ enum gs_status {
 
 enum gs_kind {
   GS_KIND_CC = 0,     /* DisjointSet (DisjointSet.java:25-151) via ConnectedComponents */
-  GS_KIND_SIGNED = 1  /* Candidates (Candidates.java:27-196) via BipartitenessCheck  */
+  GS_KIND_SIGNED = 1, /* Candidates (Candidates.java:27-196) via BipartitenessCheck  */
+  GS_KIND_DEGREE = 2  /* vertex degrees and their distribution (the gs_degree_* section below) */
 };
 
 /* Last error message of the calling thread ("" if none). */
@@ -165,7 +166,8 @@ int gs_combine_exported_device(gs_handle h, const int64_t* v, const int64_t* lab
 /* Block until all work queued on the handle has finished. */
 int gs_sync(gs_handle h);
 
-/* Number of distinct vertices seen (DisjointSet.getMatches().size(), :44-46). */
+/* Number of distinct vertices seen (DisjointSet.getMatches().size(), :44-46). On a degree
+ * summary: the table entries, those whose net count is <= 0 included. */
 int gs_num_vertices(gs_handle h, uint64_t* n);
 
 /* Canonical label of one vertex: *label = min id of its component; *found = 0 if
@@ -350,6 +352,61 @@ int gs_take_changes_device(gs_handle h, int64_t* v, int64_t* label, uint8_t* par
 /* The same rows into HOST arrays (a JVM sink; parity may be
  * NULL); device scratch is kept in the handle. */
 int gs_take_changes(gs_handle h, int64_t* v, int64_t* label, uint8_t* parity, size_t cap, uint64_t* n);
+
+/* ---- degree summary (GS_KIND_DEGREE) -------------------------------------------------
+ * Streaming vertex degrees -- SimpleEdgeStream.getDegrees / getInDegrees / getOutDegrees
+ * (SimpleEdgeStream.java:366-478) -- and the degree distribution under edge additions and
+ * deletions (example/DegreeDistribution.java:52-132), folded on the device. The summary keeps
+ * one signed 32-bit NET count per vertex: occurrences added minus occurrences deleted.
+ *
+ * dir follows DegreeTypeSeparator (SimpleEdgeStream.java:440-459): GS_DEGREE_ALL adds 1 to the
+ * source and to the target of every edge (a self-loop counts 2, a repeated edge every time),
+ * GS_DEGREE_OUT to the source only, GS_DEGREE_IN to the target only. An endpoint that is not
+ * collected is neither looked up nor inserted (getInDegrees never emits a vertex without an
+ * in-edge). del (optional, may be NULL = every edge is an addition) holds one byte per edge,
+ * of which bit 0 is read: 0 = addition, 1 = deletion (EventType, DegreeDistribution.java:
+ * 73-78); a deletion subtracts 1.
+ *
+ * A vertex whose count is <= 0 is absent from the exports, from the distribution and for
+ * gs_degree_find_device (VertexDegreeCounts removes it, DegreeDistribution.java:98-101), but
+ * it stays a table entry: gs_num_vertices counts the entries, those at <= 0 included.
+ * One difference from the reference: it clamps at removal, so the deletion of an edge that
+ * was never added is forgotten there; here it stays in the net count. Streams whose every
+ * deletion removes an edge that is present give identical results.
+ *
+ * Overflow: the handle keeps the endpoint occurrences folded since the last reset (additions
+ * and deletions alike; gs_combine adds the source's total, gs_deserialize restores it). A
+ * call that would take that total past 2^31 - 1 fails with GS_ERR_CAPACITY and leaves the
+ * summary unchanged, so no counter can wrap.
+ *
+ * A degree summary also serves gs_destroy, gs_reset, gs_reset_config, gs_sync,
+ * gs_num_vertices, gs_get_stream, gs_wait_event, gs_wait_stream, gs_table_capacity,
+ * gs_combine (dst += src, same kind only) and gs_serialize / gs_deserialize (the image
+ * carries its kind); every other call above and below returns GS_ERR_INVALID on it, as the
+ * gs_degree_* calls do on a summary of another kind.
+ *
+ * gs_degree_fold: n edges from HOST arrays (copied before the call returns).
+ * gs_degree_fold_device: DEVICE arrays, element i = src[i*stride], dst[i*stride], del[i];
+ *   ordered like gs_fold_device (gs_wait_event / gs_wait_stream). Asynchronous.
+ * gs_degree_find_device: degree[i] = count of the DEVICE id v[i] when it is > 0, else 0;
+ *   found[i] (optional, may be NULL) = 1 when it is > 0. Asynchronous.
+ * gs_degree_export_device / gs_degree_export: the (vertex, degree) rows with degree > 0 into
+ *   DEVICE / HOST arrays of capacity cap; unordered, or with sorted != 0 ascending by vertex
+ *   in signed order (sorted on the device; the sort's scratch is kept in the handle and
+ *   counted by gs_hbm_bytes). *n on the host (synchronises); GS_ERR_TRUNCATED with *n set and
+ *   nothing written when cap < *n.
+ * gs_degree_distribution_device / gs_degree_distribution: degree[0..*n) the distinct degrees,
+ *   strictly ascending, count[i] the number of vertices of degree[i] -- the final state of
+ *   DegreeDistributionMap (DegreeDistribution.java:116-131). Same capacity rule. */
+enum gs_degree_dir { GS_DEGREE_ALL = 0, GS_DEGREE_IN = 1, GS_DEGREE_OUT = 2 };
+int gs_degree_fold(gs_handle h, const int64_t* src, const int64_t* dst, const uint8_t* del, size_t n, int dir);
+int gs_degree_fold_device(gs_handle h, const int64_t* src, const int64_t* dst, const uint8_t* del, size_t n,
+                          size_t stride, int dir);
+int gs_degree_find_device(gs_handle h, const int64_t* v, size_t n, int64_t* degree, uint8_t* found);
+int gs_degree_export_device(gs_handle h, int64_t* v, int64_t* degree, size_t cap, size_t* n, int sorted);
+int gs_degree_export(gs_handle h, int64_t* v, int64_t* degree, size_t cap, size_t* n, int sorted);
+int gs_degree_distribution_device(gs_handle h, int64_t* degree, int64_t* count, size_t cap, size_t* n);
+int gs_degree_distribution(gs_handle h, int64_t* degree, int64_t* count, size_t cap, size_t* n);
 
 /* ---- introspection -----------------------------------------------------------
  * The HIP stream (hipStream_t) the handle enqueues on, and per-kernel timing:

@@ -34,7 +34,11 @@ enum gs_testing_knob {
   /* exchange group (created afterwards): exchanges between an own fold and its data
    * half, 1..3 (product: 2) */
   GS_TESTING_GROUP_DATA_LAG = 4,
-  GS_TESTING_KNOBS = 5
+  /* degree fold: kernel variant of the measured alternatives (tools/degree_bench.py):
+   * 0 product, 1 no on-chip combining, 2 4096 LDS slots, 3 tile 1024, 4 2048 LDS slots,
+   * 5 diagnostic without the counter adds (counts stay 0) */
+  GS_TESTING_DEGREE_VARIANT = 5,
+  GS_TESTING_KNOBS = 6
 };
 
 /* Set knob `knob` to `value` (< 0: the product value). Returns GS_OK or GS_ERR_INVALID. */
