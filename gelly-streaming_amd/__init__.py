@@ -70,6 +70,10 @@ EXPORTED_SYMBOLS = (
     "gs_num_components", "gs_export_components_device", "gs_export_components",
     "gs_degree_fold", "gs_degree_fold_device", "gs_degree_find_device", "gs_degree_export_device",
     "gs_degree_export", "gs_degree_distribution_device", "gs_degree_distribution",
+    "gs_triangle_create", "gs_triangle_destroy", "gs_triangle_reset", "gs_triangle_fold", "gs_triangle_fold_device",
+    "gs_triangle_count", "gs_triangle_count_device", "gs_triangle_find_device", "gs_triangle_export_device",
+    "gs_triangle_export", "gs_triangle_sync", "gs_triangle_get_stream", "gs_triangle_wait_stream",
+    "gs_testing_triangle_stats",
 )
 
 # Pairs per workgroup of the component export's radix-sort kernels (csrc/gs_sort.hpp kSortTile):
@@ -79,6 +83,13 @@ SORT_TILE = 2048
 # Edges per workgroup of the degree fold (csrc/gs_degree.hpp DEGREE_TILE): the tile whose
 # endpoint occurrences are combined on chip; sizes around it are where a tile fills exactly.
 DEGREE_TILE = 2048
+
+# The triangle summary's count step (csrc/gs_triangle.hpp): lanes that share one new edge's
+# shorter row in the product, edges per workgroup of the per-edge passes, and the number of
+# work assignments gsamd.testing(triangle_variant=...) selects (0 is the product).
+TRIANGLE_LANES = 8
+TRIANGLE_TILE = 1024
+TRIANGLE_VARIANTS = 2
 
 FAIL_BIT = 1 << 62  # count words: a failed signed verdict (GS_FAIL_BIT)
 DIGEST_FAILED = (1 << 64) - 1  # gs_digest of a signed summary whose verdict failed (GS_DIGEST_FAILED)
@@ -207,6 +218,20 @@ def lib():
     L.gs_degree_export.argtypes = [_vp, _vp, _vp, _sz, ctypes.POINTER(_sz), ctypes.c_int]
     L.gs_degree_distribution_device.argtypes = [_vp, _vp, _vp, _sz, ctypes.POINTER(_sz)]
     L.gs_degree_distribution.argtypes = [_vp, _vp, _vp, _sz, ctypes.POINTER(_sz)]
+    L.gs_triangle_create.argtypes = [ctypes.POINTER(_vp), ctypes.c_int, _u64]
+    L.gs_triangle_destroy.argtypes = [_vp]
+    L.gs_triangle_reset.argtypes = [_vp]
+    L.gs_triangle_fold.argtypes = [_vp, _vp, _vp, _sz]
+    L.gs_triangle_fold_device.argtypes = [_vp, _vp, _vp, _sz, _sz]
+    L.gs_triangle_count.argtypes = [_vp, ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(_u64)]
+    L.gs_triangle_count_device.argtypes = [_vp, _vp]
+    L.gs_triangle_find_device.argtypes = [_vp, _vp, _sz, _vp, _vp]
+    L.gs_triangle_export_device.argtypes = [_vp, _vp, _vp, _sz, ctypes.POINTER(_sz), ctypes.c_int]
+    L.gs_triangle_export.argtypes = [_vp, _vp, _vp, _sz, ctypes.POINTER(_sz), ctypes.c_int]
+    L.gs_triangle_sync.argtypes = [_vp]
+    L.gs_triangle_get_stream.argtypes = [_vp, ctypes.POINTER(_vp)]
+    L.gs_triangle_wait_stream.argtypes = [_vp, _vp]
+    L.gs_testing_triangle_stats.argtypes = [_vp, ctypes.POINTER(_u64)]
     L.gs_testing_set.argtypes = [ctypes.c_int, _i64]
     L.gs_testing_get.argtypes = [ctypes.c_int]
     L.gs_testing_get.restype = _i64
@@ -253,7 +278,7 @@ def digest_rows(v, label, parity=None):
 # ---------------------------------------------------------------- test controls
 # include/gs_testing.h: private knobs the tests use (the product reads no environment)
 TESTING_KNOBS = {"server_idle_us": 0, "changes_walk_max": 1, "parse_lb_timeout_us": 2, "group_self_apply": 3,
-                 "group_data_lag": 4, "degree_variant": 5}
+                 "group_data_lag": 4, "degree_variant": 5, "triangle_variant": 6, "triangle_profile": 7}
 
 
 def testing_set(knob, value):
@@ -868,6 +893,127 @@ class Degrees:
         cap = degree.numel() if hasattr(degree, "numel") else len(degree)
         _check(lib().gs_degree_distribution_device(self._h, _ptr(degree), _ptr(count), cap, ctypes.byref(got)))
         return got.value
+
+
+# ---------------------------------------------------------------- triangle summary
+class Triangles:
+    """Exact triangle counts of a streamed graph (the gs_triangle_* section of
+    include/gs_summary.h): the count of each window's graph (example/WindowTriangles: `window`)
+    or the running global and per-vertex counts of an insertion-only stream
+    (example/ExactTriangleCount: `fold` after `fold`). Direction, repeated edges and self-loops
+    do not change the graph. Owns a gs_triangles handle."""
+
+    def __init__(self, device=0, edge_hint=1 << 20):
+        self.device = device
+        h = _vp()
+        _check(lib().gs_triangle_create(ctypes.byref(h), device, int(edge_hint)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().gs_triangle_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def stream(self):
+        s = _vp()
+        _check(lib().gs_triangle_get_stream(self._h, ctypes.byref(s)))
+        return s.value
+
+    def reset(self):
+        """The graph empty and every counter zero; capacity is kept."""
+        _check(lib().gs_triangle_reset(self._h))
+
+    def sync(self):
+        _check(lib().gs_triangle_sync(self._h))
+
+    def wait_stream(self, stream="torch"):
+        if isinstance(stream, str):
+            import torch
+            stream = torch.cuda.current_stream(self.device)
+        raw = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
+        _check(lib().gs_triangle_wait_stream(self._h, raw))
+
+    def fold(self, src, dst):
+        """Fold host edges (int64 arrays)."""
+        s = np.ascontiguousarray(np.asarray(src, dtype=np.int64))
+        d = np.ascontiguousarray(np.asarray(dst, dtype=np.int64))
+        assert s.shape == d.shape
+        _check(lib().gs_triangle_fold(self._h, s.ctypes.data, d.ctypes.data, len(s)))
+
+    def fold_device(self, src, dst, n=None, stride=1, after=None):
+        """Fold device-resident edges (torch tensors on this device or raw pointers), queued on
+        the handle's stream; `after`: a stream the edges were written on (Degrees.fold_device).
+        The fold synchronises with the host once (the number of new edges)."""
+        if n is None:
+            n = src.numel() // (stride if stride > 1 else 1)
+        if after is not None:
+            self.wait_stream(after)
+        _check(lib().gs_triangle_fold_device(self._h, _ptr(src), _ptr(dst), int(n), int(stride)))
+
+    def count(self):
+        """(triangles, edges, vertices) of the graph folded so far. Synchronises."""
+        t, e, v = _u64(), _u64(), _u64()
+        _check(lib().gs_triangle_count(self._h, ctypes.byref(t), ctypes.byref(e), ctypes.byref(v)))
+        return t.value, e.value, v.value
+
+    def count_device(self, out):
+        """The same three 64-bit words into DEVICE memory; asynchronous on self.stream."""
+        _check(lib().gs_triangle_count_device(self._h, _ptr(out)))
+
+    def find_device(self, v, count, found=None, n=None):
+        """count[i] = triangles through the DEVICE id v[i] (0 when absent), found[i] = 1 when
+        v[i] is a vertex of the graph. Asynchronous on self.stream."""
+        n = v.numel() if n is None else n
+        _check(lib().gs_triangle_find_device(self._h, _ptr(v), int(n), _ptr(count), _ptr(found)))
+
+    def local_counts(self, nonzero_only=False):
+        """(vertex, triangles through it) numpy int64 arrays, ascending by vertex."""
+        got = _sz()
+        n = max(self.count()[2], 1)
+        v = np.empty(n, np.int64)
+        c = np.empty(n, np.int64)
+        _check(lib().gs_triangle_export(self._h, v.ctypes.data, c.ctypes.data, n, ctypes.byref(got),
+                                        1 if nonzero_only else 0))
+        return v[: got.value].copy(), c[: got.value].copy()
+
+    def local_counts_device(self, v, count, nonzero_only=False):
+        """The same rows into DEVICE arrays (capacity v.numel()); returns the row count."""
+        got = _sz()
+        cap = v.numel() if hasattr(v, "numel") else len(v)
+        _check(lib().gs_triangle_export_device(self._h, _ptr(v), _ptr(count), cap, ctypes.byref(got),
+                                               1 if nonzero_only else 0))
+        return got.value
+
+    def window(self, src, dst):
+        """The triangle count of the graph of one window of host edges: reset, fold, count."""
+        self.reset()
+        self.fold(src, dst)
+        return self.count()[0]
+
+    def stats(self):
+        """gs_testing_triangle_stats: intersection steps and the longest row met since reset, and
+        the phase times (microseconds) of the last fold under testing(triangle_profile=1)."""
+        out = (_u64 * 6)()
+        _check(lib().gs_testing_triangle_stats(self._h, out))
+        return {"steps": out[0], "hot_row": out[1], "canon_us": out[2], "sort_dedup_us": out[3], "merge_us": out[4],
+                "count_us": out[5]}
 
 
 # ---------------------------------------------------------------- native multi-GPU group

@@ -1,0 +1,591 @@
+// gs_triangle.cpp -- the triangle summary behind include/gs_summary.h's gs_triangle_* section:
+// exact triangle counts of the graph G folded so far, global (T) and per vertex (t(v)), per
+// window (reset, fold, read: example/WindowTriangles) or running (fold after fold:
+// example/ExactTriangleCount). State layout, the once-only rule and the kernels are described
+// in gs_triangle.hpp / gs_triangle_k.hip and DESIGN.md section 6c.
+//
+// A fold of n edges: canonise; sort by (min, max) with two stable passes of gs_sort_k.hip's
+// radix sort; drop loops, repeats and pairs already in A (the new edges N); ONE host
+// synchronisation to learn |N| and the vertex count, after which the table and the adjacency
+// buffers grow when they must; sort N's reverse entries; merge A, N and reverse N into the
+// other adjacency buffer; per new edge insert the endpoints and find their rows; count.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "gs_internal.hpp"
+#include "gs_triangle.hpp"
+
+using namespace gsi;
+
+struct gs_triangles_s {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  hipEvent_t ext_ev = nullptr;
+  // relabel table with the counters t(v)
+  gs::Slot* tab = nullptr;
+  uint64_t cap = 0;
+  int logcap = 0;
+  uint32_t* ctr = nullptr;
+  unsigned long long* ctl = nullptr;  // gs::TriCtl words
+  // adjacency: two buffers, the merge of a fold reads one and writes the other
+  int64_t* ax[2] = {nullptr, nullptr};
+  int64_t* ay[2] = {nullptr, nullptr};
+  uint32_t* aseq[2] = {nullptr, nullptr};
+  uint64_t acap[2] = {0, 0};
+  int cur = 0;
+  uint64_t entries = 0;  // live entries of buffer `cur` (2 |G|)
+  uint64_t edges = 0;    // |G|, exact after every fold
+  uint32_t seq = 0;      // number of the last fold
+  // fold scratch, sized for f_cap elements
+  uint64_t f_cap = 0;
+  int64_t* stage = nullptr;  // [2][f_cap] host folds
+  int64_t* lo = nullptr;     // canonical pairs; later the reverse entries of N
+  int64_t* hi = nullptr;
+  int64_t* nx = nullptr;     // N
+  int64_t* ny = nullptr;
+  gs::TriRowInfo* info = nullptr;
+  uint32_t* list1 = nullptr;
+  uint32_t* list2 = nullptr;
+  unsigned long long* skey[2] = {nullptr, nullptr};
+  uint32_t* spay[2] = {nullptr, nullptr};
+  uint32_t* stable = nullptr;
+  uint32_t* sctl = nullptr;
+  // flag / tile-count scratch of the dedup and of the exports, sized for g_cap elements
+  uint64_t g_cap = 0;
+  uint8_t* flags = nullptr;
+  uint32_t* blk = nullptr;
+  // device staging of the host export
+  uint64_t o_cap = 0;
+  int64_t* o_v = nullptr;
+  int64_t* o_c = nullptr;
+  // diagnostics (gs_testing_triangle_stats): phase times of the last profiled fold, microseconds
+  uint64_t phase_us[4] = {0, 0, 0, 0};
+
+  gs::Table table() const {
+    gs::Table t;
+    t.tab = tab;
+    t.ctr = ctr;
+    t.cap = (uint32_t)cap;
+    t.mask = (uint32_t)(cap - 1);
+    t.shift = 64 - logcap;
+    t.r0 = (uint32_t)cap;
+    t.vlist = nullptr;
+    t.vshard_cap = 0;
+    t.mark_new = 0;
+    t.hflags = nullptr;
+    return t;
+  }
+  gs::TriAdj adj() const {
+    gs::TriAdj a;
+    a.x = ax[cur];
+    a.y = ay[cur];
+    a.seq = aseq[cur];
+    a.n = entries;
+    return a;
+  }
+};
+
+namespace {
+
+// Adjacency entries are row indices of 32 bits (TriRowInfo, the sort's payload).
+constexpr uint64_t kTriMaxEntries = 0xFFFFFFFFull;
+constexpr uint64_t kTriMinCap = 64;
+
+int check_tri(gs_triangles t) {
+  if (!t) return fail(GS_ERR_INVALID, "null triangle handle");
+  return GS_OK;
+}
+
+int count_variant() {
+  const int64_t v = testing_value(GS_TESTING_TRIANGLE_VARIANT, gs::kTriangleProduct);
+  return v >= 0 && v < gs::kTriangleVariants ? (int)v : gs::kTriangleProduct;
+}
+
+template <typename T>
+void release(T*& p) {
+  (void)dfree(p);
+  p = nullptr;
+}
+
+uint64_t pow2_at_least(uint64_t x) {
+  uint64_t p = 1;
+  while (p < x) p <<= 1;
+  return p;
+}
+
+int alloc_table(gs_triangles_s* t, uint64_t cap) {
+  if (cap > kMaxCap) return fail(GS_ERR_CAPACITY, "vertex table would exceed 2^30 slots");
+  GS_HIP(dmalloc(&t->tab, (cap + 1) * sizeof(gs::Slot)));
+  t->cap = cap;
+  t->logcap = 0;
+  while ((1ull << t->logcap) < cap) ++t->logcap;
+  gs::launch_tri_init(t->table(), t->stream);
+  GS_HIP(hipGetLastError());
+  return GS_OK;
+}
+
+int ensure_adj(gs_triangles_s* t, int side, uint64_t need) {
+  if (t->acap[side] >= need) return GS_OK;
+  GS_HIP(hipStreamSynchronize(t->stream));
+  release(t->ax[side]);
+  release(t->ay[side]);
+  release(t->aseq[side]);
+  t->acap[side] = 0;
+  const uint64_t c = std::min<uint64_t>(kTriMaxEntries, need + need / 2);
+  GS_HIP(dmalloc(&t->ax[side], c * 8));
+  GS_HIP(dmalloc(&t->ay[side], c * 8));
+  GS_HIP(dmalloc(&t->aseq[side], c * 4));
+  t->acap[side] = c;
+  return GS_OK;
+}
+
+int ensure_flags(gs_triangles_s* t, uint64_t n) {
+  if (t->g_cap >= n) return GS_OK;
+  GS_HIP(hipStreamSynchronize(t->stream));
+  release(t->flags);
+  release(t->blk);
+  t->g_cap = 0;
+  const uint64_t c = n + n / 4;
+  GS_HIP(dmalloc(&t->flags, c));
+  GS_HIP(dmalloc(&t->blk, (gs::tri_blocks(c) + 1) * 4));
+  t->g_cap = c;
+  return GS_OK;
+}
+
+int ensure_fold_scratch(gs_triangles_s* t, uint64_t n) {
+  if (int rc = ensure_flags(t, n)) return rc;
+  if (!t->sctl) GS_HIP(dmalloc(&t->sctl, gs::kSortCtlWords * 4));
+  if (t->f_cap >= n) return GS_OK;
+  GS_HIP(hipStreamSynchronize(t->stream));
+  release(t->stage);
+  release(t->lo);
+  release(t->hi);
+  release(t->nx);
+  release(t->ny);
+  release(t->info);
+  release(t->list1);
+  release(t->list2);
+  for (int i = 0; i < 2; ++i) {
+    release(t->skey[i]);
+    release(t->spay[i]);
+  }
+  release(t->stable);
+  t->f_cap = 0;
+  const uint64_t c = gs::sort_blocks(n + n / 4) * gs::kSortTile;
+  GS_HIP(dmalloc(&t->stage, 2 * c * 8));
+  GS_HIP(dmalloc(&t->lo, c * 8));
+  GS_HIP(dmalloc(&t->hi, c * 8));
+  GS_HIP(dmalloc(&t->nx, c * 8));
+  GS_HIP(dmalloc(&t->ny, c * 8));
+  GS_HIP(dmalloc(&t->info, c * sizeof(gs::TriRowInfo)));
+  GS_HIP(dmalloc(&t->list1, c * 4));
+  GS_HIP(dmalloc(&t->list2, c * 4));
+  for (int i = 0; i < 2; ++i) {
+    GS_HIP(dmalloc(&t->skey[i], c * 8));
+    GS_HIP(dmalloc(&t->spay[i], c * 4));
+  }
+  GS_HIP(dmalloc(&t->stable, gs::kSortRadix * gs::sort_row_stride(gs::sort_blocks(c)) * 4));
+  t->f_cap = c;
+  return GS_OK;
+}
+
+// Stable radix passes over the digits of ids[payload] that `skip` does not mark; hist: the
+// eight 256-bin device rows of those keys. Continues from *cur / *side.
+int sort_by(gs_triangles_s* t, const int64_t* ids, uint64_t n, const uint32_t* hist, const bool* skip, gs::SortSrc* cur,
+            int* side) {
+  cur->key = nullptr;
+  cur->ids = ids;
+  cur->rows = n;
+  for (int p = 0; p < (int)gs::kSortPasses; ++p) {
+    if (skip && skip[p]) continue;
+    gs::launch_sort_pass(*cur, n, p, t->stable, hist + p * gs::kSortRadix, t->skey[*side], t->spay[*side], t->stream);
+    GS_HIP(hipGetLastError());
+    cur->key = t->skey[*side];
+    cur->pay = t->spay[*side];
+    cur->ids = nullptr;
+    *side ^= 1;
+  }
+  return GS_OK;
+}
+
+// A table of new_cap slots carrying every vertex's counter: A's row heads are the vertices.
+int grow_table(gs_triangles_s* t, uint64_t new_cap) {
+  if (new_cap > kMaxCap) return fail(GS_ERR_CAPACITY, "vertex table would exceed 2^30 slots");
+  const gs::Table old = t->table();
+  gs::Slot* old_tab = t->tab;
+  t->tab = nullptr;
+  if (int rc = alloc_table(t, new_cap)) {
+    t->tab = old_tab;  // (the old table still serves)
+    t->cap = old.cap;
+    t->logcap = 64 - old.shift;
+    return rc;
+  }
+  gs::launch_tri_rehash(old, t->table(), t->adj(), t->stream);
+  GS_HIP(hipGetLastError());
+  GS_HIP(hipStreamSynchronize(t->stream));
+  (void)dfree(old_tab);
+  return GS_OK;
+}
+
+struct PhaseTimer {
+  gs_triangles_s* t;
+  bool on;
+  hipEvent_t ev[5] = {};
+  PhaseTimer(gs_triangles_s* h, bool enable) : t(h), on(enable) {
+    for (int i = 0; on && i < 5; ++i)
+      if (hipEventCreate(&ev[i]) != hipSuccess) on = false;
+  }
+  void mark(int i) {
+    if (on) (void)hipEventRecord(ev[i], t->stream);
+  }
+  void finish(int last) {
+    if (!on) return;
+    (void)hipStreamSynchronize(t->stream);
+    for (int i = 0; i < 4; ++i) {
+      float ms = 0;
+      t->phase_us[i] = 0;
+      if (i < last && hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess) t->phase_us[i] = (uint64_t)(ms * 1000.0f);
+    }
+  }
+  ~PhaseTimer() {
+    for (int i = 0; i < 5; ++i)
+      if (ev[i]) (void)hipEventDestroy(ev[i]);
+  }
+};
+
+// n > 0 device elements src[i * stride], dst[i * stride] on t->stream
+int fold_impl(gs_triangles_s* t, const int64_t* src, const int64_t* dst, uint64_t n, uint64_t stride) {
+  if (int rc = ensure_fold_scratch(t, n)) return rc;
+  if (++t->seq == 0) {  // the fold numbers wrapped: every entry so far becomes fold 0
+    if (t->entries) GS_HIP(hipMemsetAsync(t->aseq[t->cur], 0, t->entries * 4, t->stream));
+    t->seq = 1;
+  }
+  PhaseTimer timer(t, testing_value(GS_TESTING_TRIANGLE_PROFILE, 0) == 1);
+  timer.mark(0);
+  // 1. canonise
+  gs::launch_tri_canon(src, dst, n, stride, t->lo, t->hi, t->stream);
+  GS_HIP(hipGetLastError());
+  timer.mark(1);
+  // 2. sort by max, then stably by min; flag, scan, compact: N in (nx, ny)
+  GS_HIP(hipMemsetAsync(t->sctl, 0, gs::kSortCtlWords * 4, t->stream));
+  gs::launch_sort_digits(t->lo, t->hi, n, t->sctl, t->stream);  // rows 0..7: min, rows 8..15: max
+  GS_HIP(hipGetLastError());
+  gs::SortSrc cur;
+  int side = 0;
+  if (int rc = sort_by(t, t->hi, n, t->sctl + gs::kSortPasses * gs::kSortRadix, nullptr, &cur, &side)) return rc;
+  if (int rc = sort_by(t, t->lo, n, t->sctl, nullptr, &cur, &side)) return rc;
+  gs::launch_tri_flag_new(cur.pay, t->lo, t->hi, n, t->adj(), t->flags, t->blk, t->stream);
+  GS_HIP(hipGetLastError());
+  gs::launch_tri_scan(t->blk, gs::tri_blocks(n), t->ctl, gs::TRI_NEW, -1, t->stream);
+  GS_HIP(hipGetLastError());
+  gs::launch_tri_compact_new(cur.pay, t->lo, t->hi, n, t->flags, t->blk, t->nx, t->ny, t->f_cap, t->stream);
+  GS_HIP(hipGetLastError());
+  // the fold's one host synchronisation: |N|, the vertex count, the digit histograms of max
+  unsigned long long words[4] = {0, 0, 0, 0};
+  std::vector<uint32_t> hist(gs::kSortPasses * gs::kSortRadix);
+  GS_HIP(hipMemcpyAsync(words, t->ctl, sizeof(words), hipMemcpyDeviceToHost, t->stream));
+  GS_HIP(hipMemcpyAsync(hist.data(), t->sctl + gs::kSortPasses * gs::kSortRadix, hist.size() * 4,
+                        hipMemcpyDeviceToHost, t->stream));
+  timer.mark(2);
+  GS_HIP(hipStreamSynchronize(t->stream));
+  const uint64_t m = words[gs::TRI_NEW], nv = words[gs::TRI_NV];
+  if (m > n) return fail(GS_ERR_HIP, "triangle fold: more new edges than elements");
+  if (m == 0) {
+    timer.finish(2);
+    return GS_OK;
+  }
+  // (a failure below -- out of device memory while growing -- leaves G and its counts as they were)
+  if ((double)(nv + 2 * m) > kMaxLoad * (double)t->cap) {
+    uint64_t nc = t->cap;
+    while (kMaxLoad * (double)nc < (double)(nv + 2 * m)) nc <<= 1;
+    if (int rc = grow_table(t, nc)) return rc;
+  }
+  const int other = t->cur ^ 1;
+  if (int rc = ensure_adj(t, other, t->entries + 2 * m)) return rc;
+  // 3. N ordered by (max, min): a stable sort of N by max. A digit on which every max of the
+  // fold agrees is an identity pass for N's subset of them.
+  bool skip[gs::kSortPasses];
+  for (int p = 0; p < (int)gs::kSortPasses; ++p) {
+    const uint32_t* gh = hist.data() + p * gs::kSortRadix;
+    skip[p] = *std::max_element(gh, gh + gs::kSortRadix) == n;
+  }
+  GS_HIP(hipMemsetAsync(t->sctl, 0, gs::kSortCtlWords * 4, t->stream));
+  gs::launch_sort_digits(t->ny, t->ny, m, t->sctl, t->stream);
+  GS_HIP(hipGetLastError());
+  cur = gs::SortSrc();
+  side = 0;
+  if (int rc = sort_by(t, t->ny, m, t->sctl, skip, &cur, &side)) return rc;
+  gs::launch_tri_reverse(cur.pay, t->nx, t->ny, m, t->lo, t->hi, t->stream);
+  GS_HIP(hipGetLastError());
+  gs::TriAdjOut out;
+  out.x = t->ax[other];
+  out.y = t->ay[other];
+  out.seq = t->aseq[other];
+  out.cap = t->acap[other];
+  gs::launch_tri_merge(t->adj(), t->nx, t->ny, t->lo, t->hi, m, out, t->seq, t->stream);
+  GS_HIP(hipGetLastError());
+  t->cur = other;
+  t->entries += 2 * m;
+  t->edges += m;
+  timer.mark(3);
+  // 4. rows and count
+  const int variant = count_variant();
+  GS_HIP(hipMemsetAsync(t->ctl + gs::TRI_BIN1, 0, 16, t->stream));
+  gs::launch_tri_rows(t->table(), t->ctl, t->adj(), t->nx, t->ny, m, t->info, t->list1, t->list2, variant, t->stream);
+  GS_HIP(hipGetLastError());
+  gs::launch_tri_count(t->table(), t->ctl, t->adj(), t->nx, t->ny, m, t->info, t->list1, t->list2, t->seq, variant,
+                       t->stream);
+  GS_HIP(hipGetLastError());
+  timer.mark(4);
+  timer.finish(4);
+  return GS_OK;
+}
+
+int fold_guard(gs_triangles_s* t, const void* src, const void* dst, size_t n) {
+  if (n && (!src || !dst)) return fail(GS_ERR_INVALID, "null edge arrays");
+  if (2 * (t->edges + (uint64_t)n) > kTriMaxEntries || (uint64_t)n > kTriMaxEntries)
+    return fail(GS_ERR_CAPACITY, "triangle adjacency: " + std::to_string(t->edges) + " + " + std::to_string(n) +
+                                     " edges could pass 2^32 - 1 entries, the sort payload's range");
+  return GS_OK;
+}
+
+int export_impl(gs_triangles_s* t, int64_t* v, int64_t* count, size_t cap, size_t* n, int nonzero_only, bool to_host) {
+  *n = 0;
+  if (t->entries == 0) {
+    GS_HIP(hipStreamSynchronize(t->stream));
+    return GS_OK;
+  }
+  if (int rc = ensure_flags(t, t->entries)) return rc;
+  const gs::TriAdj A = t->adj();
+  gs::launch_tri_flag_heads(t->table(), t->ctl, A, nonzero_only ? 1 : 0, t->flags, t->blk, t->stream);
+  GS_HIP(hipGetLastError());
+  gs::launch_tri_scan(t->blk, gs::tri_blocks(A.n), t->ctl, gs::TRI_ROWS, -1, t->stream);
+  GS_HIP(hipGetLastError());
+  unsigned long long rows = 0;
+  GS_HIP(hipMemcpyAsync(&rows, t->ctl + gs::TRI_ROWS, 8, hipMemcpyDeviceToHost, t->stream));
+  GS_HIP(hipStreamSynchronize(t->stream));
+  *n = rows;
+  if (cap < rows)
+    return fail(GS_ERR_TRUNCATED, "output capacity " + std::to_string(cap) + " < " + std::to_string(rows));
+  if (rows == 0) return GS_OK;
+  if (!v || !count) return fail(GS_ERR_INVALID, "null arrays");
+  int64_t *dv = v, *dc = count;
+  if (to_host) {
+    if (t->o_cap < rows) {
+      release(t->o_v);
+      release(t->o_c);
+      t->o_cap = 0;
+      const uint64_t c = rows + rows / 4;
+      GS_HIP(dmalloc(&t->o_v, c * 8));
+      GS_HIP(dmalloc(&t->o_c, c * 8));
+      t->o_cap = c;
+    }
+    dv = t->o_v;
+    dc = t->o_c;
+  }
+  gs::launch_tri_compact_rows(t->table(), t->ctl, A, t->flags, t->blk, dv, dc, rows, t->stream);
+  GS_HIP(hipGetLastError());
+  if (to_host) {
+    GS_HIP(hipMemcpyAsync(v, dv, rows * 8, hipMemcpyDeviceToHost, t->stream));
+    GS_HIP(hipMemcpyAsync(count, dc, rows * 8, hipMemcpyDeviceToHost, t->stream));
+  }
+  GS_HIP(hipStreamSynchronize(t->stream));
+  return GS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gs_triangle_destroy(gs_triangles t) {
+  if (!t) return GS_OK;
+  DeviceGuard g(t->device);
+  if (t->stream) (void)hipStreamSynchronize(t->stream);
+  release(t->tab);
+  release(t->ctr);
+  release(t->ctl);
+  for (int i = 0; i < 2; ++i) {
+    release(t->ax[i]);
+    release(t->ay[i]);
+    release(t->aseq[i]);
+    release(t->skey[i]);
+    release(t->spay[i]);
+  }
+  release(t->stage);
+  release(t->lo);
+  release(t->hi);
+  release(t->nx);
+  release(t->ny);
+  release(t->info);
+  release(t->list1);
+  release(t->list2);
+  release(t->stable);
+  release(t->sctl);
+  release(t->flags);
+  release(t->blk);
+  release(t->o_v);
+  release(t->o_c);
+  if (t->ext_ev) (void)hipEventDestroy(t->ext_ev);
+  if (t->stream) (void)hipStreamDestroy(t->stream);
+  delete t;
+  return GS_OK;
+}
+
+int gs_triangle_create(gs_triangles* out, int device, uint64_t edge_hint) {
+  if (!out) return fail(GS_ERR_INVALID, "out is null");
+  *out = nullptr;
+  int count = 0;
+  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail(GS_ERR_HIP, "no HIP device available");
+  if (device < 0 || device >= count) return fail(GS_ERR_INVALID, "bad device");
+  if (2 * edge_hint > kTriMaxEntries) return fail(GS_ERR_CAPACITY, "edge hint beyond 2^31 - 1 edges");
+  DeviceGuard g(device);
+  gs_triangles_s* t = new gs_triangles_s();
+  t->device = device;
+  int rc = GS_OK;
+  auto body = [&]() -> int {
+    GS_HIP(hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking));
+    GS_HIP(hipEventCreateWithFlags(&t->ext_ev, hipEventDisableTiming));
+    GS_HIP(dmalloc(&t->ctr, (size_t)gs::CTR_COUNT * gs::kCtrStride * 4));
+    GS_HIP(hipMemsetAsync(t->ctr, 0, (size_t)gs::CTR_COUNT * gs::kCtrStride * 4, t->stream));
+    GS_HIP(dmalloc(&t->ctl, gs::TRI_CTL_WORDS * 8));
+    GS_HIP(hipMemsetAsync(t->ctl, 0, gs::TRI_CTL_WORDS * 8, t->stream));
+    const uint64_t e = std::max<uint64_t>(edge_hint, kTriMinCap / 2);
+    if (int r = alloc_table(t, std::min<uint64_t>(kMaxCap, pow2_at_least(2 * e)))) return r;
+    if (int r = ensure_adj(t, 0, 2 * e)) return r;
+    GS_HIP(hipStreamSynchronize(t->stream));
+    return GS_OK;
+  };
+  rc = body();
+  if (rc) {
+    const std::string msg = gs_last_error();
+    (void)gs_triangle_destroy(t);
+    return fail(rc, msg);
+  }
+  *out = t;
+  return GS_OK;
+}
+
+int gs_triangle_reset(gs_triangles t) {
+  if (int rc = check_tri(t)) return rc;
+  DeviceGuard g(t->device);
+  gs::launch_tri_init(t->table(), t->stream);
+  GS_HIP(hipGetLastError());
+  GS_HIP(hipMemsetAsync(t->ctr, 0, (size_t)gs::CTR_COUNT * gs::kCtrStride * 4, t->stream));
+  GS_HIP(hipMemsetAsync(t->ctl, 0, gs::TRI_CTL_WORDS * 8, t->stream));
+  t->entries = 0;
+  t->edges = 0;
+  return GS_OK;
+}
+
+int gs_triangle_fold_device(gs_triangles t, const int64_t* src, const int64_t* dst, size_t n, size_t stride) {
+  if (int rc = check_tri(t)) return rc;
+  if (stride == 0 || stride > 0xFFFFFFFFull) return fail(GS_ERR_INVALID, "stride must be >= 1");
+  if (int rc = fold_guard(t, src, dst, n)) return rc;
+  if (n == 0) return GS_OK;
+  DeviceGuard g(t->device);
+  return fold_impl(t, src, dst, n, stride);
+}
+
+int gs_triangle_fold(gs_triangles t, const int64_t* src, const int64_t* dst, size_t n) {
+  if (int rc = check_tri(t)) return rc;
+  if (int rc = fold_guard(t, src, dst, n)) return rc;
+  if (n == 0) return GS_OK;
+  DeviceGuard g(t->device);
+  if (int rc = ensure_fold_scratch(t, n)) return rc;
+  int64_t *ds = t->stage, *dd = t->stage + t->f_cap;
+  GS_HIP(hipMemcpyAsync(ds, src, n * 8, hipMemcpyHostToDevice, t->stream));
+  GS_HIP(hipMemcpyAsync(dd, dst, n * 8, hipMemcpyHostToDevice, t->stream));
+  if (int rc = fold_impl(t, ds, dd, n, 1)) return rc;
+  GS_HIP(hipStreamSynchronize(t->stream));
+  return GS_OK;
+}
+
+int gs_triangle_count(gs_triangles t, uint64_t* triangles, uint64_t* edges, uint64_t* vertices) {
+  if (int rc = check_tri(t)) return rc;
+  if (!triangles || !edges || !vertices) return fail(GS_ERR_INVALID, "null count pointers");
+  DeviceGuard g(t->device);
+  unsigned long long w[3] = {0, 0, 0};
+  GS_HIP(hipMemcpyAsync(w, t->ctl, sizeof(w), hipMemcpyDeviceToHost, t->stream));
+  GS_HIP(hipStreamSynchronize(t->stream));
+  *triangles = w[gs::TRI_T];
+  *edges = w[gs::TRI_E];
+  *vertices = w[gs::TRI_NV];
+  return GS_OK;
+}
+
+int gs_triangle_count_device(gs_triangles t, uint64_t* out) {
+  if (int rc = check_tri(t)) return rc;
+  if (!out) return fail(GS_ERR_INVALID, "out is null");
+  DeviceGuard g(t->device);
+  GS_HIP(hipMemcpyAsync(out, t->ctl, 24, hipMemcpyDeviceToDevice, t->stream));
+  return GS_OK;
+}
+
+int gs_triangle_find_device(gs_triangles t, const int64_t* v, size_t n, int64_t* count, uint8_t* found) {
+  if (int rc = check_tri(t)) return rc;
+  if (n && (!v || !count)) return fail(GS_ERR_INVALID, "null arrays");
+  DeviceGuard g(t->device);
+  gs::launch_tri_find(t->table(), t->ctl, v, n, count, found, t->stream);
+  GS_HIP(hipGetLastError());
+  return GS_OK;
+}
+
+int gs_triangle_export_device(gs_triangles t, int64_t* v, int64_t* count, size_t cap, size_t* n, int nonzero_only) {
+  if (int rc = check_tri(t)) return rc;
+  if (!n) return fail(GS_ERR_INVALID, "n is null");
+  DeviceGuard g(t->device);
+  return export_impl(t, v, count, cap, n, nonzero_only, false);
+}
+
+int gs_triangle_export(gs_triangles t, int64_t* v, int64_t* count, size_t cap, size_t* n, int nonzero_only) {
+  if (int rc = check_tri(t)) return rc;
+  if (!n) return fail(GS_ERR_INVALID, "n is null");
+  DeviceGuard g(t->device);
+  return export_impl(t, v, count, cap, n, nonzero_only, true);
+}
+
+int gs_triangle_sync(gs_triangles t) {
+  if (int rc = check_tri(t)) return rc;
+  DeviceGuard g(t->device);
+  GS_HIP(hipStreamSynchronize(t->stream));
+  return GS_OK;
+}
+
+int gs_triangle_get_stream(gs_triangles t, void** stream) {
+  if (int rc = check_tri(t)) return rc;
+  if (!stream) return fail(GS_ERR_INVALID, "stream is null");
+  *stream = t->stream;
+  return GS_OK;
+}
+
+int gs_triangle_wait_stream(gs_triangles t, void* stream) {
+  if (int rc = check_tri(t)) return rc;
+  DeviceGuard g(t->device);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (st == t->stream) return GS_OK;
+  GS_HIP(hipEventRecord(t->ext_ev, st));  // (stream 0 = the device's null stream)
+  GS_HIP(hipStreamWaitEvent(t->stream, t->ext_ev, 0));
+  return GS_OK;
+}
+
+// gs_testing.h: out[0] = intersection steps since reset, out[1] = the longest row a new edge
+// met, out[2..5] = microseconds of the last profiled fold's canonise / sort and dedup / merge
+// / count phases. Synchronises.
+int gs_testing_triangle_stats(void* handle, uint64_t* out) {
+  gs_triangles t = static_cast<gs_triangles>(handle);
+  if (int rc = check_tri(t)) return rc;
+  if (!out) return fail(GS_ERR_INVALID, "out is null");
+  DeviceGuard g(t->device);
+  unsigned long long w[2] = {0, 0};
+  GS_HIP(hipMemcpyAsync(w, t->ctl + gs::TRI_STEPS, sizeof(w), hipMemcpyDeviceToHost, t->stream));
+  GS_HIP(hipStreamSynchronize(t->stream));
+  out[0] = w[0];
+  out[1] = w[1];
+  for (int i = 0; i < 4; ++i) out[2 + i] = t->phase_us[i];
+  return GS_OK;
+}
+
+}  // extern "C"

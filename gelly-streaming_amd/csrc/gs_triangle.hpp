@@ -1,0 +1,130 @@
+// gs_triangle.hpp -- host-side launchers of the triangle summary's kernels (gs_triangle_k.hip):
+// canonise, the flag / scan / compact passes of the dedup and of the exports, the three-way
+// merge into the sorted adjacency, the per-edge row pass and the intersection (count) kernels.
+// Every launch is queued on the given stream; kernel boundaries carry all ordering between
+// workgroups (no workgroup waits on another inside a launch, no load has to be fresh).
+//
+// State. The adjacency A holds every edge {u, v} of G as the two
+// directed entries (u, v) and (v, u): three parallel arrays x, y (the 64-bit ids themselves)
+// and seq (the number of the fold that added the edge), sorted by (x, y) in signed order. The
+// row of a vertex is the contiguous range of its x value (gs_triangle_rows.hpp). The counter
+// t(v) is the 64-bit word {link, aux} of v's slot in a relabel table of the existing layout
+// (gs_device.hpp):
+//   t(slot s) = (aux << 32 | link) - (s << 1)
+// so the table's initial state (link = s << 1, aux = 0) reads as zero. INT64_MIN, the table's
+// empty marker, keeps its presence flag and counter in two control words instead (the
+// reserved slot's aux bit would sit inside a 64-bit counter).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "gs_device.hpp"
+
+namespace gs {
+
+// Lanes that share one edge's shorter row in the product (gsamd.TRIANGLE_LANES): the lane
+// group of the binned count kernel's short bin.
+constexpr uint32_t TRIANGLE_LANES = 8;
+// Edges per workgroup of the per-edge passes (gsamd.TRIANGLE_TILE): canonise, flag, compact.
+constexpr uint32_t TRIANGLE_TILE = 1024;
+constexpr uint32_t kTriBS = 256;                       // threads of every workgroup but the scan's
+constexpr uint32_t kTriPer = TRIANGLE_TILE / kTriBS;   // consecutive elements per thread
+static_assert(TRIANGLE_TILE == kTriBS * kTriPer, "tile = threads x elements per thread");
+constexpr uint32_t kTriShortRow = 4 * TRIANGLE_LANES;  // binned: shorter rows up to here take a lane group
+constexpr uint32_t kTriWaveRow = 64;                   // binned: shorter rows above here may take a workgroup ...
+constexpr uint32_t kTriLdsRow = 4096;                  // ... when the longer row has at least this many entries
+constexpr uint32_t kTriSamples = 1024;                 // samples of the longer row staged in LDS (8 KiB)
+
+// Work assignment of the count step (GS_TESTING_TRIANGLE_VARIANT; tools/triangle_bench.py)
+enum TriangleVariant : int {
+  kTriangleBinned = 0,  // product: lane group of 8 / wave / workgroup with LDS samples, by row length
+  kTriangleWave = 1,    // one wave per new edge, 64 lanes striding the shorter row
+  kTriangleVariants = 2,
+  kTriangleProduct = kTriangleBinned
+};
+
+// control words (uint64) of a handle
+enum TriCtl : int {
+  TRI_T = 0,      // triangles of G        } the three words of
+  TRI_E = 1,      // edges of G            } gs_triangle_count_device,
+  TRI_NV = 2,     // vertices of G         } in this order
+  TRI_NEW = 3,    // new edges of the current fold
+  TRI_MINP = 4,   // INT64_MIN is a vertex
+  TRI_MINC = 5,   // t(INT64_MIN)
+  TRI_ROWS = 6,   // rows of the current export
+  TRI_BIN1 = 7,   // binned count: edges in the wave list
+  TRI_BIN2 = 8,   //               edges in the workgroup list
+  TRI_STEPS = 9,  // diagnostics: sum over new edges of the shorter row length, since reset
+  TRI_HOT = 10,   // diagnostics: the longest row a new edge met, since reset
+  TRI_CTL_WORDS = 16
+};
+
+struct TriAdj {
+  const int64_t* x = nullptr;
+  const int64_t* y = nullptr;
+  const uint32_t* seq = nullptr;
+  uint64_t n = 0;
+};
+
+struct TriAdjOut {
+  int64_t* x = nullptr;
+  int64_t* y = nullptr;
+  uint32_t* seq = nullptr;
+  uint64_t cap = 0;
+};
+
+// per new edge: the shorter row [sb, se) and the longer row [lb, le) of its endpoints in A,
+// and the table slots of the two endpoints
+struct TriRowInfo {
+  uint32_t sb, se, lb, le, ss, sl;
+};
+
+__host__ __device__ constexpr uint64_t tri_blocks(uint64_t n) { return (n + TRIANGLE_TILE - 1) / TRIANGLE_TILE; }
+
+// every slot empty, link = slot << 1, aux = 0 (slots 0 .. cap)
+void launch_tri_init(const Table& t, hipStream_t st);
+// lo[i] = min, hi[i] = max of element i (src[i * stride], dst[i * stride]); loops stay as lo == hi
+void launch_tri_canon(const int64_t* src, const int64_t* dst, uint64_t n, uint64_t stride, int64_t* lo, int64_t* hi,
+                      hipStream_t st);
+// Over the n rows (lo[pay[i]], hi[pay[i]]) sorted by (lo, hi): flags[i] = not a loop, not equal
+// to the row before, not in A; blk[b] = flagged rows of tile b.
+void launch_tri_flag_new(const uint32_t* pay, const int64_t* lo, const int64_t* hi, uint64_t n, const TriAdj& A,
+                         uint8_t* flags, uint32_t* blk, hipStream_t st);
+// Exclusive scan of blk[0 .. nb) in place (one workgroup); ctl[total_word] = the sum, also
+// added to ctl[add_word] when add_word >= 0.
+void launch_tri_scan(uint32_t* blk, uint64_t nb, unsigned long long* ctl, int total_word, int add_word,
+                     hipStream_t st);
+// the flagged rows in order into (nx, ny), at most cap of them
+void launch_tri_compact_new(const uint32_t* pay, const int64_t* lo, const int64_t* hi, uint64_t n,
+                            const uint8_t* flags, const uint32_t* blk, int64_t* nx, int64_t* ny, uint64_t cap,
+                            hipStream_t st);
+// rx[j] = ny[pay[j]], ry[j] = nx[pay[j]] for j < n (pay: the new edges ordered by (hi, lo))
+void launch_tri_reverse(const uint32_t* pay, const int64_t* nx, const int64_t* ny, uint64_t n, int64_t* rx,
+                        int64_t* ry, hipStream_t st);
+// O = merge of A, the forward entries (nx, ny) and the reverse entries (rx, ry), n_new each, all
+// sorted by (x, y) and disjoint; the new entries get fold number seq.
+void launch_tri_merge(const TriAdj& A, const int64_t* nx, const int64_t* ny, const int64_t* rx, const int64_t* ry,
+                      uint64_t n_new, const TriAdjOut& O, uint32_t seq, hipStream_t st);
+// Per new edge: insert both endpoints into the table (ctl[TRI_NV] += fresh ones), find their
+// rows in A, write info[e]; binned variant: append e to the wave / workgroup list by row length.
+// ctl[TRI_E] += n_new.
+void launch_tri_rows(const Table& t, unsigned long long* ctl, const TriAdj& A, const int64_t* nx, const int64_t* ny,
+                     uint64_t n_new, TriRowInfo* info, uint32_t* list1, uint32_t* list2, int variant,
+                     hipStream_t st);
+// the intersection: every triangle closed by a new edge counted once (the once-only rule)
+void launch_tri_count(const Table& t, unsigned long long* ctl, const TriAdj& A, const int64_t* nx, const int64_t* ny,
+                      uint64_t n_new, const TriRowInfo* info, const uint32_t* list1, const uint32_t* list2,
+                      uint32_t seq, int variant, hipStream_t st);
+// count[i] = t(v[i]) (0 when absent), found[i] (optional) = v[i] is a vertex of G
+void launch_tri_find(const Table& t, const unsigned long long* ctl, const int64_t* v, uint64_t n, int64_t* count,
+                     uint8_t* found, hipStream_t st);
+// flags[i] = entry i heads its row (and, nonzero, its vertex has t > 0); blk as above
+void launch_tri_flag_heads(const Table& t, const unsigned long long* ctl, const TriAdj& A, int nonzero,
+                           uint8_t* flags, uint32_t* blk, hipStream_t st);
+// the flagged vertices in order with their counters into (ov, oc), at most cap rows
+void launch_tri_compact_rows(const Table& t, const unsigned long long* ctl, const TriAdj& A, const uint8_t* flags,
+                             const uint32_t* blk, int64_t* ov, int64_t* oc, uint64_t cap, hipStream_t st);
+// every vertex of A but INT64_MIN inserted into `to` with its counter of `from`
+void launch_tri_rehash(const Table& from, const Table& to, const TriAdj& A, hipStream_t st);
+
+}  // namespace gs

@@ -408,6 +408,66 @@ int gs_degree_export(gs_handle h, int64_t* v, int64_t* degree, size_t cap, size_
 int gs_degree_distribution_device(gs_handle h, int64_t* degree, int64_t* count, size_t cap, size_t* n);
 int gs_degree_distribution(gs_handle h, int64_t* degree, int64_t* count, size_t cap, size_t* n);
 
+/* ---- triangle summary -----------------------------------------------------------
+ * Exact triangle counts of a streamed graph: example/WindowTriangles (the count of each
+ * window's graph: reset, fold, read) and example/ExactTriangleCount with
+ * SimpleEdgeStream.buildNeighborhood (single pass, insertion only: fold after fold).
+ *
+ * A triangle handle is its own opaque type with its own create call, not a gs_kind. It
+ * holds a graph G and its counts. G is the set of distinct unordered pairs {u, v}, u != v,
+ * of signed 64-bit ids folded since create or reset: edge direction, repeated edges (inside
+ * one fold or across folds) and self-loops do not change G, a self-loop does not register its
+ * vertex, and every id is legal, INT64_MIN and INT64_MAX included. The handle answers T (the
+ * triangles of G), t(v) for every vertex of G (the triangles through v; their sum is 3 T),
+ * the number of edges and the number of vertices -- all 64-bit counters, on the device and
+ * here. The answers depend on G only, never on how the stream was cut into folds or ordered.
+ *
+ * Relation to the reference. On a window without self-loops the count equals
+ * WindowTriangles (it deduplicates neighbours in a HashSet too). On a stream without
+ * repeated edges and without self-loops T and t(v) equal the final counters of
+ * ExactTriangleCount (key -1 the total, the other keys the vertices). The reference
+ * intersects a repeated edge again and counts its triangles twice; here it is ignored. The
+ * reference's handling of self-loops (the j = i candidates of WindowTriangles.java:103-104,
+ * undirected() of a loop) is not reproduced. No deletions, gs_combine, serialization or
+ * multi-GPU groups.
+ *
+ * Synchronisation: a fold synchronises with the host ONCE, to learn the number of new edges
+ * and grow its arrays; apart from that gs_triangle_fold_device is ordered like
+ * gs_fold_device (its reads of src / dst are queued on the handle's stream:
+ * gs_triangle_wait_stream orders them behind a producer). Adjacency entries (two per edge)
+ * are indexed by the sort's 32-bit payload: a fold that could take them past 2^32 - 1 fails
+ * with GS_ERR_CAPACITY before any work. Every device allocation of a handle, growth
+ * included, is counted by gs_hbm_bytes and released by gs_triangle_destroy.
+ *
+ * gs_triangle_create: edge_hint sizes the first allocation only (growth keeps the counts).
+ * gs_triangle_reset: G empty, counters zero, capacity kept.
+ * gs_triangle_fold / _fold_device: n edges from HOST arrays (copied before the call
+ *   returns) / DEVICE arrays, element i = src[i*stride], dst[i*stride].
+ * gs_triangle_count: T, |G| and the vertex count on the host (synchronises).
+ * gs_triangle_count_device: the same three words into DEVICE memory, asynchronous.
+ * gs_triangle_find_device: count[i] = t(v[i]) of the DEVICE id v[i] (0 when absent);
+ *   found[i] (optional, may be NULL) = 1 when v[i] is a vertex of G. Asynchronous.
+ * gs_triangle_export_device / gs_triangle_export: the rows (vertex, t(vertex)) into DEVICE /
+ *   HOST arrays of capacity cap, ascending by vertex in signed order (ordered on the device);
+ *   nonzero_only drops the vertices with t = 0. *n on the host (synchronises);
+ *   GS_ERR_TRUNCATED with *n set and nothing written when cap < *n.
+ * gs_triangle_sync / _get_stream / _wait_stream: as gs_sync / gs_get_stream / gs_wait_stream.
+ * Null handles and pointers return GS_ERR_INVALID before any device call. */
+typedef struct gs_triangles_s* gs_triangles;
+int gs_triangle_create(gs_triangles* out, int device, uint64_t edge_hint);
+int gs_triangle_destroy(gs_triangles t); /* NULL is GS_OK */
+int gs_triangle_reset(gs_triangles t);
+int gs_triangle_fold(gs_triangles t, const int64_t* src, const int64_t* dst, size_t n);
+int gs_triangle_fold_device(gs_triangles t, const int64_t* src, const int64_t* dst, size_t n, size_t stride);
+int gs_triangle_count(gs_triangles t, uint64_t* triangles, uint64_t* edges, uint64_t* vertices);
+int gs_triangle_count_device(gs_triangles t, uint64_t* out);
+int gs_triangle_find_device(gs_triangles t, const int64_t* v, size_t n, int64_t* count, uint8_t* found);
+int gs_triangle_export_device(gs_triangles t, int64_t* v, int64_t* count, size_t cap, size_t* n, int nonzero_only);
+int gs_triangle_export(gs_triangles t, int64_t* v, int64_t* count, size_t cap, size_t* n, int nonzero_only);
+int gs_triangle_sync(gs_triangles t);
+int gs_triangle_get_stream(gs_triangles t, void** stream);
+int gs_triangle_wait_stream(gs_triangles t, void* stream);
+
 /* ---- introspection -----------------------------------------------------------
  * The HIP stream (hipStream_t) the handle enqueues on, and per-kernel timing:
  * when profiling is on, every launch is bracketed by HIP events on the stream it

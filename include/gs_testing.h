@@ -38,7 +38,14 @@ enum gs_testing_knob {
    * 0 product, 1 no on-chip combining, 2 4096 LDS slots, 3 tile 1024, 4 2048 LDS slots,
    * 5 diagnostic without the counter adds (counts stay 0) */
   GS_TESTING_DEGREE_VARIANT = 5,
-  GS_TESTING_KNOBS = 6
+  /* triangle fold: work assignment of the count step (tools/triangle_bench.py): 0 product
+   * (edges binned by shorter-row length: a lane group of 8, a wave, a workgroup with the
+   * longer row sampled in LDS), 1 one wave per new edge */
+  GS_TESTING_TRIANGLE_VARIANT = 6,
+  /* triangle fold: 1 = bracket the fold's phases with events and wait for them
+   * (gs_testing_triangle_stats); product: 0 */
+  GS_TESTING_TRIANGLE_PROFILE = 7,
+  GS_TESTING_KNOBS = 8
 };
 
 /* Set knob `knob` to `value` (< 0: the product value). Returns GS_OK or GS_ERR_INVALID. */
@@ -51,6 +58,12 @@ int64_t gs_testing_get(int knob);
  * summary handle the caller may read (gs_counters, gs_debug_counters, gs_num_vertices) but
  * not destroy; *forest = NULL for a replica group. `g` is a gs_group_t. */
 int gs_testing_group_forest(void* g, void** forest);
+
+/* Diagnostics of a triangle handle (`t` is a gs_triangles; synchronises): out[0] = intersection
+ * steps since reset (the sum over new edges of the shorter row's length), out[1] = the longest
+ * row a new edge met, out[2..5] = microseconds of the last profiled fold's canonise, sort and
+ * dedup, merge (with the fold's host synchronisation and growth) and count phases. Six words. */
+int gs_testing_triangle_stats(void* t, uint64_t* out);
 
 #ifdef __cplusplus
 }
