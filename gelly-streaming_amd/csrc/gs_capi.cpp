@@ -78,12 +78,6 @@ int64_t testing_value(int knob, int64_t product) {
 
 namespace {
 
-uint64_t next_pow2(uint64_t x) {
-  uint64_t p = 1;
-  while (p < x) p <<= 1;
-  return p;
-}
-
 hipEvent_t take_event(gs_summary* h) {
   if (!h->ev_pool.empty()) {
     hipEvent_t e = h->ev_pool.back();
@@ -156,7 +150,7 @@ int wait_x_consumer(gs_summary* h) {
 // Combine scratch of at least `rows` rows (v, label, parity), allocated on growth only.
 int ensure_x(gs_summary* h, uint64_t rows) {
   if (!h->x_cnt) {
-    GS_HIP(dmalloc(&h->x_cnt, 16));
+    GS_HIP(h->x_cnt.alloc(2));
     GS_HIP(hipEventCreateWithFlags(&h->x_ready, hipEventDisableTiming));
     GS_HIP(hipEventCreateWithFlags(&h->x_used, hipEventDisableTiming));
   }
@@ -164,16 +158,12 @@ int ensure_x(gs_summary* h, uint64_t rows) {
   if (h->x_v) {
     if (int rc = wait_x_consumer(h)) return rc;
     GS_HIP(hipStreamSynchronize(h->stream));
-    (void)dfree(h->x_v);
-    (void)dfree(h->x_l);
-    (void)dfree(h->x_p);
-    h->x_v = h->x_l = nullptr;
-    h->x_p = nullptr;
   }
+  h->x_cap = 0;
   const uint64_t c = std::max<uint64_t>(rows, (uint64_t)(kMaxLoad * (double)h->cap) + 2);
-  GS_HIP(dmalloc(&h->x_v, c * 8));
-  GS_HIP(dmalloc(&h->x_l, c * 8));
-  GS_HIP(dmalloc(&h->x_p, c));
+  GS_HIP(h->x_v.alloc(c));
+  GS_HIP(h->x_l.alloc(c));
+  GS_HIP(h->x_p.alloc(c));
   h->x_cap = c;
   return GS_OK;
 }
@@ -210,19 +200,16 @@ uint64_t create_bytes(uint64_t cap) {
 namespace {
 
 int alloc_vlist(gs_summary* h) {
-  (void)dfree(h->vlist);
-  h->vlist = nullptr;
   h->vshard_cap = (uint32_t)(h->cap / gs::kShards + 1024);
-  GS_HIP(dmalloc(&h->vlist, (size_t)gs::kShards * h->vshard_cap * 4));
+  GS_HIP(h->vlist.alloc((uint64_t)gs::kShards * h->vshard_cap));
   return GS_OK;
 }
 
 // keep_delta: a rebuild (grow) keeps the pending delta counters.
 int alloc_table(gs_summary* h, uint64_t cap, bool keep_delta = false) {
   h->cap = cap;
-  h->logcap = 0;
-  while ((1ull << h->logcap) < cap) ++h->logcap;
-  GS_HIP(dmalloc(&h->tab, (cap + 1) * sizeof(gs::Slot)));
+  h->logcap = log2_ceil(cap);
+  GS_HIP(h->tab.alloc(cap + 1));
   if (int rc = alloc_vlist(h)) return rc;
   memset(h->h_flags, 0, 16);  // the device flags are cleared below (no kernel of the old table runs)
   if (keep_delta) {
@@ -249,18 +236,11 @@ int grow(gs_summary* h, uint64_t new_cap) {
   uint64_t nv = 0;
   int rc = read_nv(h, &nv);
   if (rc) return rc;
-  int64_t *v = nullptr, *l = nullptr;
-  uint8_t* p = nullptr;
+  DevBuf<int64_t> v, l;
+  DevBuf<uint8_t> p;
   const size_t m = nv + 1;
-  auto release = [&] {
-    (void)dfree(v);
-    (void)dfree(l);
-    (void)dfree(p);
-  };
-  if (dmalloc(&v, m * 8) != hipSuccess || dmalloc(&l, m * 8) != hipSuccess || dmalloc(&p, m) != hipSuccess) {
-    release();
+  if (v.alloc(m) != hipSuccess || l.alloc(m) != hipSuccess || p.alloc(m) != hipSuccess)
     return fail(GS_ERR_HIP, "table rebuild: out of device memory");
-  }
   size_t got = 0;
   uint32_t fail_flag = 0;
   rc = export_device_impl(h, v, l, p, m, &got);
@@ -268,12 +248,7 @@ int grow(gs_summary* h, uint64_t new_cap) {
                  hipSuccess)
     rc = fail(GS_ERR_HIP, "table rebuild: flag read failed");
   if (!rc && hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(GS_ERR_HIP, "table rebuild: sync failed");
-  if (rc) {
-    release();
-    return rc;
-  }
-  (void)dfree(h->tab);
-  h->tab = nullptr;
+  if (rc) return rc;
   const bool track = h->track;
   h->track = false;  // the rebuild is not a delta
   rc = alloc_table(h, new_cap, /*keep_delta=*/true);
@@ -286,7 +261,6 @@ int grow(gs_summary* h, uint64_t new_cap) {
   }
   h->track = track;
   if (!rc && hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(GS_ERR_HIP, "table rebuild: sync failed");
-  release();
   return rc;
 }
 
@@ -443,7 +417,7 @@ int server_start(gs_summary* h) {
   memset(b, 0, sizeof(gs::ServerBox));
   b->seq = h->srv_seq;
   b->bc_init = h->srv_seq;
-  GS_HIP(hipMemcpyAsync(&h->srv_bc->seq, &b->bc_init, 8, hipMemcpyHostToDevice, h->stream));
+  GS_HIP(hipMemcpyAsync(&h->srv_bc.get()->seq, &b->bc_init, 8, hipMemcpyHostToDevice, h->stream));
   // ~2 ms without a window: the launch leaves on its own (wall clock 100 MHz). It holds
   // its stream's hardware queue while resident, so another stream that shares the queue
   // waits at most that long behind an idle server (the config-5 windows arrive
@@ -693,13 +667,10 @@ int fold_device_impl(gs_summary* h, const int64_t* src, const int64_t* dst, cons
         if (st == h->lane[li]) set = 1 + li;
       if (h->dd_edges[set] < c) {
         GS_HIP(hipStreamSynchronize(st));  // the set's previous user is done
-        (void)dfree(h->dd_tab[set]);
-        (void)dfree(h->dd_w[set]);
-        h->dd_tab[set] = nullptr;
-        h->dd_w[set] = nullptr;
+        h->dd_edges[set] = 0;
         const uint64_t e = next_pow2(c);
-        GS_HIP(dmalloc(&h->dd_tab[set], 2 * e * 16));
-        GS_HIP(dmalloc(&h->dd_w[set], e));
+        GS_HIP(h->dd_tab[set].alloc(2 * e * 2));  // 2 e slots of 16 bytes
+        GS_HIP(h->dd_w[set].alloc(e));
         h->dd_edges[set] = e;
       }
       const uint64_t slots = 2 * next_pow2(c);  // load factor <= 1/2
@@ -827,12 +798,8 @@ int ensure_delta_list(gs_summary* h, uint64_t edges) {
   uint64_t per = 256;  // slack
   for (uint64_t off = 0; off < edges; off += kMaxChunk) per += per_shard_edges(std::min<uint64_t>(kMaxChunk, edges - off));
   if (per > 0xFFFFFFFFull) return fail(GS_ERR_INVALID, "delta list too large");
-  if (h->drec) {
-    GS_HIP(hipStreamSynchronize(h->stream));
-    (void)dfree(h->drec);
-    h->drec = nullptr;
-  }
-  GS_HIP(dmalloc(&h->drec, (size_t)gs::kDeltaSets * gs::kShards * per * 24));
+  if (h->drec) GS_HIP(hipStreamSynchronize(h->stream));
+  GS_HIP(h->drec.alloc((uint64_t)gs::kDeltaSets * gs::kShards * per * 3));
   h->delta_shard_cap = (uint32_t)per;
   h->delta_edges = edges;
   return GS_OK;
@@ -881,9 +848,9 @@ int gs_create(gs_handle* out, int device, int kind, uint64_t capacity_hint) {
   };
   if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess)
     return bail(fail(GS_ERR_HIP, "hipStreamCreate failed"));
-  if (dmalloc(&h->ctr, gs::CTR_COUNT * gs::kCtrStride * 4) != hipSuccess)
+  if (h->ctr.alloc(gs::CTR_COUNT * gs::kCtrStride) != hipSuccess)
     return bail(fail(GS_ERR_HIP, "hipMalloc(counters) failed"));
-  if (dmalloc(&h->d_scratch, 64) != hipSuccess) return bail(fail(GS_ERR_HIP, "hipMalloc(scratch) failed"));
+  if (h->d_scratch.alloc(8) != hipSuccess) return bail(fail(GS_ERR_HIP, "hipMalloc(scratch) failed"));
   if (hipHostMalloc(&h->h_flags, 64, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
       hipHostGetDevicePointer(reinterpret_cast<void**>(&h->hflags_dev), h->h_flags, 0) != hipSuccess)
     return bail(fail(GS_ERR_HIP, "hipHostMalloc(flags) failed"));
@@ -921,12 +888,7 @@ int gs_destroy(gs_handle h) {
   if (h->main_ev) (void)hipEventDestroy(h->main_ev);
   if (h->ext_ev) (void)hipEventDestroy(h->ext_ev);
   if (h->idle_ev) (void)hipEventDestroy(h->idle_ev);
-  for (int i = 0; i < gs_summary::kDedupSets; ++i) {
-    (void)dfree(h->dd_tab[i]);
-    (void)dfree(h->dd_w[i]);
-  }
   if (h->srv_box) (void)hipHostFree(h->srv_box);
-  if (h->srv_bc) (void)dfree(h->srv_bc);
   for (auto e : h->ev_pool) (void)hipEventDestroy(e);
   for (int i = 0; i < 2; ++i) {
     if (h->stage_ev[i]) (void)hipEventDestroy(h->stage_ev[i]);
@@ -940,16 +902,9 @@ int gs_destroy(gs_handle h) {
   if (h->h_wstage) (void)hipHostFree(h->h_wstage);
   if (h->h_text) (void)hipHostFree(h->h_text);
   if (h->h_tres) (void)hipHostFree(h->h_tres);
-  for (void* p : {(void*)h->d_text, (void*)h->d_tsrc, (void*)h->d_tdst, h->d_tscratch, (void*)h->tab, (void*)h->ctr,
-                  (void*)h->vlist, (void*)h->drec, (void*)h->nxt, (void*)h->chg_scratch, (void*)h->chg_ov,
-                  (void*)h->chg_ol, (void*)h->chg_op, (void*)h->d_stage,
-                  (void*)h->d_wstage, (void*)h->d_scratch, (void*)h->x_v, (void*)h->x_l, (void*)h->x_p,
-                  (void*)h->x_cnt, (void*)h->cs_key[0], (void*)h->cs_key[1], (void*)h->cs_pay[0], (void*)h->cs_pay[1],
-                  (void*)h->cs_table, (void*)h->cs_ctl, (void*)h->co_comp, (void*)h->co_off, (void*)h->co_member,
-                  (void*)h->co_sign})
-    (void)dfree(p);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
+  const hipStream_t stream = h->stream;
+  delete h;  // frees every device buffer (DevBuf members): device current, every stream joined and idle
+  if (stream) (void)hipStreamDestroy(stream);
   return GS_OK;
 }
 
@@ -1049,14 +1004,10 @@ static int ensure_dev_stage(gs_summary* h, size_t edges) {
   if (h->d_stage) {  // folds queued on the stream or the lanes may still read the old buffers
     if (int rc = join_lanes(h)) return rc;
     GS_HIP(hipStreamSynchronize(h->stream));
-    (void)dfree(h->d_stage);
-    (void)dfree(h->d_wstage);
-    h->d_stage = nullptr;
-    h->d_wstage = nullptr;
-    h->d_stage_chunk = 0;
   }
-  GS_HIP(dmalloc(&h->d_stage, sizeof(int64_t) * 4 * c));
-  GS_HIP(dmalloc(&h->d_wstage, 2 * c));
+  h->d_stage_chunk = 0;
+  GS_HIP(h->d_stage.alloc(4 * c));
+  GS_HIP(h->d_wstage.alloc(2 * c));
   h->d_stage_chunk = c;
   return GS_OK;
 }
@@ -1251,7 +1202,7 @@ int gs_digest(gs_handle h, uint64_t* digest) {
   if (!digest) return fail(GS_ERR_INVALID, "digest is null");
   DeviceGuard g(h->device);
   if (int rc_ = join_lanes(h)) return rc_;
-  unsigned long long* d = reinterpret_cast<unsigned long long*>(h->d_scratch);
+  unsigned long long* d = reinterpret_cast<unsigned long long*>(h->d_scratch.get());
   uint32_t failed = 0;
   GS_HIP(hipMemsetAsync(d, 0, 8, h->stream));
   gs::launch_digest(h->table(), d, std::min<uint64_t>(h->nv_ub, h->cap + 1), h->stream);
@@ -1382,55 +1333,22 @@ static int gather_rows(gs_handle h, uint64_t* n) {
   return GS_OK;
 }
 
-// Sort scratch for `rows` rows: allocated on growth only, with a quarter of headroom so
-// that a summary exported every window does not reallocate every window.
-static int ensure_sort_scratch(gs_handle h, uint64_t rows) {
-  if (!h->cs_ctl) GS_HIP(dmalloc(&h->cs_ctl, gs::kSortCtlWords * 4));
-  if (h->cs_rows >= rows) return GS_OK;
-  GS_HIP(hipStreamSynchronize(h->stream));
-  for (int i = 0; i < 2; ++i) {
-    (void)dfree(h->cs_key[i]);
-    (void)dfree(h->cs_pay[i]);
-    h->cs_key[i] = nullptr;
-    h->cs_pay[i] = nullptr;
-  }
-  (void)dfree(h->cs_table);
-  h->cs_table = nullptr;
-  h->cs_rows = 0;
-  const uint64_t c = gs::sort_blocks(rows + rows / 4) * gs::kSortTile;
-  for (int i = 0; i < 2; ++i) {
-    GS_HIP(dmalloc(&h->cs_key[i], c * 8));
-    GS_HIP(dmalloc(&h->cs_pay[i], c * 4));
-  }
-  GS_HIP(dmalloc(&h->cs_table, gs::kSortRadix * gs::sort_row_stride(gs::sort_blocks(c)) * 4));
-  h->cs_rows = c;
-  return GS_OK;
-}
-
 // Device staging of the host-array form: nv members / signs, nc components.
 static int ensure_comp_staging(gs_handle h, uint64_t nv, uint64_t nc) {
   if (h->co_vcap < nv) {
     GS_HIP(hipStreamSynchronize(h->stream));
-    (void)dfree(h->co_member);
-    (void)dfree(h->co_sign);
-    h->co_member = nullptr;
-    h->co_sign = nullptr;
     h->co_vcap = 0;
     const uint64_t c = nv + nv / 4;
-    GS_HIP(dmalloc(&h->co_member, c * 8));
-    GS_HIP(dmalloc(&h->co_sign, c));
+    GS_HIP(h->co_member.alloc(c));
+    GS_HIP(h->co_sign.alloc(c));
     h->co_vcap = c;
   }
   if (h->co_ccap < nc) {
     GS_HIP(hipStreamSynchronize(h->stream));
-    (void)dfree(h->co_comp);
-    (void)dfree(h->co_off);
-    h->co_comp = nullptr;
-    h->co_off = nullptr;
     h->co_ccap = 0;
     const uint64_t c = nc + nc / 4;
-    GS_HIP(dmalloc(&h->co_comp, c * 8));
-    GS_HIP(dmalloc(&h->co_off, (c + 1) * 8));
+    GS_HIP(h->co_comp.alloc(c));
+    GS_HIP(h->co_off.alloc(c + 1));
     h->co_ccap = c;
   }
   return GS_OK;
@@ -1449,12 +1367,13 @@ static int components_impl(gs_handle h, int64_t* comp, uint64_t* offset, int64_t
     }
     return GS_OK;
   }
-  if (int rc = ensure_sort_scratch(h, n)) return rc;
+  SortScratch& ss = h->sort;
+  if (int rc = sort_scratch_ensure(ss, n, h->stream)) return rc;
   std::vector<uint32_t> ctl(gs::kSortCtlWords);
-  GS_HIP(hipMemsetAsync(h->cs_ctl, 0, gs::kSortCtlWords * 4, h->stream));
-  gs::launch_sort_digits(h->x_v, h->x_l, n, h->cs_ctl, h->stream);
+  GS_HIP(hipMemsetAsync(ss.ctl, 0, gs::kSortCtlWords * 4, h->stream));
+  gs::launch_sort_digits(h->x_v, h->x_l, n, ss.ctl, h->stream);
   GS_HIP(hipGetLastError());
-  GS_HIP(hipMemcpyAsync(ctl.data(), h->cs_ctl, gs::kSortCtlWords * 4, hipMemcpyDeviceToHost, h->stream));
+  GS_HIP(hipMemcpyAsync(ctl.data(), ss.ctl, gs::kSortCtlWords * 4, hipMemcpyDeviceToHost, h->stream));
   GS_HIP(hipStreamSynchronize(h->stream));
   const uint64_t roots = ctl[gs::kSortCtlRoots];
   *nv = n;
@@ -1478,29 +1397,18 @@ static int components_impl(gs_handle h, int64_t* comp, uint64_t* offset, int64_t
   }
   // sort 1 by vertex (payload = row), sort 2 stably by the row's label: ordered by (label,
   // vertex). A digit with one bin holding every key is an identity pass and is skipped.
+  // (keys of sort 2: the label of row cur.pay[i], or of row i when sort 1 had no pass to run)
   gs::SortSrc cur;
-  cur.ids = h->x_v;
-  cur.rows = n;
   int side = 0;
   for (int s = 0; s < 2; ++s) {
-    if (s == 1) {
-      cur.key = nullptr;  // keys of sort 2: the label of row cur.pay[i] (row i when sort 1 had no pass to run)
-      cur.ids = h->x_l;
-    }
-    for (int p = 0; p < (int)gs::kSortPasses; ++p) {
-      const uint32_t* gh = ctl.data() + (s * gs::kSortPasses + p) * gs::kSortRadix;
-      if (*std::max_element(gh, gh + gs::kSortRadix) == n) continue;
-      gs::launch_sort_pass(cur, n, p, h->cs_table, h->cs_ctl + (gh - ctl.data()), h->cs_key[side], h->cs_pay[side],
-                           h->stream);
-      GS_HIP(hipGetLastError());
-      cur.key = h->cs_key[side];
-      cur.pay = h->cs_pay[side];
-      cur.ids = nullptr;
-      side ^= 1;
-    }
+    const uint32_t rows0 = s * gs::kSortPasses * gs::kSortRadix;  // the sort's histogram rows in ctl
+    bool skip[gs::kSortPasses];
+    sort_skip_digits(ctl.data() + rows0, n, skip);
+    if (int rc = sort_run(ss, s == 0 ? h->x_v.get() : h->x_l.get(), n, ss.ctl + rows0, skip, &cur, &side, h->stream))
+      return rc;
   }
   if (!cur.key) cur.ids = h->x_l;
-  gs::launch_comp_csr(cur, n, h->x_v, h->x_p, h->kind == GS_KIND_SIGNED, h->cs_table, d_comp, d_off, d_member, d_sign,
+  gs::launch_comp_csr(cur, n, h->x_v, h->x_p, h->kind == GS_KIND_SIGNED, ss.table, d_comp, d_off, d_member, d_sign,
                       d_cap_c, h->stream);
   GS_HIP(hipGetLastError());
   if (to_host) {
@@ -1521,7 +1429,7 @@ int gs_num_components(gs_handle h, uint64_t* n) {
   uint64_t rows = 0;
   if (int rc = gather_rows(h, &rows)) return rc;
   if (rows == 0) return GS_OK;
-  unsigned long long* d = reinterpret_cast<unsigned long long*>(h->d_scratch);
+  unsigned long long* d = reinterpret_cast<unsigned long long*>(h->d_scratch.get());
   unsigned long long out = 0;
   GS_HIP(hipMemsetAsync(d, 0, 8, h->stream));
   gs::launch_comp_roots(h->x_v, h->x_l, rows, d, h->stream);
@@ -1785,7 +1693,7 @@ int gs_set_window_server(gs_handle h, int on) {
   if (int rc = join_lanes(h)) return rc;  // stops a running server
   if (on && !h->srv_box) {
     GS_HIP(hipHostMalloc(&h->srv_box, sizeof(gs::ServerBox), hipHostMallocMapped | hipHostMallocCoherent));
-    GS_HIP(dmalloc(&h->srv_bc, sizeof(gs::ServerBcast)));
+    GS_HIP(h->srv_bc.alloc(1));
     memset(h->srv_box, 0, sizeof(gs::ServerBox));
   }
   h->srv_on = on != 0;
@@ -2004,10 +1912,10 @@ int gs_fold_text(gs_handle h, const char* text, size_t len, int sep, uint64_t* n
     const size_t sb = gs::parse_scratch_bytes(kTextChunk, &cub);
     GS_HIP(hipHostMalloc(&h->h_text, 2 * kTextChunk, hipHostMallocDefault));
     GS_HIP(hipHostMalloc(&h->h_tres, 4 * sizeof(uint64_t), hipHostMallocDefault));
-    GS_HIP(dmalloc(&h->d_text, 2 * kTextChunk));
-    GS_HIP(dmalloc(&h->d_tsrc, max_lines * 8));
-    GS_HIP(dmalloc(&h->d_tdst, max_lines * 8));
-    GS_HIP(dmalloc(&h->d_tscratch, sb));
+    GS_HIP(h->d_text.alloc(2 * kTextChunk));
+    GS_HIP(h->d_tsrc.alloc(max_lines));
+    GS_HIP(h->d_tdst.alloc(max_lines));
+    GS_HIP(h->d_tscratch.alloc(sb));
     for (int i = 0; i < 2; ++i) GS_HIP(hipEventCreateWithFlags(&h->text_ev[i], hipEventDisableTiming));
     gs::parse_scratch_init(h->tscratch, h->d_tscratch, kTextChunk);
   }
@@ -2080,13 +1988,8 @@ int x_scratch(gs_summary* h, uint64_t rows) {
 
 void exact_count(gs_summary* h, uint64_t nv) { note_exact_count(h, nv); }
 
-int rebuild_table(gs_summary* h, uint64_t cap) {
-  (void)dfree(h->tab);
-  h->tab = nullptr;
-  return alloc_table(h, cap, /*keep_delta=*/true);
-}
+int rebuild_table(gs_summary* h, uint64_t cap) { return alloc_table(h, cap, /*keep_delta=*/true); }
 
-int sort_scratch(gs_summary* h, uint64_t rows) { return ensure_sort_scratch(h, rows); }
 int comp_staging(gs_summary* h, uint64_t nv, uint64_t nc) { return ensure_comp_staging(h, nv, nc); }
 int dev_stage(gs_summary* h, size_t edges) { return ensure_dev_stage(h, edges); }
 

@@ -49,13 +49,9 @@ ChgScratch scratch(gs_summary* h) {
 int ensure_scratch(gs_summary* h) {
   const uint64_t rows = (uint64_t)gs::kShards * h->delta_shard_cap;
   if (h->chg_scratch && h->chg_scratch_rows >= rows) return GS_OK;
-  if (h->chg_scratch) {
-    GS_HIP(hipStreamSynchronize(h->stream));
-    (void)dfree(h->chg_scratch);
-    h->chg_scratch = nullptr;
-  }
+  if (h->chg_scratch) GS_HIP(hipStreamSynchronize(h->stream));
   const size_t words = 1 + gs::kShards / 2 + (rows + 1) / 2 + 3 * rows;
-  GS_HIP(dmalloc(&h->chg_scratch, words * 8));
+  GS_HIP(h->chg_scratch.alloc(words));
   GS_HIP(hipMemsetAsync(h->chg_scratch, 0, (1 + gs::kShards / 2) * 8, h->stream));
   h->chg_scratch_rows = rows;
   return GS_OK;
@@ -63,12 +59,8 @@ int ensure_scratch(gs_summary* h) {
 
 int ensure_nxt(gs_summary* h) {
   if (h->nxt && h->nxt_slots == h->cap + 1) return GS_OK;
-  if (h->nxt) {
-    GS_HIP(hipStreamSynchronize(h->stream));
-    (void)dfree(h->nxt);
-    h->nxt = nullptr;
-  }
-  GS_HIP(dmalloc(&h->nxt, (h->cap + 1) * 4));
+  if (h->nxt) GS_HIP(hipStreamSynchronize(h->stream));
+  GS_HIP(h->nxt.alloc(h->cap + 1));
   h->nxt_slots = h->cap + 1;
   return GS_OK;
 }
@@ -193,16 +185,11 @@ int gs_take_changes(gs_handle h, int64_t* v, int64_t* label, uint8_t* parity, si
   *n = 0;
   if (cap < nv) return fail(GS_ERR_INVALID, "cap below the vertex count: " + std::to_string(nv));
   if (h->chg_ocap < nv + 1) {
-    (void)dfree(h->chg_ov);
-    (void)dfree(h->chg_ol);
-    (void)dfree(h->chg_op);
-    h->chg_ov = h->chg_ol = nullptr;
-    h->chg_op = nullptr;
     h->chg_ocap = 0;
     const uint64_t rows = std::max<uint64_t>(nv + 1, 1024) * 5 / 4;  // headroom: fewer reallocations
-    GS_HIP(dmalloc(&h->chg_ov, rows * 8));
-    GS_HIP(dmalloc(&h->chg_ol, rows * 8));
-    GS_HIP(dmalloc(&h->chg_op, rows));
+    GS_HIP(h->chg_ov.alloc(rows));
+    GS_HIP(h->chg_ol.alloc(rows));
+    GS_HIP(h->chg_op.alloc(rows));
     h->chg_ocap = rows;
   }
   uint64_t k = 0;

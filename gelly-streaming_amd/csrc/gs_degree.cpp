@@ -128,7 +128,7 @@ int gather_rows(gs_summary* h, bool all, uint64_t* n) {
   exact_count(h, nv);
   if (nv == 0) return GS_OK;
   if (int rc = x_scratch(h, nv + 1)) return rc;
-  unsigned long long* cnt = reinterpret_cast<unsigned long long*>(h->d_scratch);
+  unsigned long long* cnt = reinterpret_cast<unsigned long long*>(h->d_scratch.get());
   unsigned long long got = 0;
   GS_HIP(hipMemsetAsync(cnt, 0, 8, h->stream));
   gs::launch_degree_export(h->table(), h->x_v, h->x_l, h->x_cap, cnt, all, h->stream);
@@ -140,33 +140,23 @@ int gather_rows(gs_summary* h, bool all, uint64_t* n) {
   return GS_OK;
 }
 
-// Stable radix sort of n int64 ids (signed order) with gs_sort_k.hip: on return `cur` names
-// the sorted (key, row index) pairs -- key / pay null when no pass had to run (the input
-// order is the sorted order) -- and *side the ping-pong buffer not holding them.
+// Stable radix sort of n int64 ids (signed order) with the shared driver (gs_sort.cpp): on
+// return `cur` names the sorted (key, row index) pairs -- key / pay null when no pass had to
+// run (the input order is the sorted order) -- and *side the ping-pong buffer not holding them.
 int sort_rows(gs_summary* h, const int64_t* ids, uint64_t n, gs::SortSrc* cur, int* side) {
-  if (int rc = sort_scratch(h, n)) return rc;
+  SortScratch& ss = h->sort;
+  if (int rc = sort_scratch_ensure(ss, n, h->stream)) return rc;
   std::vector<uint32_t> ctl(gs::kSortCtlWords);
-  GS_HIP(hipMemsetAsync(h->cs_ctl, 0, gs::kSortCtlWords * 4, h->stream));
-  gs::launch_sort_digits(ids, ids, n, h->cs_ctl, h->stream);
+  GS_HIP(hipMemsetAsync(ss.ctl, 0, gs::kSortCtlWords * 4, h->stream));
+  gs::launch_sort_digits(ids, ids, n, ss.ctl, h->stream);
   GS_HIP(hipGetLastError());
-  GS_HIP(hipMemcpyAsync(ctl.data(), h->cs_ctl, gs::kSortCtlWords * 4, hipMemcpyDeviceToHost, h->stream));
+  GS_HIP(hipMemcpyAsync(ctl.data(), ss.ctl, gs::kSortCtlWords * 4, hipMemcpyDeviceToHost, h->stream));
   GS_HIP(hipStreamSynchronize(h->stream));
+  bool skip[gs::kSortPasses];
+  sort_skip_digits(ctl.data(), n, skip);
   *cur = gs::SortSrc();
-  cur->ids = ids;
-  cur->rows = n;
   *side = 0;
-  for (int p = 0; p < (int)gs::kSortPasses; ++p) {
-    const uint32_t* gh = ctl.data() + p * gs::kSortRadix;
-    if (*std::max_element(gh, gh + gs::kSortRadix) == n) continue;  // one bin holds every key: identity
-    gs::launch_sort_pass(*cur, n, p, h->cs_table, h->cs_ctl + p * gs::kSortRadix, h->cs_key[*side],
-                         h->cs_pay[*side], h->stream);
-    GS_HIP(hipGetLastError());
-    cur->key = h->cs_key[*side];
-    cur->pay = h->cs_pay[*side];
-    cur->ids = nullptr;
-    *side ^= 1;
-  }
-  return GS_OK;
+  return sort_run(ss, ids, n, ss.ctl, skip, cur, side, h->stream);
 }
 
 int export_impl(gs_summary* h, int64_t* v, int64_t* degree, size_t cap, size_t* n, int sorted, bool to_host) {
@@ -216,7 +206,7 @@ int distribution_impl(gs_summary* h, int64_t* degree, int64_t* count, size_t cap
   if (int rc = sort_rows(h, h->x_l, rows, &cur, &side)) return rc;
   unsigned long long nd = 1;  // no pass ran: every key equal
   if (cur.key) {
-    unsigned long long* heads = reinterpret_cast<unsigned long long*>(h->d_scratch) + 1;
+    unsigned long long* heads = reinterpret_cast<unsigned long long*>(h->d_scratch.get()) + 1;
     GS_HIP(hipMemsetAsync(heads, 0, 8, h->stream));
     gs::launch_degree_heads(cur.key, rows, heads, h->stream);
     GS_HIP(hipGetLastError());
@@ -228,13 +218,13 @@ int distribution_impl(gs_summary* h, int64_t* degree, int64_t* count, size_t cap
   if (!degree || !count) return fail(GS_ERR_INVALID, "null arrays");
   if (int rc = comp_staging(h, rows, rows)) return rc;
   if (!cur.key) cur.ids = h->x_l;
-  gs::launch_comp_csr(cur, rows, h->x_l, nullptr, false, h->cs_table, h->co_comp, h->co_off, h->co_member, nullptr,
+  gs::launch_comp_csr(cur, rows, h->x_l, nullptr, false, h->sort.table, h->co_comp, h->co_off, h->co_member, nullptr,
                       h->co_ccap, h->stream);
   GS_HIP(hipGetLastError());
   if (to_host) {
     // (the CSR's member column and the sort's free ping-pong buffer are dead by now)
     int64_t* sd = h->co_member;
-    int64_t* sc = reinterpret_cast<int64_t*>(h->cs_key[side]);
+    int64_t* sc = reinterpret_cast<int64_t*>(h->sort.key[side].get());
     gs::launch_degree_runs(h->co_comp, h->co_off, nd, sd, sc, h->stream);
     GS_HIP(hipGetLastError());
     GS_HIP(hipMemcpyAsync(degree, sd, nd * 8, hipMemcpyDeviceToHost, h->stream));
@@ -256,17 +246,11 @@ int degree_grow(gs_summary* h, uint64_t new_cap) {
   if (new_cap > kMaxCap) return fail(GS_ERR_CAPACITY, "vertex table would exceed 2^30 slots");
   uint64_t nv = 0;
   if (int rc = read_nv(h, &nv)) return rc;
-  int64_t *v = nullptr, *d = nullptr;
+  DevBuf<int64_t> v, d;
   const size_t m = nv + 1;
-  auto release = [&] {
-    (void)dfree(v);
-    (void)dfree(d);
-  };
-  if (dmalloc(&v, m * 8) != hipSuccess || dmalloc(&d, m * 8) != hipSuccess) {
-    release();
+  if (v.alloc(m) != hipSuccess || d.alloc(m) != hipSuccess)
     return fail(GS_ERR_HIP, "table rebuild: out of device memory");
-  }
-  unsigned long long* cnt = reinterpret_cast<unsigned long long*>(h->d_scratch);
+  unsigned long long* cnt = reinterpret_cast<unsigned long long*>(h->d_scratch.get());
   unsigned long long got = 0;
   int rc = GS_OK;
   if (hipMemsetAsync(cnt, 0, 8, h->stream) != hipSuccess) rc = fail(GS_ERR_HIP, "table rebuild: memset failed");
@@ -281,7 +265,6 @@ int degree_grow(gs_summary* h, uint64_t new_cap) {
   if (!rc) rc = add_rows(h, v, d, got, /*check_cap=*/false);
   if (!rc && hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(GS_ERR_HIP, "table rebuild: sync failed");
   if (!rc) exact_count(h, got);
-  release();
   return rc;
 }
 

@@ -190,9 +190,9 @@ struct gs_group {
   bool self_apply = false;       // test knob (GS_TESTING_GROUP_SELF_APPLY): also fold this rank's own rows back
   uint64_t batch = 0, rows_cap = 0;
   // exchange b uses buffer set b % kLag (send, counts, headers, receive) and delta set b % kDeltaSets
-  int64_t* send[kLag] = {};                             // [rows_cap * width]
-  int64_t* recv[kLag] = {};                             // [nranks * rows_cap * width]
-  unsigned long long* cnt = nullptr;                    // device: [kLag] send counts, then [kLag][nranks] gathered
+  DevBuf<int64_t> send[kLag];                           // [rows_cap * width]
+  DevBuf<int64_t> recv[kLag];                           // [nranks * rows_cap * width]
+  DevBuf<unsigned long long> cnt;                       // device: [kLag] send counts, then [kLag][nranks] gathered
   long long* hdr_host = nullptr;                        // pinned host-mapped [kLag][nranks + 1]
   long long* hdr_dev = nullptr;
   hipStream_t xc = nullptr, xd = nullptr, as = nullptr;  // counts, data, apply (the summary's side stream)
@@ -236,19 +236,17 @@ struct gs_group {
   gs_summary* G = nullptr;       // the label forest: a replica of the labels that need a cross-rank union
   uint64_t window = 0;           // own edges between combines (0: one combine per pass, untracked folds)
   uint64_t win_edges = 0;        // own edges since the last combine
-  gs::OwnerTable ot{};
-  uint32_t* mark = nullptr;      // device [64]: vertex-list fill at the previous combine
-  uint32_t* snap = nullptr;      // device [64]: the fill now
-  uint32_t* pflags = nullptr;    // device: [0] owner-table overflow, [1] odd cycle found by an owner
-  unsigned long long* pdev = nullptr;  // device: [0..2] snap out, [3] pairs, [4] count word, [5] label rows,
+  gs::OwnerTable ot{};           // (ot.tab = ot_tab, ot.err = pflags)
+  DevBuf<gs::OwnerSlot> ot_tab;
+  DevBuf<uint32_t> mark;         // device [64]: vertex-list fill at the previous combine
+  DevBuf<uint32_t> snap;         // device [64]: the fill now
+  DevBuf<uint32_t> pflags;       // device: [0] owner-table overflow, [1] odd cycle found by an owner
+  DevBuf<unsigned long long> pdev;     // device: [0..2] snap out, [3] pairs, [4] count word, [5] label rows,
                                        // [8, 8 + N) send counts, then N x N all send counts, then N count words
   unsigned long long* phost = nullptr;  // pinned host mirror of pdev's words
-  int64_t *stage = nullptr, *sendbuf = nullptr, *recvbuf = nullptr, *pairs = nullptr, *pairs_all = nullptr;
-  uint64_t stage_cap = 0, send_cap = 0, recv_cap = 0, pairs_cap = 0, pairs_all_cap = 0;
-  uint32_t* bcnt = nullptr;
-  uint64_t bcnt_cap = 0;
-  gs::PairSlot* pset = nullptr;  // the owner step's set of label pairs emitted this combine (N > 1)
-  uint64_t pset_cap = 0;
+  DevBuf<int64_t> stage, sendbuf, recvbuf, pairs, pairs_all;  // grow-only (ensure_buf)
+  DevBuf<uint32_t> bcnt;
+  DevBuf<gs::PairSlot> pset;     // the owner step's set of label pairs emitted this combine (N > 1)
   uint64_t cap_seen = 0;         // the local table's capacity at the previous combine (a rebuild re-exports all)
   hipEvent_t pev = nullptr;      // the combine's pair gather -> the label forest's fold
   uint64_t combines = 0, rows_exported = 0, rows_owned = 0, pairs_sent = 0, pairs_folded = 0;
@@ -443,7 +441,7 @@ int gs_group_create(gs_group_t* out, gs_handle h, const void* id, int nranks, in
     bool ok = hipHostMalloc(&g->hdr_host, kLag * (size_t)(nranks + 1) * 8,
                             hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess &&
               hipHostGetDevicePointer(reinterpret_cast<void**>(&g->hdr_dev), g->hdr_host, 0) == hipSuccess &&
-              dmalloc(&g->cnt, (kLag + kLag * (size_t)nranks) * 8) == hipSuccess &&
+              g->cnt.alloc(kLag + kLag * (uint64_t)nranks) == hipSuccess &&
               create_comm_stream(&g->xc) == hipSuccess && create_comm_stream(&g->xd) == hipSuccess &&
               hipStreamCreateWithFlags(&g->as, hipStreamNonBlocking) == hipSuccess &&
               hipEventCreateWithFlags(&g->as_ev, hipEventDisableTiming) == hipSuccess;
@@ -453,8 +451,8 @@ int gs_group_create(gs_group_t* out, gs_handle h, const void* id, int nranks, in
       ok = ok && hipEventCreateWithFlags(&g->staged[k], hipEventDisableTiming) == hipSuccess;
     }
     for (int k = 0; k < kLag && ok; ++k)
-      ok = dmalloc(&g->send[k], g->rows_cap * g->width * 8) == hipSuccess &&
-           dmalloc(&g->recv[k], (size_t)nranks * g->rows_cap * g->width * 8) == hipSuccess &&
+      ok = g->send[k].alloc(g->rows_cap * g->width) == hipSuccess &&
+           g->recv[k].alloc((uint64_t)nranks * g->rows_cap * g->width) == hipSuccess &&
            hipEventCreateWithFlags(&g->counted[k], hipEventDisableTiming) == hipSuccess &&
            hipEventCreateWithFlags(&g->gathered[k], hipEventDisableTiming) == hipSuccess &&
            hipEventCreateWithFlags(&g->applied[k], hipEventDisableTiming) == hipSuccess;
@@ -631,18 +629,10 @@ int tree_send(gs_group* g, int peer, int64_t* hdr) {
   gs_summary* h = g->h;
   uint64_t nv = 0;
   if (int rc = read_nv(h, &nv)) return rc;
-  int64_t *v = nullptr, *l = nullptr;
-  uint8_t* p = nullptr;
-  auto release = [&] {
-    (void)dfree(v);
-    (void)dfree(l);
-    (void)dfree(p);
-  };
-  if (dmalloc(&v, (nv + 1) * 8) != hipSuccess || dmalloc(&l, (nv + 1) * 8) != hipSuccess ||
-      dmalloc(&p, nv + 1) != hipSuccess) {
-    release();
+  DevBuf<int64_t> v, l;  // (freed on return: the sends have completed by then)
+  DevBuf<uint8_t> p;
+  if (v.alloc(nv + 1) != hipSuccess || l.alloc(nv + 1) != hipSuccess || p.alloc(nv + 1) != hipSuccess)
     return fail(GS_ERR_HIP, "tree combine: out of device memory");
-  }
   size_t got = 0;
   uint32_t failed = 0;
   int rc = export_device_impl(h, v, l, p, nv + 1, &got);
@@ -666,7 +656,6 @@ int tree_send(gs_group* g, int peer, int64_t* hdr) {
     if (r || e) rc = rccl_fail(&g->api, "ncclSend", r ? r : e);
   }
   if (hipStreamSynchronize(h->stream) != hipSuccess && !rc) rc = fail(GS_ERR_HIP, "tree combine: sync failed");
-  release();  // the sends have completed
   return rc;
 }
 
@@ -679,16 +668,10 @@ int tree_recv(gs_group* g, int peer, int64_t* hdr) {
   GS_HIP(hipMemcpyAsync(hv, hdr, 16, hipMemcpyDeviceToHost, h->stream));
   GS_HIP(hipStreamSynchronize(h->stream));
   const size_t got = (size_t)hv[0];
-  int64_t *v = nullptr, *l = nullptr;
-  uint8_t* p = nullptr;
-  auto release = [&] {
-    (void)dfree(v);
-    (void)dfree(l);
-    (void)dfree(p);
-  };
+  DevBuf<int64_t> v, l;
+  DevBuf<uint8_t> p;
   int rc = GS_OK;
-  if (got && (dmalloc(&v, got * 8) != hipSuccess || dmalloc(&l, got * 8) != hipSuccess ||
-              dmalloc(&p, got) != hipSuccess))
+  if (got && (v.alloc(got) != hipSuccess || l.alloc(got) != hipSuccess || p.alloc(got) != hipSuccess))
     rc = fail(GS_ERR_HIP, "tree combine: out of device memory");
   if (!rc && got) {
     g->api.group_start();
@@ -705,7 +688,6 @@ int tree_recv(gs_group* g, int peer, int64_t* hdr) {
     h->track = track;
   }
   if (hipStreamSynchronize(h->stream) != hipSuccess && !rc) rc = fail(GS_ERR_HIP, "tree combine: sync failed");
-  release();
   return rc;
 }
 
@@ -720,8 +702,8 @@ int gs_group_tree_combine(gs_group_t g) {
   gs_summary* h = g->h;
   DeviceGuard dg(h->device);
   if (int rc = join_lanes(h)) return rc;
-  int64_t* hdr = nullptr;  // device {count, failed}
-  GS_HIP(dmalloc(&hdr, 16));
+  DevBuf<int64_t> hdr;  // device {count, failed}
+  GS_HIP(hdr.alloc(2));
   int rc = GS_OK;
   // binomial tree (SummaryTreeReduce.enhance pairs partitions by f0/2, :107): at level l
   // rank r with r mod 2^(l+1) == 2^l sends to r - 2^l and leaves the tree
@@ -733,7 +715,6 @@ int gs_group_tree_combine(gs_group_t g) {
     }
     if (pos == 0 && g->rank + step < g->nranks) rc = tree_recv(g, g->rank + step, hdr);
   }
-  (void)dfree(hdr);
   return rc;
 }
 
@@ -826,25 +807,23 @@ int gs_group_destroy(gs_group_t g) {
   for (int k = 0; k < kLag; ++k) {
     for (hipEvent_t e : {g->counted[k], g->gathered[k], g->applied[k]})
       if (e) (void)hipEventDestroy(e);
-    (void)dfree(g->send[k]);
-    (void)dfree(g->recv[k]);
   }
   if (g->part) {
     if (g->G) (void)gs_destroy(g->G);
-    for (void* q : {(void*)g->ot.tab, (void*)g->mark, (void*)g->snap, (void*)g->pflags, (void*)g->pdev, (void*)g->stage,
-                    (void*)g->sendbuf, (void*)g->recvbuf, (void*)g->pairs, (void*)g->pairs_all, (void*)g->bcnt, (void*)g->pset})
-      (void)dfree(q);
     if (g->phost) (void)hipHostFree(g->phost);
     if (g->pev) (void)hipEventDestroy(g->pev);
     if (g->window && !g->prev_track) (void)gs_set_delta_tracking(g->h, 0);
   }
   ph_drain(g);
   for (hipEvent_t e : g->ph_pool) (void)hipEventDestroy(e);
-  (void)dfree(g->cnt);
-  if (g->xc) (void)hipStreamDestroy(g->xc);
-  if (g->xd) (void)hipStreamDestroy(g->xd);
-  if (g->hdr_host) (void)hipHostFree(g->hdr_host);
+  const hipStream_t xc = g->xc, xd = g->xd;
+  long long* const hdr_host = g->hdr_host;
+  // frees the group's device buffers (DevBuf members): g->h's device is current (dg), its
+  // stream, the side stream and the two communication streams are idle
   delete g;
+  if (xc) (void)hipStreamDestroy(xc);
+  if (xd) (void)hipStreamDestroy(xd);
+  if (hdr_host) (void)hipHostFree(hdr_host);
   return GS_OK;
 }
 
@@ -864,18 +843,15 @@ int part_of(gs_group* g) {
 
 // grow-only device buffer of `need` elements of T; `keep` elements are carried over (stream st)
 template <typename T>
-int ensure_buf(T*& buf, uint64_t& cap, uint64_t need, hipStream_t st, uint64_t keep = 0) {
-  if (need <= cap && buf) return GS_OK;
-  const uint64_t c = std::max<uint64_t>(need + need / 4, 1024);
-  T* nb = nullptr;
-  GS_HIP(dmalloc(&nb, c * sizeof(T)));
+int ensure_buf(DevBuf<T>& buf, uint64_t need, hipStream_t st, uint64_t keep = 0) {
+  if (need <= buf.size() && buf) return GS_OK;
+  DevBuf<T> nb;
+  GS_HIP(nb.alloc(std::max<uint64_t>(need + need / 4, 1024)));
   if (buf) {
     if (keep) GS_HIP(hipMemcpyAsync(nb, buf, keep * sizeof(T), hipMemcpyDeviceToDevice, st));
     GS_HIP(hipStreamSynchronize(st));
-    (void)dfree(buf);
   }
-  buf = nb;
-  cap = c;
+  buf.swap(nb);  // (the old buffer, now idle, is freed with nb)
   return GS_OK;
 }
 
@@ -941,17 +917,16 @@ int gs_group_create_partitioned(gs_group_t* out, gs_handle h, const void* id, in
   if (ocap > (1ull << 31)) return bail(fail(GS_ERR_INVALID, "vertices_hint too large for the owner table"));
   g->ot.cap = (uint32_t)ocap;
   g->ot.mask = (uint32_t)(ocap - 1);
-  int lg = 0;
-  while ((1ull << lg) < ocap) ++lg;
-  g->ot.shift = 64 - lg;
+  g->ot.shift = 64 - log2_ceil(ocap);
   g->ot.r0 = (uint32_t)ocap;
   const size_t pwords = 8 + (size_t)nranks + (size_t)nranks * nranks + nranks;
-  bool ok = dmalloc(&g->ot.tab, (ocap + 1) * sizeof(gs::OwnerSlot)) == hipSuccess &&
-            dmalloc(&g->mark, gs::kShards * 4) == hipSuccess && dmalloc(&g->snap, gs::kShards * 4) == hipSuccess &&
-            dmalloc(&g->pflags, 16) == hipSuccess && dmalloc(&g->pdev, pwords * 8) == hipSuccess &&
+  bool ok = g->ot_tab.alloc(ocap + 1) == hipSuccess && g->mark.alloc(gs::kShards) == hipSuccess &&
+            g->snap.alloc(gs::kShards) == hipSuccess && g->pflags.alloc(4) == hipSuccess &&
+            g->pdev.alloc(pwords) == hipSuccess &&
             hipHostMalloc(&g->phost, pwords * 8, hipHostMallocDefault) == hipSuccess &&
             hipEventCreateWithFlags(&g->pev, hipEventDisableTiming) == hipSuccess;
   if (!ok) return bail(fail(GS_ERR_HIP, "partitioned group allocation failed"));
+  g->ot.tab = g->ot_tab;
   g->ot.err = g->pflags;
   if (int rc = part_init_tables(g)) return bail(rc);
   GS_HIP(hipStreamSynchronize(h->stream));
@@ -1003,15 +978,15 @@ int gs_group_part_combine(gs_group_t g) {
   if (g->phost[2]) return fail(GS_ERR_CAPACITY, "vertex list overflow: the partitioned combine needs the list");
   const uint64_t total = g->phost[0], nrec = (g->window && h->track) ? g->phost[1] : 0;
   const uint32_t nblocks = (uint32_t)((total + gs::kPartRowsPB - 1) / gs::kPartRowsPB);
-  if (int rc = ensure_buf(g->stage, g->stage_cap, std::max<uint64_t>(total, 1) * W, st)) return rc;
-  if (int rc = ensure_buf(g->bcnt, g->bcnt_cap, (uint64_t)std::max<uint32_t>(nblocks, 1) * N, st)) return rc;
-  if (int rc = ensure_buf(g->pairs, g->pairs_cap, (nrec + 1) * W, st)) return rc;
+  if (int rc = ensure_buf(g->stage, std::max<uint64_t>(total, 1) * W, st)) return rc;
+  if (int rc = ensure_buf(g->bcnt, (uint64_t)std::max<uint32_t>(nblocks, 1) * N, st)) return rc;
+  if (int rc = ensure_buf(g->pairs, (nrec + 1) * W, st)) return rc;
   GS_HIP(hipMemsetAsync(g->pdev + 3, 0, 8, st));
   // 2. export the new vertices (marks their roots), then the marked roots hooked away
   gs::launch_part_export(sign, h->table(), g->mark, g->snap, full ? 1 : 0, total, g->stage, W, g->bcnt, N, st);
   GS_HIP(hipGetLastError());
   if (nrec) {
-    gs::launch_part_records(sign, h->table(), D, g->pairs, W, g->pdev + 3, g->pairs_cap / W, st);
+    gs::launch_part_records(sign, h->table(), D, g->pairs, W, g->pdev + 3, g->pairs.size() / W, st);
     GS_HIP(hipGetLastError());
   }
   if (h->track) {  // the window's records are consumed
@@ -1026,7 +1001,7 @@ int gs_group_part_combine(gs_group_t g) {
   } else {
     GS_HIP(hipMemsetAsync(sendcnt, 0, (size_t)N * 8, st));
   }
-  if (int rc = ensure_buf(g->sendbuf, g->send_cap, std::max<uint64_t>(total, 1) * W, st)) return rc;
+  if (int rc = ensure_buf(g->sendbuf, std::max<uint64_t>(total, 1) * W, st)) return rc;
   gs::launch_part_scatter(g->stage, total, W, g->bcnt, nblocks, sendcnt, N, g->sendbuf, st);
   GS_HIP(hipGetLastError());
   GS_HIP(hipMemcpyAsync(g->mark, g->snap, gs::kShards * 4, hipMemcpyDeviceToDevice, st));
@@ -1047,7 +1022,7 @@ int gs_group_part_combine(gs_group_t g) {
     rd[q] = (size_t)total_recv * W;
     total_recv += rcv[q] / W;
   }
-  if (int rc = ensure_buf(g->recvbuf, g->recv_cap, std::max<uint64_t>(total_recv, 1) * W, st)) return rc;
+  if (int rc = ensure_buf(g->recvbuf, std::max<uint64_t>(total_recv, 1) * W, st)) return rc;
   if (!g->api.all_to_allv) return fail(GS_ERR_HIP, "the comm backend has no all_to_allv");
   r = g->api.all_to_allv(g->sendbuf, sc.data(), sd.data(), g->recvbuf, rcv.data(), rd.data(), kNcclInt64, g->comm_d,
                          st);
@@ -1055,19 +1030,19 @@ int gs_group_part_combine(gs_group_t g) {
   ph_end(g, 3, p2, st);
   // 5. the owner step: anchors and label pairs
   hipEvent_t p3 = ph_begin(g, st);
-  if (int rc = ensure_buf(g->pairs, g->pairs_cap, (nrec + total_recv + 1) * W, st, nrec * W)) return rc;
+  if (int rc = ensure_buf(g->pairs, (nrec + total_recv + 1) * W, st, nrec * W)) return rc;
   // the pair set: ~1 slot per 4 received rows (2^12 .. 2^20: its probe bound lets a full set
   // emit a repeat, never drop a pair), cleared per combine
   gs::PairSet ps{nullptr, 0};
   if (N > 1 && total_recv) {
     uint64_t slots = 1ull << 12;
     while (slots < total_recv / 4 && slots < (1ull << 20)) slots <<= 1;
-    if (int rc = ensure_buf(g->pset, g->pset_cap, slots, st)) return rc;
+    if (int rc = ensure_buf(g->pset, slots, st)) return rc;
     GS_HIP(hipMemsetAsync(g->pset, 0, slots * sizeof(gs::PairSlot), st));
     ps.tab = g->pset;
     ps.mask = (uint32_t)(slots - 1);
   }
-  gs::launch_part_owner(sign, g->ot, ps, g->recvbuf, total_recv, W, g->pairs, g->pdev + 3, g->pairs_cap / W,
+  gs::launch_part_owner(sign, g->ot, ps, g->recvbuf, total_recv, W, g->pairs, g->pdev + 3, g->pairs.size() / W,
                         g->pflags + 1, st);
   GS_HIP(hipGetLastError());
   gs::launch_part_count_word(g->pdev + 3, sign ? h->ctr + gs::ctr_index(gs::CTR_FAIL) : nullptr,
@@ -1088,10 +1063,10 @@ int gs_group_part_combine(gs_group_t g) {
     live += c;
     if (q == g->rank) own = c;
   }
-  if (own > g->pairs_cap / W) return fail(GS_ERR_CAPACITY, "label pair buffer overflow");
+  if (own > g->pairs.size() / W) return fail(GS_ERR_CAPACITY, "label pair buffer overflow");
   const uint64_t rows = std::max<uint64_t>(maxp, 1);
-  if (int rc = ensure_buf(g->pairs, g->pairs_cap, rows * W, st, own * W)) return rc;
-  if (int rc = ensure_buf(g->pairs_all, g->pairs_all_cap, (uint64_t)N * rows * W, st)) return rc;
+  if (int rc = ensure_buf(g->pairs, rows * W, st, own * W)) return rc;
+  if (int rc = ensure_buf(g->pairs_all, (uint64_t)N * rows * W, st)) return rc;
   r = g->api.all_gather(g->pairs, g->pairs_all, rows * W, kNcclInt64, g->comm_d, st);
   if (r) return rccl_fail(&g->api, "ncclAllGather(label pairs)", r);
   GS_HIP(hipEventRecord(g->pev, st));

@@ -1,12 +1,14 @@
 // gs_internal.hpp -- the summary handle and the internal entry points shared by
-// gs_capi.cpp (include/gs_summary.h), gs_group.cpp (include/gs_group.h) and
-// gs_changes.cpp (per-window change emission).
+// gs_capi.cpp (include/gs_summary.h), gs_group.cpp (include/gs_group.h),
+// gs_changes.cpp (per-window change emission), gs_degree.cpp, gs_triangle.cpp and gs_sort.cpp.
+// Every device array a handle owns is a DevBuf (gs_devbuf.hpp): deleting the handle frees it.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <string>
 #include <vector>
 
+#include "gs_devbuf.hpp"
 #include "gs_ingest.hpp"
 #include "gs_kernels.hpp"
 #include "gs_sort.hpp"
@@ -19,15 +21,7 @@ int fail(int code, const std::string& msg);
 // gs_testing.h: a test knob's value, or `product` while the knob is unset
 int64_t testing_value(int knob, int64_t product);
 
-// Device memory of summaries and groups: hipMalloc / hipFree plus the per-device byte
-// count gs_hbm_bytes reports (tables that grow inside a fold or combine included).
-hipError_t dmalloc(void** p, size_t bytes);
-template <typename T>
-inline hipError_t dmalloc(T** p, size_t bytes) {
-  return dmalloc(reinterpret_cast<void**>(p), bytes);
-}
-hipError_t dfree(void* p);
-constexpr int kMaxDevices = 64;
+constexpr int kMaxDevices = 64;  // of the device-memory accounting (dmalloc / dfree, gs_devbuf.hpp)
 uint64_t create_capacity(uint64_t capacity_hint);
 uint64_t create_bytes(uint64_t cap);
 
@@ -62,6 +56,34 @@ inline uint64_t per_shard_edges(uint64_t c) {
   return ((blocks + gs::kShards - 1) / gs::kShards) * gs::kFoldBS;
 }
 
+inline uint64_t next_pow2(uint64_t x) {  // the smallest power of two >= x
+  uint64_t p = 1;
+  while (p < x) p <<= 1;
+  return p;
+}
+inline int log2_ceil(uint64_t x) {  // log2 of next_pow2(x)
+  int l = 0;
+  while ((1ull << l) < x) ++l;
+  return l;
+}
+
+// The kernels' view of a relabel table of cap slots (a power of two, logcap its log2) plus the
+// reserved slot; vertex list, new marks and host flags off until the caller sets them.
+inline gs::Table make_table(gs::Slot* tab, uint32_t* ctr, uint64_t cap, int logcap) {
+  gs::Table t;
+  t.tab = tab;
+  t.ctr = ctr;
+  t.cap = (uint32_t)cap;
+  t.mask = (uint32_t)(cap - 1);
+  t.shift = 64 - logcap;
+  t.r0 = (uint32_t)cap;
+  t.vlist = nullptr;
+  t.vshard_cap = 0;
+  t.mark_new = 0;
+  t.hflags = nullptr;
+  return t;
+}
+
 struct DeviceGuard {
   int prev = -1;
   explicit DeviceGuard(int d) {
@@ -80,11 +102,11 @@ struct gs_summary {
   int kind = GS_KIND_CC;
   hipStream_t stream = nullptr;
   // table + vertex list
-  gs::Slot* tab = nullptr;  // [cap + 1]: hashed slots + the reserved slot of INT64_MIN
+  gsi::DevBuf<gs::Slot> tab;  // [cap + 1]: hashed slots + the reserved slot of INT64_MIN
   uint64_t cap = 0;
   int logcap = 0;
-  uint32_t* ctr = nullptr;
-  uint32_t* vlist = nullptr;  // [kShards][vshard_cap]
+  gsi::DevBuf<uint32_t> ctr;
+  gsi::DevBuf<uint32_t> vlist;  // [kShards][vshard_cap]
   uint32_t vshard_cap = 0;
   uint32_t shard0 = 0;        // first shard of the next fold launch (rotates)
   bool vlist_ok = true;       // false once a shard of the vertex list overflowed (until reset)
@@ -117,7 +139,7 @@ struct gs_summary {
   // Two delta sets: a group's own fold b records into set b % 2 while the stage of
   // exchange b - 1 reads the other set on the communication stream.
   bool track = false;
-  int64_t* drec = nullptr;  // [kDeltaSets][kShards][delta_shard_cap][3]
+  gsi::DevBuf<int64_t> drec;  // [kDeltaSets][kShards][delta_shard_cap][3]
   uint32_t delta_shard_cap = 0;
   uint64_t delta_edges = 0;  // fold edges one delta set holds between two stages
   int dset = 0;              // the set tracked folds record into
@@ -125,44 +147,39 @@ struct gs_summary {
   // change tracking (gs_changes.cpp)
   bool changes = false;
   bool changes_own_track = false;  // change tracking turned delta tracking on (and turns it off)
-  uint32_t* nxt = nullptr;  // [cap + 1] circular member lists
+  gsi::DevBuf<uint32_t> nxt;  // [cap + 1] circular member lists
   uint64_t nxt_slots = 0;
-  unsigned long long* chg_scratch = nullptr;  // emission scratch: count, marks, big roots, staged records
+  gsi::DevBuf<unsigned long long> chg_scratch;  // emission scratch: count, marks, big roots, staged records
   uint64_t chg_scratch_rows = 0;
-  int64_t* chg_ov = nullptr;  // gs_take_changes (host arrays): device rows before the copy
-  int64_t* chg_ol = nullptr;
-  uint8_t* chg_op = nullptr;
+  gsi::DevBuf<int64_t> chg_ov;  // gs_take_changes (host arrays): device rows before the copy
+  gsi::DevBuf<int64_t> chg_ol;
+  gsi::DevBuf<uint8_t> chg_op;
   uint64_t chg_ocap = 0;
   bool chg_scan_all = false;  // the next emission emits every vertex (after a rebuild)
   // staging for host folds
-  int64_t* d_stage = nullptr;  // [2][2][d_stage_chunk] (allocated by the first host fold)
-  uint8_t* d_wstage = nullptr; // [2][d_stage_chunk]
+  gsi::DevBuf<int64_t> d_stage;   // [2][2][d_stage_chunk] (allocated by the first host fold)
+  gsi::DevBuf<uint8_t> d_wstage;  // [2][d_stage_chunk]
   uint64_t d_stage_chunk = 0;  // edges per staging buffer
   int64_t* h_stage = nullptr;  // pinned, same shape: large host folds (allocated on first use)
   uint8_t* h_wstage = nullptr;
   hipEvent_t stage_ev[2] = {nullptr, nullptr};  // after each buffer's copies
   int stage_next = 0;
-  int64_t* d_scratch = nullptr;  // small scratch (find_one)
+  gsi::DevBuf<int64_t> d_scratch;  // small scratch (find_one)
   // combine export scratch (gs_combine source side): reused across calls
-  int64_t* x_v = nullptr;
-  int64_t* x_l = nullptr;
-  uint8_t* x_p = nullptr;
+  gsi::DevBuf<int64_t> x_v;
+  gsi::DevBuf<int64_t> x_l;
+  gsi::DevBuf<uint8_t> x_p;
   uint64_t x_cap = 0;
-  unsigned long long* x_cnt = nullptr;  // device: exported rows (u64) + failure flag (u32 at word 1)
+  gsi::DevBuf<unsigned long long> x_cnt;  // device: exported rows (u64) + failure flag (u32 at word 1)
   hipEvent_t x_ready = nullptr, x_used = nullptr;
   bool x_pending = false;  // x_used recorded by a consumer not yet waited for
-  // grouped component export (gs_export_components*): the radix sort's ping-pong pair buffers,
-  // per-workgroup histogram table and control words, sized by the first call that needs them;
-  // co_*: device staging of the host-array form
-  unsigned long long* cs_key[2] = {nullptr, nullptr};
-  uint32_t* cs_pay[2] = {nullptr, nullptr};
-  uint32_t* cs_table = nullptr;
-  uint32_t* cs_ctl = nullptr;
-  uint64_t cs_rows = 0;
-  int64_t* co_comp = nullptr;
-  unsigned long long* co_off = nullptr;
-  int64_t* co_member = nullptr;
-  uint8_t* co_sign = nullptr;
+  // grouped component export (gs_export_components*) and the degree exports: the radix sort's
+  // scratch, sized by the first call that needs it; co_*: device staging of the host-array form
+  gsi::SortScratch sort;
+  gsi::DevBuf<int64_t> co_comp;
+  gsi::DevBuf<unsigned long long> co_off;
+  gsi::DevBuf<int64_t> co_member;
+  gsi::DevBuf<uint8_t> co_sign;
   uint64_t co_vcap = 0, co_ccap = 0;
   // degree summary (GS_KIND_DEGREE, gs_degree.cpp): endpoint occurrences folded since reset --
   // the host-side bound that keeps every 32-bit counter below 2^31
@@ -171,10 +188,10 @@ struct gs_summary {
   char* h_text = nullptr;
   uint64_t* h_tres = nullptr;
   hipEvent_t text_ev[2] = {nullptr, nullptr};
-  char* d_text = nullptr;
-  int64_t* d_tsrc = nullptr;
-  int64_t* d_tdst = nullptr;
-  void* d_tscratch = nullptr;
+  gsi::DevBuf<char> d_text;
+  gsi::DevBuf<int64_t> d_tsrc;
+  gsi::DevBuf<int64_t> d_tdst;
+  gsi::DevBuf<void> d_tscratch;  // (bytes)
   gs::ParseScratch tscratch;
   // pipelined folds (gs_set_pipelining): consecutive plain device folds alternate
   // over lane streams so that fold b+1 may start while fold b drains; every other
@@ -206,8 +223,8 @@ struct gs_summary {
   // fold may run on (handle stream, lanes, side stream): pair table + skip marks
   bool dedup = false;
   static constexpr int kDedupSets = kLanes + 2;
-  unsigned long long* dd_tab[kDedupSets] = {};
-  uint8_t* dd_w[kDedupSets] = {};
+  gsi::DevBuf<unsigned long long> dd_tab[kDedupSets];
+  gsi::DevBuf<uint8_t> dd_w[kDedupSets];
   uint64_t dd_edges[kDedupSets] = {};  // edges a set holds (its table has 2x that, a power of two)
   uint64_t dd_kept_hint = 0;
   // resident window server (gs_set_window_server): one persistent launch serves the
@@ -215,7 +232,7 @@ struct gs_summary {
   bool srv_on = false, srv_running = false;
   int srv_fits = -1;                     // all kServerBlocks workgroups co-resident (-1: not yet checked)
   gs::ServerBox* srv_box = nullptr;      // host-mapped mailbox
-  gs::ServerBcast* srv_bc = nullptr;     // device: block 0 -> other blocks
+  gsi::DevBuf<gs::ServerBcast> srv_bc;   // device: block 0 -> other blocks
   unsigned long long srv_seq = 0;        // last window posted and completed
   uint64_t srv_launches = 0, srv_windows = 0;
   // profiling
@@ -230,13 +247,7 @@ struct gs_summary {
   double total_ms[gsi::KID_N] = {0, 0, 0, 0};
 
   gs::Table table() const {
-    gs::Table t;
-    t.tab = tab;
-    t.ctr = ctr;
-    t.cap = (uint32_t)cap;
-    t.mask = (uint32_t)(cap - 1);
-    t.shift = 64 - logcap;
-    t.r0 = (uint32_t)cap;
+    gs::Table t = gsi::make_table(tab, ctr, cap, logcap);
     t.vlist = vlist;
     t.vshard_cap = vshard_cap;
     t.mark_new = changes ? 1 : 0;
@@ -309,7 +320,6 @@ int change_tracking_reset(gs_summary* h, int mode);
 int x_scratch(gs_summary* h, uint64_t rows);     // combine scratch x_v / x_l / x_p of >= rows rows, free to write
 void exact_count(gs_summary* h, uint64_t nv);    // an exact vertex count read with every queued fold complete
 int rebuild_table(gs_summary* h, uint64_t cap);  // free the table, allocate and initialise one of cap slots
-int sort_scratch(gs_summary* h, uint64_t rows);  // the radix sort's ping-pong buffers and tables
 int comp_staging(gs_summary* h, uint64_t nv, uint64_t nc);  // co_member / co_sign (nv), co_comp / co_off (nc)
 int dev_stage(gs_summary* h, size_t edges);      // device staging of host folds (d_stage, d_wstage)
 // gs_degree.cpp, called by the shared entry points of gs_capi.cpp on a degree summary

@@ -1,0 +1,56 @@
+// gs_sort.cpp -- the host side of the radix sort (gs_sort.hpp, kernels in gs_sort_k.hip): the
+// owner of its scratch and the one loop that queues its passes, shared by the component export
+// (gs_capi.cpp), the degree exports (gs_degree.cpp) and the triangle fold (gs_triangle.cpp).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "gs_internal.hpp"
+
+namespace gsi {
+
+int sort_scratch_ensure(SortScratch& s, uint64_t rows, hipStream_t st) {
+  if (!s.ctl) GS_HIP(s.ctl.alloc(gs::kSortCtlWords));
+  if (s.rows >= rows) return GS_OK;
+  GS_HIP(hipStreamSynchronize(st));
+  s.rows = 0;
+  for (int i = 0; i < 2; ++i) {
+    s.key[i].reset();
+    s.pay[i].reset();
+  }
+  s.table.reset();
+  const uint64_t c = gs::sort_blocks(rows + rows / 4) * gs::kSortTile;
+  for (int i = 0; i < 2; ++i) {
+    GS_HIP(s.key[i].alloc(c));
+    GS_HIP(s.pay[i].alloc(c));
+  }
+  GS_HIP(s.table.alloc(gs::kSortRadix * gs::sort_row_stride(gs::sort_blocks(c))));
+  s.rows = c;
+  return GS_OK;
+}
+
+void sort_skip_digits(const uint32_t* hist, uint64_t n, bool skip[gs::kSortPasses]) {
+  for (int p = 0; p < (int)gs::kSortPasses; ++p) {
+    const uint32_t* gh = hist + p * gs::kSortRadix;
+    skip[p] = *std::max_element(gh, gh + gs::kSortRadix) == n;
+  }
+}
+
+int sort_run(SortScratch& s, const int64_t* ids, uint64_t n, const uint32_t* hist, const bool* skip, gs::SortSrc* cur,
+             int* side, hipStream_t st) {
+  cur->key = nullptr;
+  cur->ids = ids;
+  cur->rows = n;
+  for (int p = 0; p < (int)gs::kSortPasses; ++p) {
+    if (skip && skip[p]) continue;
+    gs::launch_sort_pass(*cur, n, p, s.table, hist + p * gs::kSortRadix, s.key[*side], s.pay[*side], st);
+    GS_HIP(hipGetLastError());
+    cur->key = s.key[*side];
+    cur->pay = s.pay[*side];
+    cur->ids = nullptr;
+    *side ^= 1;
+  }
+  return GS_OK;
+}
+
+}  // namespace gsi

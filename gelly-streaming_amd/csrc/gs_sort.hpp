@@ -3,9 +3,13 @@
 // 8-bit digits, and the tail that turns rows sorted by (label, vertex) into the CSR of
 // gs_export_components*. Every launch is queued on the given stream; kernel boundaries
 // carry all ordering between workgroups (no workgroup waits on another inside a launch).
+// The host part at the end (gs_sort.cpp) owns the sort's scratch and drives its passes for
+// every caller: the component export, the degree exports and the triangle fold.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "gs_devbuf.hpp"
 
 namespace gs {
 
@@ -59,3 +63,34 @@ void launch_comp_csr(const SortSrc& src, uint64_t n, const int64_t* v, const uin
                      uint64_t cap_c, hipStream_t st);
 
 }  // namespace gs
+
+// ---- host only (gs_sort.cpp) ----
+namespace gsi {
+
+// The sort's scratch: ping-pong (key, payload) buffers, the per-workgroup histogram table
+// (also the tile scratch of launch_comp_csr) and the control words of launch_sort_digits.
+struct SortScratch {
+  DevBuf<unsigned long long> key[2];
+  DevBuf<uint32_t> pay[2];
+  DevBuf<uint32_t> table;
+  DevBuf<uint32_t> ctl;  // gs::kSortCtlWords, allocated on first use
+  uint64_t rows = 0;     // pairs key / pay hold (0 while they are not all allocated)
+};
+
+// Scratch for `rows` pairs: allocated on growth only, with a quarter of headroom rounded up
+// to whole tiles. Synchronises st before it frees.
+int sort_scratch_ensure(SortScratch& s, uint64_t rows, hipStream_t st);
+
+// skip[p] = every one of the n keys agrees on digit p (its 256-bin row of `hist`, a host copy
+// of eight rows, has one bin holding n): the pass would be an identity.
+void sort_skip_digits(const uint32_t* hist, uint64_t n, bool skip[gs::kSortPasses]);
+
+// Stable radix passes on st over the digits of ids[payload] ^ kSortSignBit that `skip` (may be
+// null: none) does not mark. hist: the device address of the eight 256-bin rows of those keys.
+// Continues from *cur / *side: the payloads of an earlier sort carry over (a chained sort by a
+// second key). On return *cur names the sorted (key, payload) pairs -- key null when no pass
+// ran, the order is then *cur's order on entry -- and *side the buffer not holding them.
+int sort_run(SortScratch& s, const int64_t* ids, uint64_t n, const uint32_t* hist, const bool* skip, gs::SortSrc* cur,
+             int* side, hipStream_t st);
+
+}  // namespace gsi

@@ -25,59 +25,43 @@ struct gs_triangles_s {
   hipStream_t stream = nullptr;
   hipEvent_t ext_ev = nullptr;
   // relabel table with the counters t(v)
-  gs::Slot* tab = nullptr;
+  DevBuf<gs::Slot> tab;
   uint64_t cap = 0;
   int logcap = 0;
-  uint32_t* ctr = nullptr;
-  unsigned long long* ctl = nullptr;  // gs::TriCtl words
+  DevBuf<uint32_t> ctr;
+  DevBuf<unsigned long long> ctl;  // gs::TriCtl words
   // adjacency: two buffers, the merge of a fold reads one and writes the other
-  int64_t* ax[2] = {nullptr, nullptr};
-  int64_t* ay[2] = {nullptr, nullptr};
-  uint32_t* aseq[2] = {nullptr, nullptr};
+  DevBuf<int64_t> ax[2];
+  DevBuf<int64_t> ay[2];
+  DevBuf<uint32_t> aseq[2];
   uint64_t acap[2] = {0, 0};
   int cur = 0;
   uint64_t entries = 0;  // live entries of buffer `cur` (2 |G|)
   uint64_t edges = 0;    // |G|, exact after every fold
   uint32_t seq = 0;      // number of the last fold
-  // fold scratch, sized for f_cap elements
+  // fold scratch, sized for f_cap elements; the radix sort's scratch holds as many pairs
   uint64_t f_cap = 0;
-  int64_t* stage = nullptr;  // [2][f_cap] host folds
-  int64_t* lo = nullptr;     // canonical pairs; later the reverse entries of N
-  int64_t* hi = nullptr;
-  int64_t* nx = nullptr;     // N
-  int64_t* ny = nullptr;
-  gs::TriRowInfo* info = nullptr;
-  uint32_t* list1 = nullptr;
-  uint32_t* list2 = nullptr;
-  unsigned long long* skey[2] = {nullptr, nullptr};
-  uint32_t* spay[2] = {nullptr, nullptr};
-  uint32_t* stable = nullptr;
-  uint32_t* sctl = nullptr;
+  DevBuf<int64_t> stage;  // [2][f_cap] host folds
+  DevBuf<int64_t> lo;     // canonical pairs; later the reverse entries of N
+  DevBuf<int64_t> hi;
+  DevBuf<int64_t> nx;     // N
+  DevBuf<int64_t> ny;
+  DevBuf<gs::TriRowInfo> info;
+  DevBuf<uint32_t> list1;
+  DevBuf<uint32_t> list2;
+  SortScratch sort;
   // flag / tile-count scratch of the dedup and of the exports, sized for g_cap elements
   uint64_t g_cap = 0;
-  uint8_t* flags = nullptr;
-  uint32_t* blk = nullptr;
+  DevBuf<uint8_t> flags;
+  DevBuf<uint32_t> blk;
   // device staging of the host export
   uint64_t o_cap = 0;
-  int64_t* o_v = nullptr;
-  int64_t* o_c = nullptr;
+  DevBuf<int64_t> o_v;
+  DevBuf<int64_t> o_c;
   // diagnostics (gs_testing_triangle_stats): phase times of the last profiled fold, microseconds
   uint64_t phase_us[4] = {0, 0, 0, 0};
 
-  gs::Table table() const {
-    gs::Table t;
-    t.tab = tab;
-    t.ctr = ctr;
-    t.cap = (uint32_t)cap;
-    t.mask = (uint32_t)(cap - 1);
-    t.shift = 64 - logcap;
-    t.r0 = (uint32_t)cap;
-    t.vlist = nullptr;
-    t.vshard_cap = 0;
-    t.mark_new = 0;
-    t.hflags = nullptr;
-    return t;
-  }
+  gs::Table table() const { return make_table(tab, ctr, cap, logcap); }
   gs::TriAdj adj() const {
     gs::TriAdj a;
     a.x = ax[cur];
@@ -104,24 +88,12 @@ int count_variant() {
   return v >= 0 && v < gs::kTriangleVariants ? (int)v : gs::kTriangleProduct;
 }
 
-template <typename T>
-void release(T*& p) {
-  (void)dfree(p);
-  p = nullptr;
-}
-
-uint64_t pow2_at_least(uint64_t x) {
-  uint64_t p = 1;
-  while (p < x) p <<= 1;
-  return p;
-}
-
+// (t->tab empty: gs_triangle_create, or grow_table holding the old table aside)
 int alloc_table(gs_triangles_s* t, uint64_t cap) {
   if (cap > kMaxCap) return fail(GS_ERR_CAPACITY, "vertex table would exceed 2^30 slots");
-  GS_HIP(dmalloc(&t->tab, (cap + 1) * sizeof(gs::Slot)));
+  GS_HIP(t->tab.alloc(cap + 1));
   t->cap = cap;
-  t->logcap = 0;
-  while ((1ull << t->logcap) < cap) ++t->logcap;
+  t->logcap = log2_ceil(cap);
   gs::launch_tri_init(t->table(), t->stream);
   GS_HIP(hipGetLastError());
   return GS_OK;
@@ -130,14 +102,11 @@ int alloc_table(gs_triangles_s* t, uint64_t cap) {
 int ensure_adj(gs_triangles_s* t, int side, uint64_t need) {
   if (t->acap[side] >= need) return GS_OK;
   GS_HIP(hipStreamSynchronize(t->stream));
-  release(t->ax[side]);
-  release(t->ay[side]);
-  release(t->aseq[side]);
   t->acap[side] = 0;
   const uint64_t c = std::min<uint64_t>(kTriMaxEntries, need + need / 2);
-  GS_HIP(dmalloc(&t->ax[side], c * 8));
-  GS_HIP(dmalloc(&t->ay[side], c * 8));
-  GS_HIP(dmalloc(&t->aseq[side], c * 4));
+  GS_HIP(t->ax[side].alloc(c));
+  GS_HIP(t->ay[side].alloc(c));
+  GS_HIP(t->aseq[side].alloc(c));
   t->acap[side] = c;
   return GS_OK;
 }
@@ -145,69 +114,30 @@ int ensure_adj(gs_triangles_s* t, int side, uint64_t need) {
 int ensure_flags(gs_triangles_s* t, uint64_t n) {
   if (t->g_cap >= n) return GS_OK;
   GS_HIP(hipStreamSynchronize(t->stream));
-  release(t->flags);
-  release(t->blk);
   t->g_cap = 0;
   const uint64_t c = n + n / 4;
-  GS_HIP(dmalloc(&t->flags, c));
-  GS_HIP(dmalloc(&t->blk, (gs::tri_blocks(c) + 1) * 4));
+  GS_HIP(t->flags.alloc(c));
+  GS_HIP(t->blk.alloc(gs::tri_blocks(c) + 1));
   t->g_cap = c;
   return GS_OK;
 }
 
 int ensure_fold_scratch(gs_triangles_s* t, uint64_t n) {
   if (int rc = ensure_flags(t, n)) return rc;
-  if (!t->sctl) GS_HIP(dmalloc(&t->sctl, gs::kSortCtlWords * 4));
+  if (int rc = sort_scratch_ensure(t->sort, n, t->stream)) return rc;
   if (t->f_cap >= n) return GS_OK;
   GS_HIP(hipStreamSynchronize(t->stream));
-  release(t->stage);
-  release(t->lo);
-  release(t->hi);
-  release(t->nx);
-  release(t->ny);
-  release(t->info);
-  release(t->list1);
-  release(t->list2);
-  for (int i = 0; i < 2; ++i) {
-    release(t->skey[i]);
-    release(t->spay[i]);
-  }
-  release(t->stable);
   t->f_cap = 0;
-  const uint64_t c = gs::sort_blocks(n + n / 4) * gs::kSortTile;
-  GS_HIP(dmalloc(&t->stage, 2 * c * 8));
-  GS_HIP(dmalloc(&t->lo, c * 8));
-  GS_HIP(dmalloc(&t->hi, c * 8));
-  GS_HIP(dmalloc(&t->nx, c * 8));
-  GS_HIP(dmalloc(&t->ny, c * 8));
-  GS_HIP(dmalloc(&t->info, c * sizeof(gs::TriRowInfo)));
-  GS_HIP(dmalloc(&t->list1, c * 4));
-  GS_HIP(dmalloc(&t->list2, c * 4));
-  for (int i = 0; i < 2; ++i) {
-    GS_HIP(dmalloc(&t->skey[i], c * 8));
-    GS_HIP(dmalloc(&t->spay[i], c * 4));
-  }
-  GS_HIP(dmalloc(&t->stable, gs::kSortRadix * gs::sort_row_stride(gs::sort_blocks(c)) * 4));
+  const uint64_t c = gs::sort_blocks(n + n / 4) * gs::kSortTile;  // (the sort scratch's count)
+  GS_HIP(t->stage.alloc(2 * c));
+  GS_HIP(t->lo.alloc(c));
+  GS_HIP(t->hi.alloc(c));
+  GS_HIP(t->nx.alloc(c));
+  GS_HIP(t->ny.alloc(c));
+  GS_HIP(t->info.alloc(c));
+  GS_HIP(t->list1.alloc(c));
+  GS_HIP(t->list2.alloc(c));
   t->f_cap = c;
-  return GS_OK;
-}
-
-// Stable radix passes over the digits of ids[payload] that `skip` does not mark; hist: the
-// eight 256-bin device rows of those keys. Continues from *cur / *side.
-int sort_by(gs_triangles_s* t, const int64_t* ids, uint64_t n, const uint32_t* hist, const bool* skip, gs::SortSrc* cur,
-            int* side) {
-  cur->key = nullptr;
-  cur->ids = ids;
-  cur->rows = n;
-  for (int p = 0; p < (int)gs::kSortPasses; ++p) {
-    if (skip && skip[p]) continue;
-    gs::launch_sort_pass(*cur, n, p, t->stable, hist + p * gs::kSortRadix, t->skey[*side], t->spay[*side], t->stream);
-    GS_HIP(hipGetLastError());
-    cur->key = t->skey[*side];
-    cur->pay = t->spay[*side];
-    cur->ids = nullptr;
-    *side ^= 1;
-  }
   return GS_OK;
 }
 
@@ -215,10 +145,10 @@ int sort_by(gs_triangles_s* t, const int64_t* ids, uint64_t n, const uint32_t* h
 int grow_table(gs_triangles_s* t, uint64_t new_cap) {
   if (new_cap > kMaxCap) return fail(GS_ERR_CAPACITY, "vertex table would exceed 2^30 slots");
   const gs::Table old = t->table();
-  gs::Slot* old_tab = t->tab;
-  t->tab = nullptr;
+  DevBuf<gs::Slot> old_tab;  // (alive until the new table holds its counters)
+  old_tab.swap(t->tab);
   if (int rc = alloc_table(t, new_cap)) {
-    t->tab = old_tab;  // (the old table still serves)
+    old_tab.swap(t->tab);  // (the old table still serves)
     t->cap = old.cap;
     t->logcap = 64 - old.shift;
     return rc;
@@ -226,7 +156,6 @@ int grow_table(gs_triangles_s* t, uint64_t new_cap) {
   gs::launch_tri_rehash(old, t->table(), t->adj(), t->stream);
   GS_HIP(hipGetLastError());
   GS_HIP(hipStreamSynchronize(t->stream));
-  (void)dfree(old_tab);
   return GS_OK;
 }
 
@@ -270,13 +199,16 @@ int fold_impl(gs_triangles_s* t, const int64_t* src, const int64_t* dst, uint64_
   GS_HIP(hipGetLastError());
   timer.mark(1);
   // 2. sort by max, then stably by min; flag, scan, compact: N in (nx, ny)
-  GS_HIP(hipMemsetAsync(t->sctl, 0, gs::kSortCtlWords * 4, t->stream));
-  gs::launch_sort_digits(t->lo, t->hi, n, t->sctl, t->stream);  // rows 0..7: min, rows 8..15: max
+  // (no digit is skipped: the histograms are on the device only)
+  uint32_t* const sctl = t->sort.ctl;
+  GS_HIP(hipMemsetAsync(sctl, 0, gs::kSortCtlWords * 4, t->stream));
+  gs::launch_sort_digits(t->lo, t->hi, n, sctl, t->stream);  // rows 0..7: min, rows 8..15: max
   GS_HIP(hipGetLastError());
   gs::SortSrc cur;
   int side = 0;
-  if (int rc = sort_by(t, t->hi, n, t->sctl + gs::kSortPasses * gs::kSortRadix, nullptr, &cur, &side)) return rc;
-  if (int rc = sort_by(t, t->lo, n, t->sctl, nullptr, &cur, &side)) return rc;
+  if (int rc = sort_run(t->sort, t->hi, n, sctl + gs::kSortPasses * gs::kSortRadix, nullptr, &cur, &side, t->stream))
+    return rc;
+  if (int rc = sort_run(t->sort, t->lo, n, sctl, nullptr, &cur, &side, t->stream)) return rc;
   gs::launch_tri_flag_new(cur.pay, t->lo, t->hi, n, t->adj(), t->flags, t->blk, t->stream);
   GS_HIP(hipGetLastError());
   gs::launch_tri_scan(t->blk, gs::tri_blocks(n), t->ctl, gs::TRI_NEW, -1, t->stream);
@@ -287,7 +219,7 @@ int fold_impl(gs_triangles_s* t, const int64_t* src, const int64_t* dst, uint64_
   unsigned long long words[4] = {0, 0, 0, 0};
   std::vector<uint32_t> hist(gs::kSortPasses * gs::kSortRadix);
   GS_HIP(hipMemcpyAsync(words, t->ctl, sizeof(words), hipMemcpyDeviceToHost, t->stream));
-  GS_HIP(hipMemcpyAsync(hist.data(), t->sctl + gs::kSortPasses * gs::kSortRadix, hist.size() * 4,
+  GS_HIP(hipMemcpyAsync(hist.data(), sctl + gs::kSortPasses * gs::kSortRadix, hist.size() * 4,
                         hipMemcpyDeviceToHost, t->stream));
   timer.mark(2);
   GS_HIP(hipStreamSynchronize(t->stream));
@@ -308,16 +240,13 @@ int fold_impl(gs_triangles_s* t, const int64_t* src, const int64_t* dst, uint64_
   // 3. N ordered by (max, min): a stable sort of N by max. A digit on which every max of the
   // fold agrees is an identity pass for N's subset of them.
   bool skip[gs::kSortPasses];
-  for (int p = 0; p < (int)gs::kSortPasses; ++p) {
-    const uint32_t* gh = hist.data() + p * gs::kSortRadix;
-    skip[p] = *std::max_element(gh, gh + gs::kSortRadix) == n;
-  }
-  GS_HIP(hipMemsetAsync(t->sctl, 0, gs::kSortCtlWords * 4, t->stream));
-  gs::launch_sort_digits(t->ny, t->ny, m, t->sctl, t->stream);
+  sort_skip_digits(hist.data(), n, skip);
+  GS_HIP(hipMemsetAsync(sctl, 0, gs::kSortCtlWords * 4, t->stream));
+  gs::launch_sort_digits(t->ny, t->ny, m, sctl, t->stream);
   GS_HIP(hipGetLastError());
   cur = gs::SortSrc();
   side = 0;
-  if (int rc = sort_by(t, t->ny, m, t->sctl, skip, &cur, &side)) return rc;
+  if (int rc = sort_run(t->sort, t->ny, m, sctl, skip, &cur, &side, t->stream)) return rc;
   gs::launch_tri_reverse(cur.pay, t->nx, t->ny, m, t->lo, t->hi, t->stream);
   GS_HIP(hipGetLastError());
   gs::TriAdjOut out;
@@ -375,12 +304,10 @@ int export_impl(gs_triangles_s* t, int64_t* v, int64_t* count, size_t cap, size_
   int64_t *dv = v, *dc = count;
   if (to_host) {
     if (t->o_cap < rows) {
-      release(t->o_v);
-      release(t->o_c);
       t->o_cap = 0;
       const uint64_t c = rows + rows / 4;
-      GS_HIP(dmalloc(&t->o_v, c * 8));
-      GS_HIP(dmalloc(&t->o_c, c * 8));
+      GS_HIP(t->o_v.alloc(c));
+      GS_HIP(t->o_c.alloc(c));
       t->o_cap = c;
     }
     dv = t->o_v;
@@ -404,33 +331,10 @@ int gs_triangle_destroy(gs_triangles t) {
   if (!t) return GS_OK;
   DeviceGuard g(t->device);
   if (t->stream) (void)hipStreamSynchronize(t->stream);
-  release(t->tab);
-  release(t->ctr);
-  release(t->ctl);
-  for (int i = 0; i < 2; ++i) {
-    release(t->ax[i]);
-    release(t->ay[i]);
-    release(t->aseq[i]);
-    release(t->skey[i]);
-    release(t->spay[i]);
-  }
-  release(t->stage);
-  release(t->lo);
-  release(t->hi);
-  release(t->nx);
-  release(t->ny);
-  release(t->info);
-  release(t->list1);
-  release(t->list2);
-  release(t->stable);
-  release(t->sctl);
-  release(t->flags);
-  release(t->blk);
-  release(t->o_v);
-  release(t->o_c);
   if (t->ext_ev) (void)hipEventDestroy(t->ext_ev);
-  if (t->stream) (void)hipStreamDestroy(t->stream);
-  delete t;
+  const hipStream_t stream = t->stream;
+  delete t;  // frees every device buffer (DevBuf members): device current, the stream idle
+  if (stream) (void)hipStreamDestroy(stream);
   return GS_OK;
 }
 
@@ -448,12 +352,12 @@ int gs_triangle_create(gs_triangles* out, int device, uint64_t edge_hint) {
   auto body = [&]() -> int {
     GS_HIP(hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking));
     GS_HIP(hipEventCreateWithFlags(&t->ext_ev, hipEventDisableTiming));
-    GS_HIP(dmalloc(&t->ctr, (size_t)gs::CTR_COUNT * gs::kCtrStride * 4));
+    GS_HIP(t->ctr.alloc((uint64_t)gs::CTR_COUNT * gs::kCtrStride));
     GS_HIP(hipMemsetAsync(t->ctr, 0, (size_t)gs::CTR_COUNT * gs::kCtrStride * 4, t->stream));
-    GS_HIP(dmalloc(&t->ctl, gs::TRI_CTL_WORDS * 8));
+    GS_HIP(t->ctl.alloc(gs::TRI_CTL_WORDS));
     GS_HIP(hipMemsetAsync(t->ctl, 0, gs::TRI_CTL_WORDS * 8, t->stream));
     const uint64_t e = std::max<uint64_t>(edge_hint, kTriMinCap / 2);
-    if (int r = alloc_table(t, std::min<uint64_t>(kMaxCap, pow2_at_least(2 * e)))) return r;
+    if (int r = alloc_table(t, std::min<uint64_t>(kMaxCap, next_pow2(2 * e)))) return r;
     if (int r = ensure_adj(t, 0, 2 * e)) return r;
     GS_HIP(hipStreamSynchronize(t->stream));
     return GS_OK;

@@ -3,6 +3,7 @@ authority: np.unique(..., return_counts=True) on the collected endpoints, additi
 deletions -- and against the reference's pinned outputs (tests/golden/degree_pins.json).
 Every output is an integer: comparisons are exact."""
 import ctypes
+import gc
 import json
 import os
 
@@ -379,6 +380,90 @@ def test_reset(gs):
         _check(D, np.zeros(0, np.int64), np.zeros(0, np.int64), absent=src[:5])
         D.fold(src[:300], dst[:300])
         _check(D, *_net(src[:300], dst[:300], "all"))
+
+
+# ------------------------------------------------------------------ the sort's edges, scratch
+def _distinct_ids(rng, rows):
+    """`rows` distinct ids of both signs, the extremes of the key order among them."""
+    special = np.array([-1, 0, I64_MIN, I64_MAX, 1, -(1 << 40)], np.int64)[:rows]
+    pool = np.setdiff1d(rng.integers(I64_MIN, I64_MAX, size=2 * rows + 8, dtype=np.int64), special)
+    ids = np.concatenate([special, rng.permutation(pool)[:rows - len(special)]])
+    assert len(np.unique(ids)) == rows and (rows < 2 or (ids.min() < 0 <= ids.max()))
+    return rng.permutation(ids)
+
+
+@pytest.mark.parametrize("uniform", [False, True])
+@pytest.mark.parametrize("rows", [1, 2047, 2048, 2049])  # one below, at, one above the sort's tile
+def test_sorted_export_at_the_sort_tile(gs, rows, uniform):
+    """The sorted export and the distribution at row counts around the radix sort's tile (2048
+    pairs a workgroup), over ids of both signs. uniform: every vertex has degree 1, so the
+    distribution's sort finds every key equal and runs no pass."""
+    rng = np.random.default_rng(6000 + rows)
+    ids = _distinct_ids(rng, rows)
+    mult = np.ones(rows, np.int64) if uniform else 1 + (np.arange(rows) % 5) * (np.arange(rows) % 3)
+    src = rng.permutation(np.repeat(ids, mult))
+    dst = np.roll(src, 1)  # ("out" collects sources only)
+    want_ids, want = _net(src, dst, "out")
+    assert len(want_ids) == rows and np.array_equal(want_ids, np.sort(ids))
+    with gs.Degrees("out", capacity_hint=rows) as D:
+        _fold_dev(D, src, dst)
+        _check(D, want_ids, want)
+        v, d = D.degrees(sorted=True)
+        assert np.array_equal(v, np.sort(ids)) and np.array_equal(d, mult[np.argsort(ids, kind="stable")])
+        gd, gc_ = D.distribution()
+        xd, xc = np.unique(mult, return_counts=True)
+        assert np.array_equal(gd, xd) and np.array_equal(gc_, xc)
+        if uniform:
+            assert gd.tolist() == [1] and gc_.tolist() == [rows]
+
+
+def test_scratch_is_counted_and_released(gs):
+    """gs_hbm_bytes over the degree exports: each call's scratch is allocated once, kept across
+    repeats and returned in full by close()."""
+    import torch
+    n = 5000
+    src = np.arange(n, dtype=np.int64) - n // 2
+    dst = src // 7 * 7
+    gc.collect()  # (no summary of an earlier test is released while this one counts)
+    start = gs.hbm_bytes()
+    D = gs.Degrees("all", capacity_hint=n)
+    try:
+        assert gs.hbm_bytes() - start == gs.create_bytes("degree", n)  # no export scratch yet
+        _fold_dev(D, src, dst)
+        ids, net = _net(src, dst, "all")
+        rows = len(ids)
+        assert n <= rows <= n + 1 and D.num_vertices() == rows
+        dev = torch.device("cuda", D.device)
+        tv = torch.empty(rows, dtype=torch.int64, device=dev)
+        td = torch.empty(rows, dtype=torch.int64, device=dev)
+        held = gs.hbm_bytes()
+        D.wait_stream("torch")
+        assert D.degrees_device(tv, td, sorted=True) == rows
+        exported = gs.hbm_bytes()
+        # two (key, payload) buffers of 12 bytes a row and a 256-row histogram table, with
+        # headroom, and the unordered rows (17 bytes a row of at least 0.7 x the table's slots)
+        assert 2 * 12 * rows + 17 * rows <= exported - held
+        k = D.distribution_device(tv, td)
+        assert 0 < k < rows
+        distributed = gs.hbm_bytes()
+        # the CSR staging of the run heads: members, signs, heads and offsets with a quarter of headroom
+        assert (8 + 1 + 16) * rows <= distributed - exported <= 2 * (8 + 1 + 16) * rows + 64
+        assert D.degrees_device(tv, td, sorted=True) == rows
+        assert D.distribution_device(tv, td) == k
+        assert gs.hbm_bytes() == distributed
+        D.degrees(sorted=True)
+        D.distribution()
+        host = gs.hbm_bytes()
+        assert host >= distributed
+        v, d = D.degrees(sorted=True)
+        gd, gc_ = D.distribution()
+        assert gs.hbm_bytes() == host
+        assert np.array_equal(v, ids) and np.array_equal(d, net)
+        xd, xc = np.unique(net, return_counts=True)
+        assert np.array_equal(gd, xd) and np.array_equal(gc_, xc)
+    finally:
+        D.close()
+    assert gs.hbm_bytes() == start
 
 
 # ------------------------------------------------------------------ combine, serialize
