@@ -73,7 +73,7 @@ EXPORTED_SYMBOLS = (
     "gs_triangle_create", "gs_triangle_destroy", "gs_triangle_reset", "gs_triangle_fold", "gs_triangle_fold_device",
     "gs_triangle_count", "gs_triangle_count_device", "gs_triangle_find_device", "gs_triangle_export_device",
     "gs_triangle_export", "gs_triangle_sync", "gs_triangle_get_stream", "gs_triangle_wait_stream",
-    "gs_testing_triangle_stats",
+    "gs_testing_triangle_stats", "gs_testing_triangle_bins",
 )
 
 # Pairs per workgroup of the component export's radix-sort kernels (csrc/gs_sort.hpp kSortTile):
@@ -90,6 +90,15 @@ DEGREE_TILE = 2048
 TRIANGLE_LANES = 8
 TRIANGLE_TILE = 1024
 TRIANGLE_VARIANTS = 2
+# The product's bins by row length (kTriShortRow, kTriWaveRow, kTriLdsRow, kTriSamples): a new
+# edge whose shorter row has at most TRIANGLE_SHORT_ROW entries takes a lane group; one whose
+# shorter row has more than TRIANGLE_WAVE_ROW and whose longer row has at least
+# TRIANGLE_LDS_ROW takes a workgroup with TRIANGLE_SAMPLES samples of the longer row in LDS;
+# every other takes a wave.
+TRIANGLE_SHORT_ROW = 32
+TRIANGLE_WAVE_ROW = 64
+TRIANGLE_LDS_ROW = 4096
+TRIANGLE_SAMPLES = 1024
 
 FAIL_BIT = 1 << 62  # count words: a failed signed verdict (GS_FAIL_BIT)
 DIGEST_FAILED = (1 << 64) - 1  # gs_digest of a signed summary whose verdict failed (GS_DIGEST_FAILED)
@@ -232,6 +241,7 @@ def lib():
     L.gs_triangle_get_stream.argtypes = [_vp, ctypes.POINTER(_vp)]
     L.gs_triangle_wait_stream.argtypes = [_vp, _vp]
     L.gs_testing_triangle_stats.argtypes = [_vp, ctypes.POINTER(_u64)]
+    L.gs_testing_triangle_bins.argtypes = [_vp, ctypes.POINTER(_u64)]
     L.gs_testing_set.argtypes = [ctypes.c_int, _i64]
     L.gs_testing_get.argtypes = [ctypes.c_int]
     L.gs_testing_get.restype = _i64
@@ -1014,6 +1024,13 @@ class Triangles:
         _check(lib().gs_testing_triangle_stats(self._h, out))
         return {"steps": out[0], "hot_row": out[1], "canon_us": out[2], "sort_dedup_us": out[3], "merge_us": out[4],
                 "count_us": out[5]}
+
+    def bins(self):
+        """gs_testing_triangle_bins: (wave, workgroup), the new edges the count step of the last
+        fold with new edges gave to a wave and to a workgroup; (0, 0) under triangle_variant 1."""
+        out = (_u64 * 2)()
+        _check(lib().gs_testing_triangle_bins(self._h, out))
+        return out[0], out[1]
 
 
 # ---------------------------------------------------------------- native multi-GPU group

@@ -492,4 +492,20 @@ int gs_testing_triangle_stats(void* handle, uint64_t* out) {
   return GS_OK;
 }
 
+// gs_testing.h: out[0] = edges of the wave list, out[1] = edges of the workgroup list of the
+// last fold that had new edges (both 0 under the wave variant and after reset). Synchronises.
+int gs_testing_triangle_bins(void* handle, uint64_t* out) {
+  gs_triangles t = static_cast<gs_triangles>(handle);
+  if (int rc = check_tri(t)) return rc;
+  if (!out) return fail(GS_ERR_INVALID, "out is null");
+  DeviceGuard g(t->device);
+  static_assert(gs::TRI_BIN2 == gs::TRI_BIN1 + 1, "the two list lengths are adjacent words");
+  unsigned long long w[2] = {0, 0};
+  GS_HIP(hipMemcpyAsync(w, t->ctl + gs::TRI_BIN1, sizeof(w), hipMemcpyDeviceToHost, t->stream));
+  GS_HIP(hipStreamSynchronize(t->stream));
+  out[0] = w[0];
+  out[1] = w[1];
+  return GS_OK;
+}
+
 }  // extern "C"

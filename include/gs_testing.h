@@ -65,6 +65,12 @@ int gs_testing_group_forest(void* g, void** forest);
  * dedup, merge (with the fold's host synchronisation and growth) and count phases. Six words. */
 int gs_testing_triangle_stats(void* t, uint64_t* out);
 
+/* The work assignment of a triangle handle's last fold that had new edges (`t` is a
+ * gs_triangles; synchronises): out[0] = edges the count step gave to a wave, out[1] = edges it
+ * gave to a workgroup with the longer row sampled in LDS; every other new edge took a lane
+ * group. Both are 0 under GS_TESTING_TRIANGLE_VARIANT 1 and after a reset. Two words. */
+int gs_testing_triangle_bins(void* t, uint64_t* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,9 @@
 same edge set -- with A the symmetric 0/1 adjacency without loops, t = rowsum((A.A) o A) / 2
 and T = sum(t) / 3 -- against networkx on small graphs, and against the reference's pinned
 outputs (tests/golden/triangle_pins.json). Every count is an integer: comparisons are exact.
-The shape cases run under every work assignment of the count step (triangle_variant)."""
+The shape cases run under every work assignment of the count step (triangle_variant).
+Section 11 fills every bin of the product's assignment at its thresholds and checks the
+assignment itself (the list lengths, the step count, the longest row) against a host model."""
 import ctypes
 import itertools
 import json
@@ -22,6 +24,9 @@ I64_MAX = np.iinfo(np.int64).max
 SENTINEL = -0x5A5A5A5A5A5A5A5B
 L = gsamd.TRIANGLE_LANES
 TILE = gsamd.TRIANGLE_TILE
+SHORT_ROW = gsamd.TRIANGLE_SHORT_ROW
+WAVE_ROW = gsamd.TRIANGLE_WAVE_ROW
+LDS_ROW = gsamd.TRIANGLE_LDS_ROW
 
 
 @pytest.fixture(params=range(gsamd.TRIANGLE_VARIANTS), ids=lambda v: "variant%d" % v)
@@ -55,15 +60,68 @@ def _truth(src, dst):
     return ids, t, int(t.sum()) // 3, int(A.nnz) // 2
 
 
+_TRUTHS = {}
+
+
+def _shared_truth(key, src, dst):
+    """_truth of a graph that several cases (the variants, the fold orders) share, computed once."""
+    if key not in _TRUTHS:
+        _TRUTHS[key] = _truth(src, dst)
+    return _TRUTHS[key]
+
+
+def _assignment(folds):
+    """Host model of the product's work assignment for the folds [(src, dst), ...] applied after
+    a reset: ([(short, wave, workgroup) per fold], steps, hot). A fold's new edges are its
+    canonical pairs that are no loop, no repeat and in no earlier fold; k_tri_rows reads the
+    rows of the adjacency the fold was merged into, so slen / llen of a new edge are the smaller
+    / larger degree of its endpoints AFTER the fold. steps is the sum of slen and hot the
+    greatest llen over every new edge so far."""
+    folds = [(np.asarray(s, np.int64), np.asarray(d, np.int64)) for s, d in folds]
+    ids = np.unique(np.concatenate([np.zeros(0, np.int64)] + [a for f in folds for a in f]))
+    n = max(len(ids), 1)
+    deg = np.zeros(n, np.int64)
+    seen = np.zeros(0, np.int64)
+    per_fold, steps, hot = [], 0, 0
+    for s, d in folds:
+        a, b = np.searchsorted(ids, s), np.searchsorted(ids, d)
+        keep = a != b
+        new = np.setdiff1d(np.minimum(a, b)[keep] * n + np.maximum(a, b)[keep], seen)  # sorted, unique
+        seen = np.concatenate([seen, new])
+        lo, hi = new // n, new % n
+        deg += np.bincount(lo, minlength=n) + np.bincount(hi, minlength=n)
+        slen, llen = np.minimum(deg[lo], deg[hi]), np.maximum(deg[lo], deg[hi])
+        workgroup = int(np.sum((slen > WAVE_ROW) & (llen >= LDS_ROW)))
+        wave = int(np.sum(slen > SHORT_ROW)) - workgroup
+        per_fold.append((len(new) - wave - workgroup, wave, workgroup))
+        steps += int(slen.sum())
+        hot = max(hot, int(llen.max()) if len(new) else 0)
+    return per_fold, steps, hot
+
+
+def _check_assignment(T, folds, variant):
+    """After the last of the folds: the library's step count and longest row equal the model's
+    under every variant, and the lengths of the product's wave and workgroup lists equal the
+    model's for the last fold that had new edges (variant 1 keeps no lists)."""
+    per_fold, steps, hot = _assignment(folds)
+    st = T.stats()
+    assert (st["steps"], st["hot_row"]) == (steps, hot)
+    last = [f for f in per_fold if sum(f)]
+    want = last[-1][1:] if last and variant == 0 else (0, 0)
+    assert T.bins() == want
+    return per_fold
+
+
 def _dev(T, a):
     import torch
     return torch.from_numpy(np.ascontiguousarray(a)).to(torch.device("cuda", T.device))
 
 
-def _check(T, src, dst, absent=()):
-    """Every answer of the handle equals the truth of the edges (src, dst)."""
+def _check(T, src, dst, absent=(), truth=None):
+    """Every answer of the handle equals the truth of the edges (src, dst); truth: _truth(src,
+    dst) where the caller holds it already."""
     import torch
-    ids, t, total, edges = _truth(src, dst)
+    ids, t, total, edges = truth if truth is not None else _truth(src, dst)
     assert T.count() == (total, edges, len(ids))
     v, c = T.local_counts()
     assert np.array_equal(v, ids) and np.array_equal(c, t)
@@ -436,3 +494,239 @@ def test_reset_and_windows(gs, variant):
         for i in range(0, 3000, 600):
             assert T.window(s[i:i + 600], d[i:i + 600]) == _truth(s[i:i + 600], d[i:i + 600])[2]
             _check(T, s[i:i + 600], d[i:i + 600])
+
+
+# ------------------------------------------------------------------ 11. every bin of the count step
+# The product's count step gives a new edge to a lane group (shorter row <= SHORT_ROW), to a
+# workgroup that samples the longer row in LDS (shorter row > WAVE_ROW and longer row >=
+# LDS_ROW) or to a wave (the rest). Every case below states in literal numbers, on the host
+# model and before it touches the GPU, which bins it fills: after a retune of a threshold
+# the case fails instead of testing another kernel than it names.
+_NB0 = 1000  # the smallest neighbour of the hub of _hub_and_clique
+WAYS = ("one_fold", "hub_first", "hub_last")
+
+
+def _hub_and_clique(c, D, where):
+    """A hub with the D neighbours _NB0, _NB0 + 2, ...; c of them, the mids, form a clique and
+    the others are leaves, so that an edge (hub, mid) has a shorter row of c and a longer row of
+    D entries. The mids are every 61st neighbour and the last one: they fall into many sample
+    segments of the hub's row, the first and the last among them. where: the hub's id below
+    every other id (its triangles are counted at the mid-mid edges), above every other id
+    (counted at the hub's edges) or inside the mids' range (either, per triangle).
+    Returns (hub, mids, the hub's edges, the clique's edges)."""
+    nb = _NB0 + 2 * np.arange(D, dtype=np.int64)
+    pos = np.concatenate([61 * np.arange(c - 1), [D - 1]])
+    assert np.all(np.diff(pos) > 0)
+    mids = nb[pos]
+    hub = {"below": 5, "above": _NB0 + 2 * D + 5000, "middle": int(mids[c // 2]) + 1}[where]
+    hs, hd = np.full(D, hub, np.int64), nb.copy()
+    hs[1::2], hd[1::2] = hd[1::2].copy(), hs[1::2].copy()  # both directions occur
+    return hub, mids, (hs, hd), _clique(mids.tolist())
+
+
+def _in_ways(hub_edges, other_edges):
+    both = tuple(np.concatenate([a, b]) for a, b in zip(hub_edges, other_edges))
+    return {"one_fold": [both], "hub_first": [hub_edges, other_edges], "hub_last": [other_edges, hub_edges]}
+
+
+def _fold_and_check(gs, variant, folds, truth):
+    s = np.concatenate([f[0] for f in folds])
+    d = np.concatenate([f[1] for f in folds])
+    with gs.Triangles(edge_hint=64) as T:
+        for k, (fs, fd) in enumerate(folds):
+            T.fold(fs, fd)
+            _check_assignment(T, folds[:k + 1], variant)
+        _check(T, s, d, truth=truth)
+
+
+@pytest.mark.parametrize("way", WAYS)
+@pytest.mark.parametrize("where", ["below", "above", "middle"])
+@pytest.mark.parametrize("D", [4095, 4096, 4097, 4101, 5120, 5121])
+@pytest.mark.parametrize("c", [64, 65])
+def test_hub_and_clique_at_the_thresholds(gs, variant, c, D, where, way):
+    """Both thresholds of the workgroup bin bracketed: a shorter row of 64 | 65 against a longer
+    row of 4095 | 4096 | 4097 entries; further 4096 and 5120 (exactly 1024 samples), 4097 and
+    5121 (the sample step goes from 4 to 5 and from 5 to 6, a last segment of 2 and of 3
+    entries) and 4101 (a last segment of one entry). In one fold all three edges of a triangle
+    are new; with the hub's edges in a fold of their own, first or last, the rows of the walk
+    mix entries of the fold with older ones."""
+    hub, mids, hub_edges, clique_edges = _hub_and_clique(c, D, where)
+    folds = _in_ways(hub_edges, clique_edges)[way]
+    per_fold, steps, hot = _assignment(folds)
+    pairs = math.comb(c, 2)
+    sampled = c == 65 and D >= 4096  # the c edges (hub, mid) take a workgroup each
+    of_hub = (D - c, 0, c) if sampled else (D - c, c, 0)
+    assert per_fold == {"one_fold": [(D - c, pairs + of_hub[1], of_hub[2])],
+                        "hub_first": [(D, 0, 0), (0, pairs, 0)],
+                        "hub_last": [(0, pairs, 0), of_hub]}[way]
+    assert hot == D
+    assert steps == {"one_fold": pairs * c + c * c + D - c, "hub_first": D + pairs * c,
+                     "hub_last": pairs * (c - 1) + c * c + D - c}[way]
+    if sampled:
+        assert gs.TRIANGLE_SAMPLES == 1024  # the sample arithmetic these lengths were chosen for
+        step = -(-D // 1024)
+        nsamp = -(-D // step)
+        assert (step, nsamp, D - (nsamp - 1) * step) == {4096: (4, 1024, 4), 4097: (5, 820, 2), 4101: (5, 821, 1),
+                                                         5120: (5, 1024, 5), 5121: (6, 854, 3)}[D]
+    s = np.concatenate([hub_edges[0], clique_edges[0]])
+    d = np.concatenate([hub_edges[1], clique_edges[1]])
+    truth = _shared_truth(("hub and clique", c, D, where), s, d)
+    ids, t, total, edges = truth
+    assert total == pairs + math.comb(c, 3) and edges == D + pairs and len(ids) == D + 1
+    assert t[ids == hub].tolist() == [pairs] and np.all(t[np.isin(ids, mids)] == c - 1 + math.comb(c - 1, 2))
+    assert int(t.sum()) == pairs + c * (c - 1 + math.comb(c - 1, 2))  # the leaves have none
+    _fold_and_check(gs, variant, folds, truth)
+
+
+@pytest.mark.parametrize("way", ["one_fold", "hub_last"])
+@pytest.mark.parametrize("where", ["below", "above", "middle"])
+def test_neighbours_the_sampled_search_rejects(gs, variant, where, way):
+    """The hub and clique with 65 mids and 4097 neighbours (sample step 5, a last segment of two
+    entries), where four mids (the first and the last neighbour of the hub among them) have
+    three more neighbours each that the hub has not: one below the hub's first neighbour (no
+    sample is <= it), one above its last, one strictly between two consecutive neighbours of
+    the same sample segment. They are vertices without a triangle, and no count changes."""
+    c, D, step = 65, 4097, 5
+    hub, mids, hub_edges, clique_edges = _hub_and_clique(c, D, where)
+    owners = mids[[0, 21, 42, 64]]
+    inside = np.array([7, 2001, 3001, 4095])  # neighbours p and p + 1 lie in one segment
+    assert -(-D // 1024) == step and np.all(inside % step != step - 1) and inside.max() + 1 == D - 1
+    extras = np.concatenate([100 + np.arange(4), _NB0 + 2 * D + 100 + np.arange(4), _NB0 + 2 * inside + 1])
+    assert hub not in extras and len(np.unique(extras)) == 12
+    other = (np.concatenate([clique_edges[0], extras]), np.concatenate([clique_edges[1], np.tile(owners, 3)]))
+    folds = _in_ways(hub_edges, other)[way]
+    per_fold, steps, hot = _assignment(folds)
+    pairs = math.comb(c, 2)
+    assert per_fold == {"one_fold": [(D - c + 12, pairs, c)], "hub_last": [(12, pairs, 0), (D - c, 0, c)]}[way]
+    assert hot == D
+    s = np.concatenate([hub_edges[0], other[0]])
+    d = np.concatenate([hub_edges[1], other[1]])
+    truth = _shared_truth(("rejected neighbours", where), s, d)
+    ids, t, total, edges = truth
+    assert total == pairs + math.comb(c, 3) and edges == D + pairs + 12 and len(ids) == D + 13
+    assert np.all(t[np.isin(ids, extras)] == 0) and t[ids == hub].tolist() == [pairs]
+    _fold_and_check(gs, variant, folds, truth)
+
+
+def test_more_workgroup_edges_than_workgroups(gs, variant):
+    """One fold with 1176 edges in the workgroup list, which 1024 workgroups serve: some take a
+    second edge. 16 hubs in a clique, 66 mids in a clique and 4030 leaves, every mid and every
+    leaf adjacent to every hub; the hubs have the greatest ids, so their edges count."""
+    leaves = 1000 + 2 * np.arange(4030, dtype=np.int64)
+    mids = 1001 + 2 * 61 * np.arange(66, dtype=np.int64)  # among the leaves
+    hubs = 100000 + np.arange(16, dtype=np.int64)
+    assert mids.max() < leaves.max()
+    parts = [_clique(hubs.tolist()), _clique(mids.tolist()), (np.repeat(hubs, 66), np.tile(mids, 16)),
+             (np.tile(leaves, 16), np.repeat(hubs, 4030))]
+    s = np.concatenate([p[0] for p in parts])
+    d = np.concatenate([p[1] for p in parts])
+    order = np.random.default_rng(12).permutation(len(s))
+    s, d = s[order], d[order]
+    assert len(s) == 67801
+    per_fold, steps, hot = _assignment([(s, d)])
+    assert per_fold == [(16 * 4030, math.comb(66, 2), math.comb(16, 2) + 16 * 66)]
+    assert per_fold[0][2] == 1176 > 1024 and hot == 15 + 66 + 4030
+    assert steps == 16 * 4030 * 16 + (math.comb(66, 2) + 16 * 66) * 81 + math.comb(16, 2) * 4111
+    truth = _shared_truth("sixteen hubs", s, d)
+    assert truth[2] == math.comb(16, 3) + math.comb(66, 3) + math.comb(16, 2) * 4096 + 16 * math.comb(66, 2) == 572160
+    _fold_and_check(gs, variant, [(s, d)], truth)
+
+
+def test_more_wave_edges_than_the_wave_grid_takes_at_once(gs, variant):
+    """One fold with more than 16384 edges in the wave list (4096 workgroups of 4 edges: a second
+    iteration), every shorter row above 64 entries and no row near 4096: G(640, 0.15)."""
+    iu = np.triu_indices(640, 1)
+    m = np.random.default_rng(3).random(len(iu[0])) < 0.15
+    s, d = iu[0][m].astype(np.int64), iu[1][m].astype(np.int64)
+    per_fold, steps, hot = _assignment([(s, d)])
+    short, wave, workgroup = per_fold[0]
+    assert wave > 16384 and workgroup == 0 and short == 0 and wave == len(s)
+    assert 64 < np.bincount(np.concatenate([s, d])).min() and hot < 4096
+    _fold_and_check(gs, variant, [(s, d)], _shared_truth("G(640, 0.15)", s, d))
+
+
+@pytest.mark.parametrize("repeat", ["thrice", "one_to_three"])
+@pytest.mark.parametrize("n", [TILE - 1, TILE, TILE + 1, 2 * TILE - 1, 2 * TILE, 2 * TILE + 1, 3 * TILE + 5])
+def test_repeats_and_loops_at_every_thread_and_tile_edge(gs, variant, n, repeat):
+    """The stream of test_path_closed_at_its_end with every edge three times, or edge i
+    1 + i % 3 times, and a self-loop after every seventh element: in the sorted fold the runs
+    of equal pairs start at every position of a thread's four elements and lie across the
+    edges of the tiles. Folded twice: the second fold has no new edge."""
+    s = np.concatenate([np.arange(0, n - 1), [n - 1]]).astype(np.int64)
+    d = np.concatenate([np.arange(1, n), [n - 3]]).astype(np.int64)
+    reps = np.full(n, 3) if repeat == "thrice" else 1 + np.arange(n) % 3
+    s, d = np.repeat(s, reps), np.repeat(d, reps)
+    at = np.arange(7, len(s) + 1, 7)
+    loops = s[at - 1]
+    s, d = np.insert(s, at, loops), np.insert(d, at, loops)
+    assert len(s) == int(reps.sum()) + len(at) and np.sum(s == d) == len(at) > 100
+    # the sorted fold as k_tri_flag_new reads it: where the runs of equal pairs start and what they straddle
+    lo, hi = np.minimum(s, d), np.maximum(s, d)
+    o = np.lexsort((hi, lo))
+    lo, hi = lo[o], hi[o]
+    same = (lo[1:] == lo[:-1]) & (hi[1:] == hi[:-1])  # same[i]: elements i and i + 1 are equal
+    starts = np.flatnonzero(same & ~np.concatenate([[False], same[:-1]]))
+    assert set((starts % 4).tolist()) == {0, 1, 2, 3}
+    assert np.any(same[3::4])  # a run goes on from one thread's last element to the next thread's first
+    assert np.any(same[TILE - 1::TILE])  # and from one tile's last element to the next tile's first
+    per_fold, steps, hot = _assignment([(s, d), (s, d)])
+    assert per_fold == [(n, 0, 0), (0, 0, 0)] and hot == 3
+    truth = _shared_truth(("closed path", n), s, d)
+    assert truth[2:] == (1, n) and len(truth[0]) == n
+    with gs.Triangles(edge_hint=8) as T:
+        T.fold(s, d)
+        assert T.count() == (1, n, n)
+        _check(T, s, d, truth=truth)
+        _check_assignment(T, [(s, d)], variant)
+        T.fold(s, d)
+        assert T.count() == (1, n, n) and T.bins() == (0, 0)
+        _check(T, s, d, truth=truth)
+        _check_assignment(T, [(s, d), (s, d)], variant)
+
+
+_STREAM = []
+
+
+def _hub_and_core_stream():
+    """47 K elements over 5000 vertices, shuffled, ids scrambled to 64 bits: 30000 uniform pairs
+    (loops and repeats among them), a core of 100 vertices with p = 0.8, three core vertices
+    joined to 4500 vertices each."""
+    if not _STREAM:
+        rng = np.random.default_rng(0x7A1B)
+        nv = 5000
+        core = rng.choice(nv, 100, replace=False)
+        iu = np.triu_indices(100, 1)
+        m = rng.random(len(iu[0])) < 0.8
+        s = [rng.integers(0, nv, 30000), core[iu[0][m]]]
+        d = [rng.integers(0, nv, 30000), core[iu[1][m]]]
+        for h in core[:3]:
+            s.append(np.full(4500, h))
+            d.append(rng.choice(nv, 4500, replace=False))
+        s, d = np.concatenate(s), np.concatenate(d)
+        order = rng.permutation(len(s))
+        mult = np.uint64(0x9E3779B97F4A7C15)
+        for a in (s, d):
+            a = (a[order].astype(np.uint64) * mult).view(np.int64)
+            a.setflags(write=False)
+            _STREAM.append(a)
+    return _STREAM
+
+
+@pytest.mark.parametrize("order", ["forward", "reverse"])
+def test_hub_and_core_stream_in_three_folds(gs, variant, order):
+    """A random stream whose last fold fills all three bins, checked after every fold, with
+    its three parts in either order."""
+    s, d = _hub_and_core_stream()
+    k = len(s) // 3
+    parts = [(s[:k], d[:k]), (s[k:2 * k], d[k:2 * k]), (s[2 * k:], d[2 * k:])]
+    if order == "reverse":
+        parts = parts[::-1]
+    per_fold, steps, hot = _assignment(parts)
+    assert min(per_fold[-1]) > 0 and hot >= 4096
+    with gs.Triangles(edge_hint=64) as T:
+        for i in range(3):
+            T.fold(*parts[i])
+            cs = np.concatenate([p[0] for p in parts[:i + 1]])
+            cd = np.concatenate([p[1] for p in parts[:i + 1]])
+            _check(T, cs, cd, truth=_shared_truth(("hub and core", order, i), cs, cd))
+            _check_assignment(T, parts[:i + 1], variant)

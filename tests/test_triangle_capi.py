@@ -25,6 +25,13 @@ def test_names_are_declared_exported_and_bound(gs):
         assert re.search(r"\bint %s\(gs_triangles\*? \w+[,)]" % n, text), n
         assert getattr(L, n).argtypes, n
     assert "gs_testing_triangle_stats" in gs.EXPORTED_SYMBOLS
+    with open(os.path.join(ROOT, "include", "gs_testing.h")) as f:
+        testing = f.read()
+    for n in ("gs_testing_triangle_stats", "gs_testing_triangle_bins"):
+        assert n in gs.EXPORTED_SYMBOLS
+        assert hasattr(ctypes.CDLL(gs.LIB_PATH), n)
+        assert re.search(r"\bint %s\(void\* t, uint64_t\* out\);" % n, testing), n
+        assert getattr(L, n).argtypes, n
 
 
 def test_null_handles_and_pointers_are_rejected(gs):
@@ -46,6 +53,7 @@ def test_null_handles_and_pointers_are_rejected(gs):
         lambda: L.gs_triangle_get_stream(None, ctypes.byref(p)),
         lambda: L.gs_triangle_wait_stream(None, None),
         lambda: L.gs_testing_triangle_stats(None, ctypes.byref(w)),
+        lambda: L.gs_testing_triangle_bins(None, ctypes.byref(w)),
     )
     for c in calls:
         assert c() == gs.GS_ERR_INVALID
@@ -55,7 +63,7 @@ def test_null_handles_and_pointers_are_rejected(gs):
 
 def test_python_class_has_the_methods(gs):
     for m in ("close", "reset", "sync", "wait_stream", "fold", "fold_device", "count", "count_device", "find_device",
-              "local_counts", "local_counts_device", "window", "__enter__", "__exit__"):
+              "local_counts", "local_counts_device", "window", "stats", "bins", "__enter__", "__exit__"):
         assert callable(getattr(gs.Triangles, m)), m
     assert isinstance(gs.Triangles.stream, property)
 
@@ -73,6 +81,14 @@ def test_triangle_constants_match_the_kernels(gs):
     assert re.search(r"kTriPer = TRIANGLE_TILE / kTriBS;", text) and tile % bs == 0
     assert gs.TRIANGLE_LANES == lanes and gs.TRIANGLE_TILE == tile and gs.TRIANGLE_VARIANTS == variants
     assert re.search(r"kTriangleProduct = kTriangleBinned\b", text) and re.search(r"kTriangleBinned = 0,", text)
+    # the bins of the product's count step, whose thresholds test_gpu_triangles.py brackets
+    assert re.search(r"constexpr uint32_t kTriShortRow = 4 \* TRIANGLE_LANES;", text)
+    wave = int(re.search(r"constexpr uint32_t kTriWaveRow = (\d+);", text).group(1))
+    lds = int(re.search(r"constexpr uint32_t kTriLdsRow = (\d+);", text).group(1))
+    samples = int(re.search(r"constexpr uint32_t kTriSamples = (\d+);", text).group(1))
+    assert gs.TRIANGLE_SHORT_ROW == 4 * lanes and gs.TRIANGLE_WAVE_ROW == wave
+    assert gs.TRIANGLE_LDS_ROW == lds and gs.TRIANGLE_SAMPLES == samples
+    assert gs.TRIANGLE_SHORT_ROW < gs.TRIANGLE_WAVE_ROW < gs.TRIANGLE_SAMPLES <= gs.TRIANGLE_LDS_ROW
 
 
 def test_triangle_variant_knob_roundtrip(gs):
