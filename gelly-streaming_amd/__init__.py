@@ -74,6 +74,9 @@ EXPORTED_SYMBOLS = (
     "gs_triangle_count", "gs_triangle_count_device", "gs_triangle_find_device", "gs_triangle_export_device",
     "gs_triangle_export", "gs_triangle_sync", "gs_triangle_get_stream", "gs_triangle_wait_stream",
     "gs_testing_triangle_stats", "gs_testing_triangle_bins",
+    "gs_slice_create", "gs_slice_destroy", "gs_slice_window", "gs_slice_window_device", "gs_slice_size",
+    "gs_slice_reduce_device", "gs_slice_reduce", "gs_slice_neighborhoods_device", "gs_slice_neighborhoods",
+    "gs_slice_sync", "gs_slice_get_stream", "gs_slice_wait_stream", "gs_testing_slice_stats",
 )
 
 # Pairs per workgroup of the component export's radix-sort kernels (csrc/gs_sort.hpp kSortTile):
@@ -99,6 +102,13 @@ TRIANGLE_SHORT_ROW = 32
 TRIANGLE_WAVE_ROW = 64
 TRIANGLE_LDS_ROW = 4096
 TRIANGLE_SAMPLES = 1024
+
+# Sorted positions per workgroup of the window slices' heads and reduce kernels
+# (csrc/gs_slice.hpp SLICE_TILE; a thread owns SLICE_TILE / 256 consecutive ones): a segment that
+# crosses a multiple of it is joined through carry records.
+SLICE_TILE = 2048
+SLICE_DIRECTIONS = {"out": 0, "in": 1, "all": 2}  # gs_slice_dir
+SLICE_OPS = {"sum": 0, "min": 1, "max": 2, "count": 3}  # gs_slice_op
 
 FAIL_BIT = 1 << 62  # count words: a failed signed verdict (GS_FAIL_BIT)
 DIGEST_FAILED = (1 << 64) - 1  # gs_digest of a signed summary whose verdict failed (GS_DIGEST_FAILED)
@@ -242,6 +252,20 @@ def lib():
     L.gs_triangle_wait_stream.argtypes = [_vp, _vp]
     L.gs_testing_triangle_stats.argtypes = [_vp, ctypes.POINTER(_u64)]
     L.gs_testing_triangle_bins.argtypes = [_vp, ctypes.POINTER(_u64)]
+    L.gs_slice_create.argtypes = [ctypes.POINTER(_vp), ctypes.c_int, _u64]
+    L.gs_slice_destroy.argtypes = [_vp]
+    L.gs_slice_window.argtypes = [_vp, _vp, _vp, _vp, _sz, ctypes.c_int]
+    L.gs_slice_window_device.argtypes = [_vp, _vp, _vp, _vp, _sz, _sz, ctypes.c_int]
+    L.gs_slice_size.argtypes = [_vp, ctypes.POINTER(_u64), ctypes.POINTER(_u64)]
+    L.gs_slice_reduce_device.argtypes = [_vp, ctypes.c_int, _vp, _vp, _sz, ctypes.POINTER(_sz)]
+    L.gs_slice_reduce.argtypes = [_vp, ctypes.c_int, _vp, _vp, _sz, ctypes.POINTER(_sz)]
+    L.gs_slice_neighborhoods_device.argtypes = [_vp, _vp, _vp, _vp, _vp, _sz, _sz, ctypes.POINTER(_sz),
+                                                ctypes.POINTER(_sz)]
+    L.gs_slice_neighborhoods.argtypes = [_vp, _vp, _vp, _vp, _vp, _sz, _sz, ctypes.POINTER(_sz), ctypes.POINTER(_sz)]
+    L.gs_slice_sync.argtypes = [_vp]
+    L.gs_slice_get_stream.argtypes = [_vp, ctypes.POINTER(_vp)]
+    L.gs_slice_wait_stream.argtypes = [_vp, _vp]
+    L.gs_testing_slice_stats.argtypes = [_vp, ctypes.POINTER(_u64)]
     L.gs_testing_set.argtypes = [ctypes.c_int, _i64]
     L.gs_testing_get.argtypes = [ctypes.c_int]
     L.gs_testing_get.restype = _i64
@@ -288,7 +312,8 @@ def digest_rows(v, label, parity=None):
 # ---------------------------------------------------------------- test controls
 # include/gs_testing.h: private knobs the tests use (the product reads no environment)
 TESTING_KNOBS = {"server_idle_us": 0, "changes_walk_max": 1, "parse_lb_timeout_us": 2, "group_self_apply": 3,
-                 "group_data_lag": 4, "degree_variant": 5, "triangle_variant": 6, "triangle_profile": 7}
+                 "group_data_lag": 4, "degree_variant": 5, "triangle_variant": 6, "triangle_profile": 7,
+                 "slice_profile": 8}
 
 
 def testing_set(knob, value):
@@ -1031,6 +1056,150 @@ class Triangles:
         out = (_u64 * 2)()
         _check(lib().gs_testing_triangle_bins(self._h, out))
         return out[0], out[1]
+
+
+# ---------------------------------------------------------------- window slices
+class Slice:
+    """The per-vertex neighbourhoods of one window of (src, dst, value) edges (the gs_slice_*
+    section of include/gs_summary.h: SimpleEdgeStream.slice and its SnapshotStream): `window`
+    replaces the handle's window, `reduce` gives one value per vertex (reduceOnEdges),
+    `neighborhoods` the CSR that foldNeighbors / applyOnNeighbors iterate, entries in arrival
+    order. Nothing is deduplicated. Owns a gs_slices handle."""
+
+    def __init__(self, device=0, edge_hint=0):
+        self.device = device
+        h = _vp()
+        _check(lib().gs_slice_create(ctypes.byref(h), device, int(edge_hint)))
+        self._h = h
+        self._has_val = True  # the current window carries values (an empty one reads none)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().gs_slice_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def stream(self):
+        s = _vp()
+        _check(lib().gs_slice_get_stream(self._h, ctypes.byref(s)))
+        return s.value
+
+    def sync(self):
+        _check(lib().gs_slice_sync(self._h))
+
+    def wait_stream(self, stream="torch"):
+        if isinstance(stream, str):
+            import torch
+            stream = torch.cuda.current_stream(self.device)
+        raw = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
+        _check(lib().gs_slice_wait_stream(self._h, raw))
+
+    def window(self, src, dst, val=None, direction="out"):
+        """One window of host edges (int64 arrays; val None: a stream without values)."""
+        s = np.ascontiguousarray(np.asarray(src, dtype=np.int64))
+        d = np.ascontiguousarray(np.asarray(dst, dtype=np.int64))
+        assert s.shape == d.shape
+        w = None
+        if val is not None:
+            w = np.ascontiguousarray(np.asarray(val, dtype=np.int64))
+            assert w.shape == s.shape
+        _check(lib().gs_slice_window(self._h, s.ctypes.data, d.ctypes.data, None if w is None else w.ctypes.data,
+                                     len(s), _slice_dir(direction)))
+        self._has_val = w is not None or len(s) == 0
+
+    def window_device(self, src, dst, val=None, direction="out", n=None, stride=1, after=None):
+        """One window of device-resident edges (torch tensors on this device or raw pointers),
+        element i at index i * stride; `after`: a stream the edges were written on. The call
+        synchronises with the host once (the vertex count)."""
+        if n is None:
+            n = src.numel() // (stride if stride > 1 else 1)
+        if after is not None:
+            self.wait_stream(after)
+        _check(lib().gs_slice_window_device(self._h, _ptr(src), _ptr(dst), _ptr(val), int(n), int(stride),
+                                            _slice_dir(direction)))
+        self._has_val = val is not None or int(n) == 0
+
+    def size(self):
+        """(vertices, entries) of the current window."""
+        v, e = _u64(), _u64()
+        _check(lib().gs_slice_size(self._h, ctypes.byref(v), ctypes.byref(e)))
+        return v.value, e.value
+
+    def reduce(self, op="sum"):
+        """(vertex, value) numpy int64 arrays, ascending by vertex; op: sum (wraps), min, max, count."""
+        n = max(self.size()[0], 1)
+        got = _sz()
+        v = np.empty(n, np.int64)
+        out = np.empty(n, np.int64)
+        _check(lib().gs_slice_reduce(self._h, _slice_op(op), v.ctypes.data, out.ctypes.data, n, ctypes.byref(got)))
+        return v[: got.value].copy(), out[: got.value].copy()
+
+    def reduce_device(self, op, v, out):
+        """The same rows into DEVICE arrays (capacity v.numel()), queued on self.stream; returns
+        the row count."""
+        got = _sz()
+        cap = v.numel() if hasattr(v, "numel") else len(v)
+        _check(lib().gs_slice_reduce_device(self._h, _slice_op(op), _ptr(v), _ptr(out), cap, ctypes.byref(got)))
+        return got.value
+
+    def neighborhoods(self):
+        """(vertex[nv], offset[nv + 1], neighbor[ne], val[ne]) numpy arrays: vertices ascending,
+        the entries of vertex k at offset[k] .. offset[k + 1] - 1 in arrival order; val is None
+        for a window without values."""
+        nv, ne = self.size()
+        got_v, got_e = _sz(), _sz()
+        v = np.empty(max(nv, 1), np.int64)
+        off = np.zeros(max(nv, 1) + 1, np.uint64)
+        nb = np.empty(max(ne, 1), np.int64)
+        w = np.empty(max(ne, 1), np.int64) if self._has_val else None
+        _check(lib().gs_slice_neighborhoods(self._h, v.ctypes.data, off.ctypes.data, nb.ctypes.data,
+                                            None if w is None else w.ctypes.data, len(v), len(nb),
+                                            ctypes.byref(got_v), ctypes.byref(got_e)))
+        nv, ne = got_v.value, got_e.value
+        return v[:nv].copy(), off[: nv + 1].copy(), nb[:ne].copy(), None if w is None else w[:ne].copy()
+
+    def neighborhoods_device(self, v, offset, neighbor, val=None):
+        """The CSR into DEVICE arrays (capacities v.numel() and neighbor.numel(); offset holds
+        v.numel() + 1 words), queued on self.stream; returns (vertices, entries)."""
+        got_v, got_e = _sz(), _sz()
+        cap_v = v.numel() if hasattr(v, "numel") else len(v)
+        cap_e = neighbor.numel() if hasattr(neighbor, "numel") else len(neighbor)
+        _check(lib().gs_slice_neighborhoods_device(self._h, _ptr(v), _ptr(offset), _ptr(neighbor), _ptr(val), cap_v,
+                                                   cap_e, ctypes.byref(got_v), ctypes.byref(got_e)))
+        return got_v.value, got_e.value
+
+    def stats(self):
+        """gs_testing_slice_stats: tiles of the last reduce, tiles of the window without a head
+        (carry records that hand a run on), the longest segment, and the phase times
+        (microseconds) of the last calls under testing(slice_profile=1)."""
+        out = (_u64 * 8)()
+        _check(lib().gs_testing_slice_stats(self._h, out))
+        return {"tiles": out[0], "headless_tiles": out[1], "longest": out[2], "expand_us": out[3], "sort_us": out[4],
+                "heads_us": out[5], "reduce_us": out[6], "gather_us": out[7]}
+
+
+def _slice_dir(direction):
+    return SLICE_DIRECTIONS[direction] if isinstance(direction, str) else int(direction)
+
+
+def _slice_op(op):
+    return SLICE_OPS[op] if isinstance(op, str) else int(op)
 
 
 # ---------------------------------------------------------------- native multi-GPU group

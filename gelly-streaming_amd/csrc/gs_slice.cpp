@@ -1,0 +1,425 @@
+// gs_slice.cpp -- the window slices behind include/gs_summary.h's gs_slice_* section: the
+// per-vertex neighbourhoods of one window of (src, dst, value) edges in arrival order, their
+// reduction (reduceOnEdges) and their CSR (foldNeighbors / applyOnNeighbors). State layout and
+// the kernels are described in gs_slice.hpp / gs_slice_k.hip and DESIGN.md section 6d.
+//
+// A window of n edges, E entries: expand the edges into entry keys; digit histograms; eight
+// stable radix passes of gs_sort_k.hip over (key, entry index) -- none is skipped, the
+// histograms stay on the device; head flags, their scan, vertices and offsets; ONE host
+// synchronisation to learn the vertex count. A reduce or an export afterwards queues its
+// launches and does not wait (the host-array forms wait for their copies).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <string>
+
+#include "gs_internal.hpp"
+#include "gs_slice.hpp"
+
+using namespace gsi;
+
+struct gs_slices_s {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  hipEvent_t ext_ev = nullptr;
+  DevBuf<unsigned long long> ctl;  // gs::SliceCtl words
+  // the window's edges, n_cap each (eval is written only by a window with values)
+  uint64_t n_cap = 0;
+  DevBuf<int64_t> esrc;
+  DevBuf<int64_t> edst;
+  DevBuf<int64_t> eval;
+  // per entry / per tile arrays, sized for e_cap entries
+  uint64_t e_cap = 0;
+  DevBuf<int64_t> kid;             // entry keys
+  DevBuf<int64_t> vtx;             // vertices, ascending
+  DevBuf<unsigned long long> off;  // [e_cap + 1]
+  DevBuf<uint8_t> flags;           // whole tiles
+  DevBuf<uint32_t> tbase;          // [tiles + 1]
+  DevBuf<int64_t> lead;            // [tiles] each: the carry records of the last reduce
+  DevBuf<int64_t> trail;
+  DevBuf<int64_t> carry;
+  SortScratch sort;
+  // the current window
+  uint64_t n = 0, entries = 0, nv = 0;
+  int dir = GS_SLICE_OUT;
+  bool has_val = true;
+  const unsigned long long* skey = nullptr;  // the sorted pairs (in the sort's scratch)
+  const uint32_t* spay = nullptr;
+  // device staging of the host-array forms
+  uint64_t o_cap = 0;
+  DevBuf<int64_t> o_a;
+  DevBuf<int64_t> o_b;
+  // diagnostics (gs_testing_slice_stats)
+  uint64_t reduce_tiles = 0;
+  uint64_t phase_us[5] = {0, 0, 0, 0, 0};  // expand, sort, heads, reduce, gather of the last profiled calls
+};
+
+namespace {
+
+// A sort payload is an entry index of 32 bits.
+constexpr uint64_t kSliceMaxEntries = 0xFFFFFFFFull;
+enum { PH_EXPAND = 0, PH_SORT = 1, PH_HEADS = 2, PH_REDUCE = 3, PH_GATHER = 4 };
+
+int check_slice(gs_slices s) {
+  if (!s) return fail(GS_ERR_INVALID, "null slice handle");
+  return GS_OK;
+}
+
+int ensure_window(gs_slices_s* s, uint64_t n, uint64_t entries) {
+  if (s->n_cap < n) {
+    GS_HIP(hipStreamSynchronize(s->stream));
+    s->n_cap = 0;
+    const uint64_t c = n + n / 4;
+    GS_HIP(s->esrc.alloc(c));
+    GS_HIP(s->edst.alloc(c));
+    GS_HIP(s->eval.alloc(c));
+    s->n_cap = c;
+  }
+  if (s->e_cap < entries) {
+    GS_HIP(hipStreamSynchronize(s->stream));
+    s->e_cap = 0;
+    const uint64_t c = std::min<uint64_t>(kSliceMaxEntries, entries + entries / 4);
+    const uint64_t tiles = gs::slice_tiles(c, gs::SLICE_TILE);
+    GS_HIP(s->kid.alloc(c));
+    GS_HIP(s->vtx.alloc(c));
+    GS_HIP(s->off.alloc(c + 1));
+    GS_HIP(s->flags.alloc(tiles * gs::SLICE_TILE));
+    GS_HIP(s->tbase.alloc(tiles + 1));
+    GS_HIP(s->lead.alloc(tiles));
+    GS_HIP(s->trail.alloc(tiles));
+    GS_HIP(s->carry.alloc(tiles));
+    s->e_cap = c;
+  }
+  return sort_scratch_ensure(s->sort, entries, s->stream);
+}
+
+int ensure_staging(gs_slices_s* s, uint64_t rows) {
+  if (s->o_cap >= rows) return GS_OK;
+  GS_HIP(hipStreamSynchronize(s->stream));
+  s->o_cap = 0;
+  const uint64_t c = rows + rows / 4;
+  GS_HIP(s->o_a.alloc(c));
+  GS_HIP(s->o_b.alloc(c));
+  s->o_cap = c;
+  return GS_OK;
+}
+
+// Brackets the phases of a call with events when GS_TESTING_SLICE_PROFILE is 1 (and waits for them).
+struct PhaseTimer {
+  gs_slices_s* s;
+  bool on;
+  hipEvent_t ev[4] = {};
+  int first = -1, marks = 0;
+  explicit PhaseTimer(gs_slices_s* h) : s(h), on(testing_value(GS_TESTING_SLICE_PROFILE, 0) == 1) {
+    for (int i = 0; on && i < 4; ++i)
+      if (hipEventCreate(&ev[i]) != hipSuccess) on = false;
+  }
+  // the work queued until the next mark (or finish) is phase `phase`; phases are consecutive
+  void mark(int phase) {
+    if (!on || marks >= 3) return;
+    if (first < 0) first = phase;
+    (void)hipEventRecord(ev[marks++], s->stream);
+  }
+  void finish() {
+    if (!on || marks == 0) return;
+    (void)hipEventRecord(ev[marks], s->stream);
+    (void)hipStreamSynchronize(s->stream);
+    for (int i = 0; i < marks; ++i) {
+      float ms = 0;
+      s->phase_us[first + i] = 0;
+      if (hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess) s->phase_us[first + i] = (uint64_t)(ms * 1000.0f);
+    }
+  }
+  ~PhaseTimer() {
+    for (int i = 0; i < 4; ++i)
+      if (ev[i]) (void)hipEventDestroy(ev[i]);
+  }
+};
+
+void set_empty(gs_slices_s* s, int dir) {
+  s->n = s->entries = s->nv = 0;
+  s->dir = dir;
+  s->has_val = true;  // (no value is ever read)
+  s->skey = nullptr;
+  s->spay = nullptr;
+}
+
+int window_guard(gs_slices s, const void* src, const void* dst, size_t n, int dir) {
+  if (int rc = check_slice(s)) return rc;
+  if (dir < 0 || dir >= gs::kSliceDirs) return fail(GS_ERR_INVALID, "unknown slice direction");
+  if (n && (!src || !dst)) return fail(GS_ERR_INVALID, "null edge arrays");
+  if ((uint64_t)n > kSliceMaxEntries || gs::slice_entries(n, dir) > kSliceMaxEntries)
+    return fail(GS_ERR_CAPACITY, "slice window: " + std::to_string(n) +
+                                     " edges pass 2^32 - 1 entries, the sort payload's range");
+  return GS_OK;
+}
+
+// n > 0 device edges on s->stream, arrays of ensure_window(n, entries)
+int window_impl(gs_slices_s* s, const int64_t* src, const int64_t* dst, const int64_t* val, uint64_t n,
+                uint64_t stride, int dir) {
+  const uint64_t entries = gs::slice_entries(n, dir);
+  set_empty(s, dir);  // (a failure below leaves an empty window)
+  PhaseTimer timer(s);
+  timer.mark(PH_EXPAND);
+  gs::launch_slice_expand(src, dst, val, n, stride, dir, s->esrc, s->edst, s->eval, s->kid, s->stream);
+  GS_HIP(hipGetLastError());
+  timer.mark(PH_SORT);
+  uint32_t* const sctl = s->sort.ctl;
+  GS_HIP(hipMemsetAsync(sctl, 0, gs::kSortCtlWords * 4, s->stream));
+  gs::launch_slice_digits(s->kid, entries, sctl, s->stream);  // rows 0..7: the keys
+  GS_HIP(hipGetLastError());
+  gs::SortSrc cur;  // (pay null: payload i of entry i is i)
+  int side = 0;
+  if (int rc = sort_run(s->sort, s->kid, entries, sctl, nullptr, &cur, &side, s->stream)) return rc;
+  if (!cur.key || !cur.pay) return fail(GS_ERR_HIP, "slice window: the sort ran no pass");
+  timer.mark(PH_HEADS);
+  gs::launch_slice_heads(cur.key, entries, s->flags, s->tbase, s->ctl, s->vtx, s->off, s->e_cap, s->stream);
+  GS_HIP(hipGetLastError());
+  // the window's one host synchronisation: the vertex count
+  unsigned long long nv = 0;
+  GS_HIP(hipMemcpyAsync(&nv, s->ctl + gs::SLICE_NV, 8, hipMemcpyDeviceToHost, s->stream));
+  GS_HIP(hipStreamSynchronize(s->stream));
+  timer.finish();
+  if (nv == 0 || nv > entries) return fail(GS_ERR_HIP, "slice window: vertex count out of range");
+  s->n = n;
+  s->entries = entries;
+  s->nv = nv;
+  s->has_val = val != nullptr;
+  s->skey = cur.key;
+  s->spay = cur.pay;
+  return GS_OK;
+}
+
+int reduce_impl(gs_slices_s* s, int op, int64_t* v, int64_t* out, size_t cap, size_t* n, bool to_host) {
+  *n = s->nv;
+  if (op != GS_SLICE_COUNT && !s->has_val)
+    return fail(GS_ERR_INVALID, "the window has no values: only the count op applies");
+  if (cap < s->nv)
+    return fail(GS_ERR_TRUNCATED, "output capacity " + std::to_string(cap) + " < " + std::to_string(s->nv));
+  if (s->nv == 0) return GS_OK;
+  if (!v || !out) return fail(GS_ERR_INVALID, "null arrays");
+  int64_t* dout = out;
+  if (to_host) {
+    if (int rc = ensure_staging(s, s->nv)) return rc;
+    dout = s->o_a;
+  }
+  PhaseTimer timer(s);
+  timer.mark(PH_REDUCE);
+  if (op == GS_SLICE_COUNT) {
+    gs::launch_slice_count(s->off, s->nv, dout, s->stream);
+  } else {
+    gs::launch_slice_reduce(op, s->flags, s->spay, s->eval, s->entries, s->n, s->dir, s->tbase, dout, s->nv, s->lead,
+                            s->trail, s->carry, s->stream);
+    s->reduce_tiles = gs::slice_tiles(s->entries, gs::SLICE_TILE);
+  }
+  GS_HIP(hipGetLastError());
+  timer.finish();
+  GS_HIP(hipMemcpyAsync(v, s->vtx, s->nv * 8, to_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, s->stream));
+  if (to_host) {
+    GS_HIP(hipMemcpyAsync(out, dout, s->nv * 8, hipMemcpyDeviceToHost, s->stream));
+    GS_HIP(hipStreamSynchronize(s->stream));
+  }
+  return GS_OK;
+}
+
+int neighborhoods_impl(gs_slices_s* s, int64_t* v, uint64_t* offset, int64_t* neighbor, int64_t* val, size_t cap_v,
+                       size_t cap_e, size_t* nv, size_t* ne, bool to_host) {
+  *nv = s->nv;
+  *ne = s->entries;
+  if (val && !s->has_val) return fail(GS_ERR_INVALID, "the window has no values: pass a null val array");
+  if (cap_v < s->nv || cap_e < s->entries)
+    return fail(GS_ERR_TRUNCATED, "output capacities " + std::to_string(cap_v) + ", " + std::to_string(cap_e) + " < " +
+                                      std::to_string(s->nv) + ", " + std::to_string(s->entries));
+  if (!offset) return fail(GS_ERR_INVALID, "null arrays");
+  if (s->nv == 0) {  // offset[0] = 0
+    if (to_host) offset[0] = 0;
+    else GS_HIP(hipMemsetAsync(offset, 0, 8, s->stream));
+    return GS_OK;
+  }
+  if (!v || !neighbor) return fail(GS_ERR_INVALID, "null arrays");
+  int64_t *dn = neighbor, *dv = val;
+  if (to_host) {
+    if (int rc = ensure_staging(s, s->entries)) return rc;
+    dn = s->o_a;
+    dv = val ? s->o_b.get() : nullptr;
+  }
+  PhaseTimer timer(s);
+  timer.mark(PH_GATHER);
+  gs::launch_slice_gather(s->spay, s->entries, s->n, s->dir, s->esrc, s->edst, s->eval, dn, dv, s->entries,
+                          s->stream);
+  GS_HIP(hipGetLastError());
+  timer.finish();
+  const hipMemcpyKind kind = to_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+  GS_HIP(hipMemcpyAsync(v, s->vtx, s->nv * 8, kind, s->stream));
+  GS_HIP(hipMemcpyAsync(offset, s->off, (s->nv + 1) * 8, kind, s->stream));
+  if (to_host) {
+    GS_HIP(hipMemcpyAsync(neighbor, dn, s->entries * 8, hipMemcpyDeviceToHost, s->stream));
+    if (val) GS_HIP(hipMemcpyAsync(val, dv, s->entries * 8, hipMemcpyDeviceToHost, s->stream));
+    GS_HIP(hipStreamSynchronize(s->stream));
+  }
+  return GS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gs_slice_destroy(gs_slices s) {
+  if (!s) return GS_OK;
+  DeviceGuard g(s->device);
+  if (s->stream) (void)hipStreamSynchronize(s->stream);
+  if (s->ext_ev) (void)hipEventDestroy(s->ext_ev);
+  const hipStream_t stream = s->stream;
+  delete s;  // frees every device buffer (DevBuf members): device current, the stream idle
+  if (stream) (void)hipStreamDestroy(stream);
+  return GS_OK;
+}
+
+int gs_slice_create(gs_slices* out, int device, uint64_t edge_hint) {
+  if (!out) return fail(GS_ERR_INVALID, "out is null");
+  *out = nullptr;
+  int count = 0;
+  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail(GS_ERR_HIP, "no HIP device available");
+  if (device < 0 || device >= count) return fail(GS_ERR_INVALID, "bad device");
+  if (edge_hint > kSliceMaxEntries) return fail(GS_ERR_CAPACITY, "edge hint beyond 2^32 - 1 entries");
+  DeviceGuard g(device);
+  gs_slices_s* s = new gs_slices_s();
+  s->device = device;
+  auto body = [&]() -> int {
+    GS_HIP(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+    GS_HIP(hipEventCreateWithFlags(&s->ext_ev, hipEventDisableTiming));
+    GS_HIP(s->ctl.alloc(gs::SLICE_CTL_WORDS));
+    GS_HIP(hipMemsetAsync(s->ctl, 0, gs::SLICE_CTL_WORDS * 8, s->stream));
+    if (edge_hint)
+      if (int r = ensure_window(s, edge_hint, edge_hint)) return r;
+    GS_HIP(hipStreamSynchronize(s->stream));
+    return GS_OK;
+  };
+  const int rc = body();
+  if (rc) {
+    const std::string msg = gs_last_error();
+    (void)gs_slice_destroy(s);
+    return fail(rc, msg);
+  }
+  *out = s;
+  return GS_OK;
+}
+
+int gs_slice_window_device(gs_slices s, const int64_t* src, const int64_t* dst, const int64_t* val, size_t n,
+                           size_t stride, int dir) {
+  if (int rc = window_guard(s, src, dst, n, dir)) return rc;
+  if (stride == 0 || stride > 0xFFFFFFFFull) return fail(GS_ERR_INVALID, "stride must be >= 1");
+  if (n == 0) {
+    set_empty(s, dir);
+    return GS_OK;
+  }
+  DeviceGuard g(s->device);
+  if (int rc = ensure_window(s, n, gs::slice_entries(n, dir))) return rc;
+  return window_impl(s, src, dst, val, n, stride, dir);
+}
+
+int gs_slice_window(gs_slices s, const int64_t* src, const int64_t* dst, const int64_t* val, size_t n, int dir) {
+  if (int rc = window_guard(s, src, dst, n, dir)) return rc;
+  if (n == 0) {
+    set_empty(s, dir);
+    return GS_OK;
+  }
+  DeviceGuard g(s->device);
+  if (int rc = ensure_window(s, n, gs::slice_entries(n, dir))) return rc;
+  GS_HIP(hipMemcpyAsync(s->esrc, src, n * 8, hipMemcpyHostToDevice, s->stream));
+  GS_HIP(hipMemcpyAsync(s->edst, dst, n * 8, hipMemcpyHostToDevice, s->stream));
+  if (val) GS_HIP(hipMemcpyAsync(s->eval, val, n * 8, hipMemcpyHostToDevice, s->stream));
+  // (the edges are in place; window_impl waits for the stream before it returns)
+  return window_impl(s, s->esrc, s->edst, val ? s->eval.get() : nullptr, n, 1, dir);
+}
+
+int gs_slice_size(gs_slices s, uint64_t* vertices, uint64_t* entries) {
+  if (int rc = check_slice(s)) return rc;
+  if (!vertices || !entries) return fail(GS_ERR_INVALID, "null count pointers");
+  *vertices = s->nv;
+  *entries = s->entries;
+  return GS_OK;
+}
+
+int gs_slice_reduce_device(gs_slices s, int op, int64_t* v, int64_t* out, size_t cap, size_t* n) {
+  if (int rc = check_slice(s)) return rc;
+  if (!n) return fail(GS_ERR_INVALID, "n is null");
+  if (op < 0 || op >= gs::kSliceOps) return fail(GS_ERR_INVALID, "unknown slice op");
+  DeviceGuard g(s->device);
+  return reduce_impl(s, op, v, out, cap, n, false);
+}
+
+int gs_slice_reduce(gs_slices s, int op, int64_t* v, int64_t* out, size_t cap, size_t* n) {
+  if (int rc = check_slice(s)) return rc;
+  if (!n) return fail(GS_ERR_INVALID, "n is null");
+  if (op < 0 || op >= gs::kSliceOps) return fail(GS_ERR_INVALID, "unknown slice op");
+  DeviceGuard g(s->device);
+  return reduce_impl(s, op, v, out, cap, n, true);
+}
+
+int gs_slice_neighborhoods_device(gs_slices s, int64_t* v, uint64_t* offset, int64_t* neighbor, int64_t* val,
+                                  size_t cap_v, size_t cap_e, size_t* nv, size_t* ne) {
+  if (int rc = check_slice(s)) return rc;
+  if (!nv || !ne) return fail(GS_ERR_INVALID, "null count pointers");
+  DeviceGuard g(s->device);
+  return neighborhoods_impl(s, v, offset, neighbor, val, cap_v, cap_e, nv, ne, false);
+}
+
+int gs_slice_neighborhoods(gs_slices s, int64_t* v, uint64_t* offset, int64_t* neighbor, int64_t* val, size_t cap_v,
+                           size_t cap_e, size_t* nv, size_t* ne) {
+  if (int rc = check_slice(s)) return rc;
+  if (!nv || !ne) return fail(GS_ERR_INVALID, "null count pointers");
+  DeviceGuard g(s->device);
+  return neighborhoods_impl(s, v, offset, neighbor, val, cap_v, cap_e, nv, ne, true);
+}
+
+int gs_slice_sync(gs_slices s) {
+  if (int rc = check_slice(s)) return rc;
+  DeviceGuard g(s->device);
+  GS_HIP(hipStreamSynchronize(s->stream));
+  return GS_OK;
+}
+
+int gs_slice_get_stream(gs_slices s, void** stream) {
+  if (int rc = check_slice(s)) return rc;
+  if (!stream) return fail(GS_ERR_INVALID, "stream is null");
+  *stream = s->stream;
+  return GS_OK;
+}
+
+int gs_slice_wait_stream(gs_slices s, void* stream) {
+  if (int rc = check_slice(s)) return rc;
+  DeviceGuard g(s->device);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (st == s->stream) return GS_OK;
+  GS_HIP(hipEventRecord(s->ext_ev, st));  // (stream 0 = the device's null stream)
+  GS_HIP(hipStreamWaitEvent(s->stream, s->ext_ev, 0));
+  return GS_OK;
+}
+
+// gs_testing.h: out[0] = tiles of the last reduce (0: none, or only the count op), out[1] = tiles
+// of the current window without a head (carry records that pass a run on), out[2] = its longest
+// segment, out[3..7] = microseconds of the last profiled expand / sort / heads / reduce / gather
+// phases. Synchronises.
+int gs_testing_slice_stats(void* handle, uint64_t* out) {
+  gs_slices s = static_cast<gs_slices>(handle);
+  if (int rc = check_slice(s)) return rc;
+  if (!out) return fail(GS_ERR_INVALID, "out is null");
+  DeviceGuard g(s->device);
+  unsigned long long w[2] = {0, 0};
+  if (s->nv) {
+    static_assert(gs::SLICE_NOHEAD == gs::SLICE_LONGEST + 1, "the two diagnostic words are adjacent");
+    GS_HIP(hipMemsetAsync(s->ctl + gs::SLICE_LONGEST, 0, 16, s->stream));
+    gs::launch_slice_stats(s->off, s->nv, s->tbase, gs::slice_tiles(s->entries, gs::SLICE_TILE), s->ctl, s->stream);
+    GS_HIP(hipGetLastError());
+    GS_HIP(hipMemcpyAsync(w, s->ctl + gs::SLICE_LONGEST, sizeof(w), hipMemcpyDeviceToHost, s->stream));
+  }
+  GS_HIP(hipStreamSynchronize(s->stream));
+  out[0] = s->reduce_tiles;
+  out[1] = w[1];
+  out[2] = w[0];
+  for (int i = 0; i < 5; ++i) out[3 + i] = s->phase_us[i];
+  return GS_OK;
+}
+
+}  // extern "C"

@@ -4,7 +4,7 @@
 // gs_export_components*. Every launch is queued on the given stream; kernel boundaries
 // carry all ordering between workgroups (no workgroup waits on another inside a launch).
 // The host part at the end (gs_sort.cpp) owns the sort's scratch and drives its passes for
-// every caller: the component export, the degree exports and the triangle fold.
+// every caller: the component export, the degree exports, the triangle fold and the window slices.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

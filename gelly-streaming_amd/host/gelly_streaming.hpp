@@ -11,6 +11,9 @@
 //   SummaryBulkAggregation      SummaryBulkAggregation.java:44-131 (run(): partition tag ->
 //                               keyed window fold -> all-window reduce -> Merger)
 //   SimpleEdgeStream::aggregate SimpleEdgeStream.java:100-102
+//   SimpleEdgeStream::slice     SimpleEdgeStream.java:135-167
+//   SnapshotStream              SnapshotStream.java:61-131 (reduceOnEdges / foldNeighbors /
+//                               applyOnNeighbors over a GPU-resident window slice)
 //   DisjointSet                 summaries/DisjointSet.java:25-151  (GPU-resident forest)
 //   Candidates                  summaries/Candidates.java:27-196   (GPU-resident signed forest)
 //   ConnectedComponents         library/ConnectedComponents.java:41-134
@@ -712,11 +715,162 @@ class SummaryBulkAggregation : public SummaryAggregation<K, EV, S, T> {
   int64_t timeMillis_;
 };
 
+// EdgeDirection (flink-gelly): which endpoint keys an edge in a slice
+enum class EdgeDirection { IN, OUT, ALL };
+
+// SnapshotStream (SnapshotStream.java:61-131): the per-vertex neighbourhoods of every window
+// of a sliced edge stream, read through a slice handle (gs_summary.h, the gs_slice_* section).
+// Windows are cut on the host: consecutive edges whose timestamps share ts / timeMillis (the
+// rule of SummaryBulkAggregation::window_bounds); no timestamps or timeMillis <= 0 is one
+// window. Every method returns its emissions window after window, vertices ascending inside a
+// window (the reference's order inside a window is unspecified). reduceOnEdges(gs_slice_op)
+// reduces on the device; the forms that take a function run it on the host over the window's
+// CSR, a vertex's entries in arrival order.
+template <typename K, typename EV>
+class SnapshotStream {
+  static_assert(std::is_same<K, int64_t>::value, "slices are built for 64-bit integer keys");
+  static_assert(std::is_same<EV, int64_t>::value || std::is_same<EV, NullValue>::value,
+                "slices are built for 64-bit integer edge values and NullValue");
+  static constexpr bool kHasValue = std::is_same<EV, int64_t>::value;
+  template <typename F>
+  struct NonDeduced {  // T of foldNeighbors comes from `initial` alone, so a lambda converts
+    using type = F;
+  };
+
+ public:
+  SnapshotStream(const EdgeStream<K, EV>* edges, int64_t timeMillis, EdgeDirection direction, int device)
+      : edges_(edges), timeMillis_(timeMillis), dir_(direction), device_(device) {}
+
+  // reduceOnEdges (:100-119) with one of the built-in functions, on the device. GS_SLICE_COUNT
+  // is the only one a NullValue stream admits.
+  std::vector<std::pair<K, int64_t>> reduceOnEdges(gs_slice_op op) const {
+    std::vector<std::pair<K, int64_t>> out;
+    each_window([&](gs_slices h) {
+      uint64_t nv = 0, ne = 0;
+      gs_check(gs_slice_size(h, &nv, &ne));
+      std::vector<int64_t> v(nv + 1), r(nv + 1);
+      size_t got = 0;
+      gs_check(gs_slice_reduce(h, (int)op, v.data(), r.data(), v.size(), &got));
+      for (size_t k = 0; k < got; ++k) out.emplace_back((K)v[k], r[k]);
+    });
+    return out;
+  }
+
+  // reduceOnEdges (:100-119) with a user function, applied in arrival order on the host
+  std::vector<std::pair<K, EV>> reduceOnEdges(const std::function<EV(EV, EV)>& reduce) const {
+    std::vector<std::pair<K, EV>> out;
+    each_neighborhood([&](K vertex, const std::vector<std::pair<K, EV>>& nb) {
+      EV acc = nb[0].second;
+      for (size_t i = 1; i < nb.size(); ++i) acc = reduce(acc, nb[i].second);
+      out.emplace_back(vertex, acc);
+    });
+    return out;
+  }
+
+  // foldNeighbors (:61-85): fold(accum, vertexID, neighborID, edgeValue) from `initial`
+  template <typename T>
+  std::vector<T> foldNeighbors(const T& initial,
+                               const typename NonDeduced<std::function<T(T, K, K, EV)>>::type& fold) const {
+    std::vector<T> out;
+    each_neighborhood([&](K vertex, const std::vector<std::pair<K, EV>>& nb) {
+      T acc = initial;
+      for (const auto& e : nb) acc = fold(std::move(acc), vertex, e.first, e.second);
+      out.push_back(std::move(acc));
+    });
+    return out;
+  }
+  template <typename T>
+  std::vector<T> foldNeighbors(const T& initial, EdgesFold<K, EV, T>& fold) const {
+    return foldNeighbors<T>(initial, [&fold](T a, K v, K n, EV e) { return fold.foldEdges(std::move(a), v, n, e); });
+  }
+
+  // applyOnNeighbors (:121-131): apply(vertexID, neighbors (id, value), collector)
+  template <typename T>
+  std::vector<T> applyOnNeighbors(
+      const std::function<void(K, const std::vector<std::pair<K, EV>>&, std::vector<T>&)>& apply) const {
+    std::vector<T> out;
+    each_neighborhood([&](K vertex, const std::vector<std::pair<K, EV>>& nb) { apply(vertex, nb, out); });
+    return out;
+  }
+
+ private:
+  struct SliceHandle {
+    gs_slices s = nullptr;
+    SliceHandle(int device, size_t edges) { gs_check(gs_slice_create(&s, device, edges)); }
+    ~SliceHandle() { gs_slice_destroy(s); }
+    SliceHandle(const SliceHandle&) = delete;
+    SliceHandle& operator=(const SliceHandle&) = delete;
+  };
+
+  // every window of the stream, in order, as the current window of one handle
+  void each_window(const std::function<void(gs_slices)>& fn) const {
+    const size_t n = edges_->edges.size();
+    if (n == 0) return;
+    const int dir = dir_ == EdgeDirection::OUT ? GS_SLICE_OUT : dir_ == EdgeDirection::IN ? GS_SLICE_IN : GS_SLICE_ALL;
+    const bool one = edges_->timestamps.empty() || timeMillis_ <= 0;
+    SliceHandle h(device_, 0);
+    std::vector<int64_t> src, dst, val;
+    size_t i = 0;
+    while (i < n) {
+      size_t j = n;
+      if (!one) {
+        const int64_t w = edges_->timestamps[i] / timeMillis_;
+        for (j = i + 1; j < n && edges_->timestamps[j] / timeMillis_ == w;) ++j;
+      }
+      src.resize(j - i);
+      dst.resize(j - i);
+      if (kHasValue) val.resize(j - i);
+      for (size_t k = i; k < j; ++k) {
+        src[k - i] = (int64_t)edges_->edges[k].getSource();
+        dst[k - i] = (int64_t)edges_->edges[k].getTarget();
+        if constexpr (kHasValue) val[k - i] = edges_->edges[k].getValue();
+      }
+      gs_check(gs_slice_window(h.s, src.data(), dst.data(), kHasValue ? val.data() : nullptr, j - i, dir));
+      fn(h.s);
+      i = j;
+    }
+  }
+
+  void each_neighborhood(const std::function<void(K, const std::vector<std::pair<K, EV>>&)>& fn) const {
+    each_window([&](gs_slices h) {
+      uint64_t nv = 0, ne = 0;
+      gs_check(gs_slice_size(h, &nv, &ne));
+      std::vector<int64_t> v(nv + 1), nbr(ne + 1), val(kHasValue ? ne + 1 : 0);
+      std::vector<uint64_t> off(nv + 2);
+      size_t gv = 0, ge = 0;
+      gs_check(gs_slice_neighborhoods(h, v.data(), off.data(), nbr.data(), kHasValue ? val.data() : nullptr, nv + 1,
+                                      ne + 1, &gv, &ge));
+      std::vector<std::pair<K, EV>> nb;
+      for (size_t k = 0; k < gv; ++k) {
+        nb.clear();
+        for (uint64_t e = off[k]; e < off[k + 1]; ++e) {
+          if constexpr (kHasValue) nb.emplace_back((K)nbr[e], val[e]);
+          else nb.emplace_back((K)nbr[e], NullValue{});
+        }
+        fn((K)v[k], nb);
+      }
+    });
+  }
+
+  const EdgeStream<K, EV>* edges_;
+  int64_t timeMillis_;
+  EdgeDirection dir_;
+  int device_;
+};
+
 // SimpleEdgeStream.aggregate (SimpleEdgeStream.java:100-102)
 template <typename K, typename EV>
 class SimpleEdgeStream {
  public:
   explicit SimpleEdgeStream(EdgeStream<K, EV> edges) : edges_(std::move(edges)) {}
+
+  // slice (SimpleEdgeStream.java:135-167): the stream cut into windows of timeMillis and keyed
+  // by source (OUT, the default), target (IN) or both (ALL). The SnapshotStream reads this
+  // stream's edges: keep the SimpleEdgeStream alive while it is used.
+  SnapshotStream<K, EV> slice(int64_t timeMillis, EdgeDirection direction = EdgeDirection::OUT, int device = 0) const {
+    return SnapshotStream<K, EV>(&edges_, timeMillis, direction, device);
+  }
+
   template <typename S, typename T>
   void aggregate(SummaryBulkAggregation<K, EV, S, T>& summaryAggregation,
                  const typename SummaryBulkAggregation<K, EV, S, T>::Sink& sink) {

@@ -468,6 +468,77 @@ int gs_triangle_sync(gs_triangles t);
 int gs_triangle_get_stream(gs_triangles t, void** stream);
 int gs_triangle_wait_stream(gs_triangles t, void* stream);
 
+/* ---- window slices ---------------------------------------------------------------
+ * The per-vertex neighbourhoods of one window of an edge stream: SimpleEdgeStream.slice
+ * (SimpleEdgeStream.java:135-167) and the SnapshotStream it returns, whose reduceOnEdges,
+ * foldNeighbors and applyOnNeighbors (SnapshotStream.java:61-131) read them.
+ *
+ * A slice handle is its own opaque type. It holds ONE window: a call of gs_slice_window
+ * replaces the window before it (capacity is kept). Edge i of the n edges of a window is
+ * (src[i], dst[i], val[i]), all int64; val may be NULL (a NullValue stream). The direction
+ * turns edges into entries (key, neighbour, value) numbered in arrival order:
+ *   GS_SLICE_OUT  entry i = (src, dst, val)              (the reference's default)
+ *   GS_SLICE_IN   entry i = (dst, src, val)              (reverse(), keyed by field 0)
+ *   GS_SLICE_ALL  entry 2i = (src, dst, val), entry 2i+1 = (dst, src, val)
+ *                 (undirected(), SimpleEdgeStream.java:355-360: a self-loop gives two entries)
+ * Nothing is deduplicated: repeated edges and loops are entries like any other. The window's
+ * vertices are the distinct keys; a vertex's neighbourhood is its entries in ascending entry
+ * number, Flink's per-key arrival order. Every id and value is legal, INT64_MIN and
+ * INT64_MAX included. A window has at most 2^32 - 1 entries (the sort's payload);
+ * more returns GS_ERR_CAPACITY before any device work. n = 0 is a valid, empty window.
+ *
+ * Two things are read from a window, both with rows in ascending signed vertex order (the
+ * reference's order is unspecified):
+ *   reduce          one int64 per vertex: GS_SLICE_SUM (two's-complement wrap-around, as Java
+ *                   long), GS_SLICE_MIN, GS_SLICE_MAX (signed), GS_SLICE_COUNT (the number of
+ *                   entries; values are not read). Equal to reduceOnEdges with the same
+ *                   function.
+ *   neighbourhoods  a CSR: v[nv], offset[nv + 1], neighbor[ne], val[ne]; the entries of
+ *                   vertex k are offset[k] .. offset[k + 1] - 1, in arrival order. What
+ *                   foldNeighbors and applyOnNeighbors iterate.
+ * On a window without values (val == NULL) only GS_SLICE_COUNT and an export with a NULL val
+ * array are valid; anything else returns GS_ERR_INVALID. Not built: floating-point values,
+ * user functions on the device, time-window assignment on the device, multi-GPU groups,
+ * serialization.
+ *
+ * Synchronisation: gs_slice_window* synchronises with the host ONCE, to learn the vertex
+ * count; its reads of DEVICE src / dst / val are queued on the handle's stream before that
+ * (gs_slice_wait_stream orders them behind a producer). gs_slice_reduce_device and
+ * gs_slice_neighborhoods_device queue their work on the handle's stream and do not wait;
+ * the host-array forms return with their arrays filled. Every device allocation of a handle
+ * is counted by gs_hbm_bytes and released by gs_slice_destroy.
+ *
+ * gs_slice_create: edge_hint sizes the first allocation only (0: none until the first window).
+ * gs_slice_window / _window_device: n edges from HOST arrays (copied before the call returns)
+ *   / DEVICE arrays, element i = src[i*stride], dst[i*stride], val[i*stride].
+ * gs_slice_size: the vertices and entries of the current window (no device call).
+ * gs_slice_reduce_device / gs_slice_reduce: v[k], out[k] for the *n vertices into DEVICE / HOST
+ *   arrays of capacity cap; GS_ERR_TRUNCATED with *n set and nothing written when cap < *n.
+ * gs_slice_neighborhoods_device / gs_slice_neighborhoods: the CSR into DEVICE / HOST arrays;
+ *   offset holds cap_v + 1 words, val may be NULL; GS_ERR_TRUNCATED with *nv, *ne set and
+ *   nothing written when cap_v < *nv or cap_e < *ne.
+ * gs_slice_sync / _get_stream / _wait_stream: as gs_sync / gs_get_stream / gs_wait_stream.
+ * Null handles and pointers return GS_ERR_INVALID before any device call; so do an unknown
+ * dir and an unknown op. */
+typedef struct gs_slices_s* gs_slices;
+enum gs_slice_dir { GS_SLICE_OUT = 0, GS_SLICE_IN = 1, GS_SLICE_ALL = 2 };
+enum gs_slice_op { GS_SLICE_SUM = 0, GS_SLICE_MIN = 1, GS_SLICE_MAX = 2, GS_SLICE_COUNT = 3 };
+int gs_slice_create(gs_slices* out, int device, uint64_t edge_hint);
+int gs_slice_destroy(gs_slices s); /* NULL is GS_OK */
+int gs_slice_window(gs_slices s, const int64_t* src, const int64_t* dst, const int64_t* val, size_t n, int dir);
+int gs_slice_window_device(gs_slices s, const int64_t* src, const int64_t* dst, const int64_t* val, size_t n,
+                           size_t stride, int dir);
+int gs_slice_size(gs_slices s, uint64_t* vertices, uint64_t* entries);
+int gs_slice_reduce_device(gs_slices s, int op, int64_t* v, int64_t* out, size_t cap, size_t* n);
+int gs_slice_reduce(gs_slices s, int op, int64_t* v, int64_t* out, size_t cap, size_t* n);
+int gs_slice_neighborhoods_device(gs_slices s, int64_t* v, uint64_t* offset, int64_t* neighbor, int64_t* val,
+                                  size_t cap_v, size_t cap_e, size_t* nv, size_t* ne);
+int gs_slice_neighborhoods(gs_slices s, int64_t* v, uint64_t* offset, int64_t* neighbor, int64_t* val, size_t cap_v,
+                           size_t cap_e, size_t* nv, size_t* ne);
+int gs_slice_sync(gs_slices s);
+int gs_slice_get_stream(gs_slices s, void** stream);
+int gs_slice_wait_stream(gs_slices s, void* stream);
+
 /* ---- introspection -----------------------------------------------------------
  * The HIP stream (hipStream_t) the handle enqueues on, and per-kernel timing:
  * when profiling is on, every launch is bracketed by HIP events on the stream it

@@ -45,7 +45,10 @@ enum gs_testing_knob {
   /* triangle fold: 1 = bracket the fold's phases with events and wait for them
    * (gs_testing_triangle_stats); product: 0 */
   GS_TESTING_TRIANGLE_PROFILE = 7,
-  GS_TESTING_KNOBS = 8
+  /* window slices: 1 = bracket the phases of a window, a reduce and an export with events and
+   * wait for them (gs_testing_slice_stats); product: 0 */
+  GS_TESTING_SLICE_PROFILE = 8,
+  GS_TESTING_KNOBS = 9
 };
 
 /* Set knob `knob` to `value` (< 0: the product value). Returns GS_OK or GS_ERR_INVALID. */
@@ -70,6 +73,13 @@ int gs_testing_triangle_stats(void* t, uint64_t* out);
  * gave to a workgroup with the longer row sampled in LDS; every other new edge took a lane
  * group. Both are 0 under GS_TESTING_TRIANGLE_VARIANT 1 and after a reset. Two words. */
 int gs_testing_triangle_bins(void* t, uint64_t* out);
+
+/* Diagnostics of a slice handle (`s` is a gs_slices; synchronises): out[0] = tiles of the last
+ * reduce (0: none yet, the count op reads no tile), out[1] = tiles of the current window that
+ * hold no head -- carry records that hand a run on to the next tile --, out[2] = the longest
+ * segment of the current window, out[3..7] = microseconds of the last profiled expand, sort,
+ * heads, reduce and gather phases (GS_TESTING_SLICE_PROFILE). Eight words. */
+int gs_testing_slice_stats(void* s, uint64_t* out);
 
 #ifdef __cplusplus
 }
