@@ -77,6 +77,12 @@ EXPORTED_SYMBOLS = (
     "gs_slice_create", "gs_slice_destroy", "gs_slice_window", "gs_slice_window_device", "gs_slice_size",
     "gs_slice_reduce_device", "gs_slice_reduce", "gs_slice_neighborhoods_device", "gs_slice_neighborhoods",
     "gs_slice_sync", "gs_slice_get_stream", "gs_slice_wait_stream", "gs_testing_slice_stats",
+    "gs_distinct_create", "gs_distinct_destroy", "gs_distinct_reset", "gs_distinct_fold", "gs_distinct_fold_device",
+    "gs_distinct_size", "gs_distinct_new_edges_device", "gs_distinct_new_edges", "gs_distinct_new_vertices_device",
+    "gs_distinct_new_vertices", "gs_distinct_vertices_device", "gs_distinct_vertices", "gs_distinct_edges_device",
+    "gs_distinct_edges", "gs_distinct_rank_device", "gs_distinct_contains_device", "gs_distinct_sync",
+    "gs_distinct_get_stream", "gs_distinct_wait_stream", "gs_testing_distinct_stats",
+    "gs_testing_distinct_phases",
 )
 
 # Pairs per workgroup of the component export's radix-sort kernels (csrc/gs_sort.hpp kSortTile):
@@ -109,6 +115,11 @@ TRIANGLE_SAMPLES = 1024
 SLICE_TILE = 2048
 SLICE_DIRECTIONS = {"out": 0, "in": 1, "all": 2}  # gs_slice_dir
 SLICE_OPS = {"sum": 0, "min": 1, "max": 2, "count": 3}  # gs_slice_op
+
+# Positions per workgroup of the distinct streams' flag and write kernels (csrc/gs_distinct.hpp
+# DISTINCT_TILE): the kept entries / edges of a fold are compacted tile by tile.
+DISTINCT_TILE = 2048
+DISTINCT_MODES = {"directed": 0, "undirected": 1}  # gs_distinct_mode
 
 FAIL_BIT = 1 << 62  # count words: a failed signed verdict (GS_FAIL_BIT)
 DIGEST_FAILED = (1 << 64) - 1  # gs_digest of a signed summary whose verdict failed (GS_DIGEST_FAILED)
@@ -266,6 +277,27 @@ def lib():
     L.gs_slice_get_stream.argtypes = [_vp, ctypes.POINTER(_vp)]
     L.gs_slice_wait_stream.argtypes = [_vp, _vp]
     L.gs_testing_slice_stats.argtypes = [_vp, ctypes.POINTER(_u64)]
+    L.gs_distinct_create.argtypes = [ctypes.POINTER(_vp), ctypes.c_int, ctypes.c_int, _u64, _u64]
+    L.gs_distinct_destroy.argtypes = [_vp]
+    L.gs_distinct_reset.argtypes = [_vp]
+    L.gs_distinct_fold.argtypes = [_vp, _vp, _vp, _sz]
+    L.gs_distinct_fold_device.argtypes = [_vp, _vp, _vp, _sz, _sz]
+    L.gs_distinct_size.argtypes = [_vp] + [ctypes.POINTER(_u64)] * 5
+    L.gs_distinct_new_edges_device.argtypes = [_vp, _vp, _vp, _vp, _sz, ctypes.POINTER(_sz)]
+    L.gs_distinct_new_edges.argtypes = [_vp, _vp, _vp, _vp, _sz, ctypes.POINTER(_sz)]
+    L.gs_distinct_new_vertices_device.argtypes = [_vp, _vp, _vp, _sz, ctypes.POINTER(_sz)]
+    L.gs_distinct_new_vertices.argtypes = [_vp, _vp, _vp, _sz, ctypes.POINTER(_sz)]
+    L.gs_distinct_vertices_device.argtypes = [_vp, _vp, _sz, ctypes.POINTER(_sz)]
+    L.gs_distinct_vertices.argtypes = [_vp, _vp, _sz, ctypes.POINTER(_sz)]
+    L.gs_distinct_edges_device.argtypes = [_vp, _vp, _vp, _vp, _sz, ctypes.POINTER(_sz)]
+    L.gs_distinct_edges.argtypes = [_vp, _vp, _vp, _vp, _sz, ctypes.POINTER(_sz)]
+    L.gs_distinct_rank_device.argtypes = [_vp, _vp, _sz, _vp, _vp]
+    L.gs_distinct_contains_device.argtypes = [_vp, _vp, _vp, _sz, _vp]
+    L.gs_distinct_sync.argtypes = [_vp]
+    L.gs_distinct_get_stream.argtypes = [_vp, ctypes.POINTER(_vp)]
+    L.gs_distinct_wait_stream.argtypes = [_vp, _vp]
+    L.gs_testing_distinct_stats.argtypes = [_vp, ctypes.POINTER(_u64)]
+    L.gs_testing_distinct_phases.argtypes = [_vp, ctypes.POINTER(_u64)]
     L.gs_testing_set.argtypes = [ctypes.c_int, _i64]
     L.gs_testing_get.argtypes = [ctypes.c_int]
     L.gs_testing_get.restype = _i64
@@ -313,7 +345,7 @@ def digest_rows(v, label, parity=None):
 # include/gs_testing.h: private knobs the tests use (the product reads no environment)
 TESTING_KNOBS = {"server_idle_us": 0, "changes_walk_max": 1, "parse_lb_timeout_us": 2, "group_self_apply": 3,
                  "group_data_lag": 4, "degree_variant": 5, "triangle_variant": 6, "triangle_profile": 7,
-                 "slice_profile": 8}
+                 "slice_profile": 8, "distinct_profile": 9}
 
 
 def testing_set(knob, value):
@@ -1200,6 +1232,196 @@ def _slice_dir(direction):
 
 def _slice_op(op):
     return SLICE_OPS[op] if isinstance(op, str) else int(op)
+
+
+# ---------------------------------------------------------------- distinct streams
+class Distinct:
+    """The first-seen edges and vertices of an edge stream (the gs_distinct_* section of
+    include/gs_summary.h: SimpleEdgeStream.distinct and getVertices): `fold` answers which edges
+    and endpoint entries of a batch are seen for the first time, always keeping the arrival-first
+    occurrence; `vertices` lists every vertex in first-appearance (rank) order and `edges` every
+    edge by first arrival. mode: "directed" keys an edge by (src, dst), "undirected" by the
+    unordered pair. Owns a gs_distinct handle."""
+
+    def __init__(self, device=0, mode="directed", vertex_hint=0, edge_hint=0):
+        self.device = device
+        self.mode = _distinct_mode(mode)
+        h = _vp()
+        _check(lib().gs_distinct_create(ctypes.byref(h), device, self.mode, int(vertex_hint), int(edge_hint)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().gs_distinct_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def stream(self):
+        s = _vp()
+        _check(lib().gs_distinct_get_stream(self._h, ctypes.byref(s)))
+        return s.value
+
+    def sync(self):
+        _check(lib().gs_distinct_sync(self._h))
+
+    def wait_stream(self, stream="torch"):
+        if isinstance(stream, str):
+            import torch
+            stream = torch.cuda.current_stream(self.device)
+        raw = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
+        _check(lib().gs_distinct_wait_stream(self._h, raw))
+
+    def reset(self):
+        """Both sets empty and folded = 0; capacity is kept."""
+        _check(lib().gs_distinct_reset(self._h))
+
+    def fold(self, src, dst):
+        """Fold host edges (int64 arrays); returns (new_vertices, new_edges) of this fold."""
+        s = np.ascontiguousarray(np.asarray(src, dtype=np.int64))
+        d = np.ascontiguousarray(np.asarray(dst, dtype=np.int64))
+        assert s.shape == d.shape
+        _check(lib().gs_distinct_fold(self._h, s.ctypes.data, d.ctypes.data, len(s)))
+        return self.size()[3:]
+
+    def fold_device(self, src, dst, n=None, stride=1, after=None):
+        """Fold device-resident edges (torch tensors on this device or raw pointers), element i
+        at index i * stride; `after`: a stream the edges were written on. The fold synchronises
+        with the host once (the two new counts); returns (new_vertices, new_edges)."""
+        if n is None:
+            n = src.numel() // (stride if stride > 1 else 1)
+        if after is not None:
+            self.wait_stream(after)
+        _check(lib().gs_distinct_fold_device(self._h, _ptr(src), _ptr(dst), int(n), int(stride)))
+        return self.size()[3:]
+
+    def size(self):
+        """(vertices, edges, folded, new_vertices, new_edges): totals and the last fold's counts."""
+        w = [_u64() for _ in range(5)]
+        _check(lib().gs_distinct_size(self._h, *[ctypes.byref(x) for x in w]))
+        return tuple(x.value for x in w)
+
+    def new_edges(self):
+        """(index, src, dst) of the last fold's new edges: index (uint32) ascending, the edges
+        with the orientation they arrived with."""
+        n = max(self.size()[4], 1)
+        got = _sz()
+        idx = np.empty(n, np.uint32)
+        s = np.empty(n, np.int64)
+        d = np.empty(n, np.int64)
+        _check(lib().gs_distinct_new_edges(self._h, idx.ctypes.data, s.ctypes.data, d.ctypes.data, n,
+                                           ctypes.byref(got)))
+        return idx[: got.value].copy(), s[: got.value].copy(), d[: got.value].copy()
+
+    def new_edges_device(self, index, src=None, dst=None, cap=None):
+        """The same rows into DEVICE arrays (each may be None; capacity: `cap`, or the first
+        array's numel), queued on self.stream; returns the row count."""
+        got = _sz()
+        _check(lib().gs_distinct_new_edges_device(self._h, _ptr(index), _ptr(src), _ptr(dst),
+                                                  _cap_of(cap, index, src, dst), ctypes.byref(got)))
+        return got.value
+
+    def new_vertices(self):
+        """(v, entry) of the last fold's new vertices: entry (uint32) ascending; entry 2i is the
+        src and 2i + 1 the dst of edge i of the fold."""
+        n = max(self.size()[3], 1)
+        got = _sz()
+        v = np.empty(n, np.int64)
+        e = np.empty(n, np.uint32)
+        _check(lib().gs_distinct_new_vertices(self._h, v.ctypes.data, e.ctypes.data, n, ctypes.byref(got)))
+        return v[: got.value].copy(), e[: got.value].copy()
+
+    def new_vertices_device(self, v, entry=None, cap=None):
+        got = _sz()
+        _check(lib().gs_distinct_new_vertices_device(self._h, _ptr(v), _ptr(entry), _cap_of(cap, v, entry),
+                                                     ctypes.byref(got)))
+        return got.value
+
+    def vertices(self):
+        """Every vertex in rank (first-appearance) order, a numpy int64 array."""
+        n = max(self.size()[0], 1)
+        got = _sz()
+        v = np.empty(n, np.int64)
+        _check(lib().gs_distinct_vertices(self._h, v.ctypes.data, n, ctypes.byref(got)))
+        return v[: got.value].copy()
+
+    def vertices_device(self, v, cap=None):
+        got = _sz()
+        _check(lib().gs_distinct_vertices_device(self._h, _ptr(v), _cap_of(cap, v), ctypes.byref(got)))
+        return got.value
+
+    def edges(self):
+        """(src, dst, first): every edge ascending by first arrival, first (uint64) = that
+        arrival number in the whole stream."""
+        n = max(self.size()[1], 1)
+        got = _sz()
+        s = np.empty(n, np.int64)
+        d = np.empty(n, np.int64)
+        f = np.empty(n, np.uint64)
+        _check(lib().gs_distinct_edges(self._h, s.ctypes.data, d.ctypes.data, f.ctypes.data, n, ctypes.byref(got)))
+        return s[: got.value].copy(), d[: got.value].copy(), f[: got.value].copy()
+
+    def edges_device(self, src, dst=None, first=None, cap=None):
+        got = _sz()
+        _check(lib().gs_distinct_edges_device(self._h, _ptr(src), _ptr(dst), _ptr(first),
+                                              _cap_of(cap, src, dst, first), ctypes.byref(got)))
+        return got.value
+
+    def rank_device(self, v, rank, found=None, n=None):
+        """rank[i] = first-appearance rank of the DEVICE id v[i], -1 when absent; found[i] = 1
+        when present. Asynchronous on self.stream."""
+        n = v.numel() if n is None else n
+        _check(lib().gs_distinct_rank_device(self._h, _ptr(v), int(n), _ptr(rank), _ptr(found)))
+
+    def contains_device(self, src, dst, found, n=None):
+        """found[i] = 1 when the DEVICE pair (src[i], dst[i]) is in the edge set (either
+        orientation in undirected mode). Asynchronous on self.stream."""
+        n = src.numel() if n is None else n
+        _check(lib().gs_distinct_contains_device(self._h, _ptr(src), _ptr(dst), int(n), _ptr(found)))
+
+    def stats(self):
+        """gs_testing_distinct_stats: table slots, rebuilds since create, the longest probe and
+        the edge-compaction tiles of the last fold."""
+        out = (_u64 * 6)()
+        _check(lib().gs_testing_distinct_stats(self._h, out))
+        return {"vertex_slots": out[0], "edge_slots": out[1], "vertex_rebuilds": out[2], "edge_rebuilds": out[3],
+                "longest_probe": out[4], "tiles": out[5]}
+
+    def phases(self):
+        """gs_testing_distinct_phases: the last fold under testing(distinct_profile=1): the phase
+        times (microseconds), the occurrences that issued an atomic and all its occurrences."""
+        out = (_u64 * 7)()
+        _check(lib().gs_testing_distinct_phases(self._h, out))
+        return {"vertex_probe_us": out[0], "vertex_compact_us": out[1], "edge_probe_us": out[2],
+                "edge_compact_us": out[3], "control_us": out[4], "atomics": out[5], "occurrences": out[6]}
+
+
+def _distinct_mode(mode):
+    return DISTINCT_MODES[mode] if isinstance(mode, str) else int(mode)
+
+
+def _cap_of(cap, *arrays):
+    if cap is not None:
+        return int(cap)
+    for a in arrays:
+        if a is not None and not isinstance(a, int):
+            return a.numel() if hasattr(a, "numel") else len(a)
+    return 0
 
 
 # ---------------------------------------------------------------- native multi-GPU group

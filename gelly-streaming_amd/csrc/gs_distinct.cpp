@@ -1,0 +1,575 @@
+// gs_distinct.cpp -- the distinct streams behind include/gs_summary.h's gs_distinct_* section:
+// the first-seen vertices and edges of an edge stream (SimpleEdgeStream.distinct / getVertices),
+// the first-appearance rank of every vertex, and the whole sets in arrival order. State layout
+// and the kernels are described in gs_distinct.hpp / gs_distinct_k.hip and DESIGN.md section 6e.
+//
+// A fold of n edges: growth is decided first, from host-known totals (worst case + 2 n vertices,
+// + n edges), so no table grows inside the fold; then the vertex phase (probe and stamp; flag,
+// scan, write), the edge phase (the same shape over rank pairs) and ONE host synchronisation to
+// read the two new counts and the overflow flag. A fold that grows a table or its scratch waits
+// once more, before the old arrays are freed.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <string>
+
+#include "gs_distinct.hpp"
+#include "gs_internal.hpp"
+#include "gs_slice.hpp"
+
+using namespace gsi;
+
+struct gs_distinct_s {
+  int device = 0;
+  int mode = GS_DISTINCT_DIRECTED;
+  hipStream_t stream = nullptr;
+  hipEvent_t ext_ev = nullptr;
+  DevBuf<unsigned long long> ctl;  // gs::DistCtl words
+  // the two tables and the vertex list
+  DevBuf<gs::DistVSlot> vtab;  // [vcap + 1]
+  DevBuf<gs::DistESlot> etab;  // [ecap]
+  DevBuf<int64_t> vid;         // [dist_vid_cap(vcap)] vertices in rank order
+  uint64_t vcap = 0, ecap = 0;
+  // the last fold's scratch and emissions, sized for n_cap edges
+  uint64_t n_cap = 0;
+  DevBuf<uint32_t> vslot;       // [2 n] slot of every entry
+  DevBuf<uint32_t> eslot;       // [n] slot of every edge
+  DevBuf<uint8_t> flags;        // whole tiles of 2 n positions
+  DevBuf<uint32_t> tbase;       // [tiles + 1]
+  DevBuf<uint32_t> newv_entry;  // [2 n] entries of the new vertices
+  DevBuf<uint32_t> newe_index;  // [n] indices of the kept edges
+  // device staging of a host fold
+  uint64_t h_cap = 0;
+  DevBuf<int64_t> hsrc;
+  DevBuf<int64_t> hdst;
+  // host-known totals
+  uint64_t nv = 0, ne = 0, folded = 0;
+  uint64_t last_n = 0, last_nv = 0, last_ne = 0;
+  // edge export: compacted (stamp, key) rows, the sort's scratch, staging of the host-array forms
+  SortScratch sort;
+  uint64_t x_cap = 0;
+  DevBuf<int64_t> x_stamp;
+  DevBuf<unsigned long long> x_key;
+  uint64_t o_cap = 0;
+  DevBuf<int64_t> o_a;
+  DevBuf<int64_t> o_b;
+  DevBuf<unsigned long long> o_c;
+  // diagnostics (gs_testing_distinct_stats)
+  uint64_t v_rebuilds = 0, e_rebuilds = 0, last_probe = 0, last_tiles = 0;
+  uint64_t phase_us[5] = {0, 0, 0, 0, 0};  // of the last profiled fold (gs_testing_distinct_phases)
+  uint64_t last_atomics = 0;
+
+  gs::DistVTable vtable() const { return vtable_of(vtab, vcap); }
+  gs::DistETable etable() const { return etable_of(etab, ecap); }
+  static gs::DistVTable vtable_of(gs::DistVSlot* tab, uint64_t cap) {
+    gs::DistVTable t;
+    t.tab = tab;
+    t.cap = (uint32_t)cap;
+    t.mask = (uint32_t)(cap - 1);
+    t.shift = 64 - gs::dist_log2(cap);
+    return t;
+  }
+  static gs::DistETable etable_of(gs::DistESlot* tab, uint64_t cap) {
+    gs::DistETable t;
+    t.tab = tab;
+    t.cap = (uint32_t)cap;
+    t.mask = (uint32_t)(cap - 1);
+    t.shift = 64 - gs::dist_log2(cap);
+    return t;
+  }
+};
+
+namespace {
+
+int check_distinct(gs_distinct d) {
+  if (!d) return fail(GS_ERR_INVALID, "null distinct handle");
+  return GS_OK;
+}
+
+// A vertex table of `cap` slots (and its vertex list) in place of the current one, whose
+// vertices move over; the first table of a handle when there is none.
+int grow_vertices(gs_distinct_s* d, uint64_t cap) {
+  DevBuf<gs::DistVSlot> tab;
+  DevBuf<int64_t> vid;
+  GS_HIP(tab.alloc(cap + 1));
+  GS_HIP(vid.alloc(gs::dist_vid_cap(cap)));
+  const gs::DistVTable to = gs_distinct_s::vtable_of(tab, cap);
+  gs::launch_dist_init(to, d->stream);
+  GS_HIP(hipGetLastError());
+  if (d->vtab) {
+    gs::launch_dist_rebuild(d->vtable(), to, d->ctl, d->stream);
+    GS_HIP(hipGetLastError());
+    if (d->nv) GS_HIP(hipMemcpyAsync(vid, d->vid, d->nv * 8, hipMemcpyDeviceToDevice, d->stream));
+    GS_HIP(hipStreamSynchronize(d->stream));  // before the old arrays are freed
+    ++d->v_rebuilds;
+  }
+  d->vtab.swap(tab);
+  d->vid.swap(vid);
+  d->vcap = cap;
+  return GS_OK;
+}
+
+int grow_edges(gs_distinct_s* d, uint64_t cap) {
+  DevBuf<gs::DistESlot> tab;
+  GS_HIP(tab.alloc(cap));
+  const gs::DistETable to = gs_distinct_s::etable_of(tab, cap);
+  gs::launch_dist_init(to, d->stream);
+  GS_HIP(hipGetLastError());
+  if (d->etab) {
+    gs::launch_dist_rebuild(d->etable(), to, d->ctl, d->stream);
+    GS_HIP(hipGetLastError());
+    GS_HIP(hipStreamSynchronize(d->stream));
+    ++d->e_rebuilds;
+  }
+  d->etab.swap(tab);
+  d->ecap = cap;
+  return GS_OK;
+}
+
+int ensure_scratch(gs_distinct_s* d, uint64_t n) {
+  if (d->n_cap >= n) return GS_OK;
+  GS_HIP(hipStreamSynchronize(d->stream));
+  d->n_cap = 0;
+  const uint64_t c = std::min<uint64_t>(gs::kDistMaxFold, n + n / 4);
+  const uint64_t tiles = gs::dist_tiles(2 * c, gs::DISTINCT_TILE);
+  GS_HIP(d->vslot.alloc(2 * c));
+  GS_HIP(d->eslot.alloc(c));
+  GS_HIP(d->flags.alloc(tiles * gs::DISTINCT_TILE));
+  GS_HIP(d->tbase.alloc(tiles + 1));
+  GS_HIP(d->newv_entry.alloc(2 * c));
+  GS_HIP(d->newe_index.alloc(c));
+  d->n_cap = c;
+  return GS_OK;
+}
+
+int ensure_staging(gs_distinct_s* d, uint64_t rows) {
+  if (d->o_cap >= rows) return GS_OK;
+  GS_HIP(hipStreamSynchronize(d->stream));
+  d->o_cap = 0;
+  const uint64_t c = rows + rows / 4;
+  GS_HIP(d->o_a.alloc(c));
+  GS_HIP(d->o_b.alloc(c));
+  GS_HIP(d->o_c.alloc(c));
+  d->o_cap = c;
+  return GS_OK;
+}
+
+void forget_last(gs_distinct_s* d) {
+  d->last_n = d->last_nv = d->last_ne = d->last_probe = d->last_tiles = d->last_atomics = 0;
+  for (uint64_t& us : d->phase_us) us = 0;
+}
+
+// The six events around the five phases of a fold when GS_TESTING_DISTINCT_PROFILE is 1.
+struct PhaseEvents {
+  bool on;
+  hipEvent_t ev[6] = {};
+  PhaseEvents() : on(testing_value(GS_TESTING_DISTINCT_PROFILE, 0) == 1) {
+    for (int i = 0; on && i < 6; ++i)
+      if (hipEventCreate(&ev[i]) != hipSuccess) on = false;
+  }
+  void mark(int i, hipStream_t st) {
+    if (on) (void)hipEventRecord(ev[i], st);
+  }
+  hipEvent_t mid(int i) const { return on ? ev[i] : nullptr; }
+  // after the stream was synchronised
+  void read(uint64_t us[5]) {
+    for (int i = 0; on && i < 5; ++i) {
+      float ms = 0;
+      if (hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess) us[i] = (uint64_t)(ms * 1000.0f);
+    }
+  }
+  ~PhaseEvents() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+
+int fold_guard(gs_distinct d, const void* src, const void* dst, size_t n) {
+  if (int rc = check_distinct(d)) return rc;
+  if (n && (!src || !dst)) return fail(GS_ERR_INVALID, "null edge arrays");
+  if ((uint64_t)n > gs::kDistMaxFold)
+    return fail(GS_ERR_CAPACITY, "distinct fold: " + std::to_string(n) + " edges pass 2^31 - 2 per fold");
+  // the worst case of this fold, before any device work
+  const uint64_t need_v = d->nv + gs::dist_worst_vertices(n), need_e = d->ne + gs::dist_worst_edges(n);
+  if (need_v > gs::kDistMaxVertices)
+    return fail(GS_ERR_CAPACITY, "distinct fold: the fold may pass 2^32 - 2 distinct vertices");
+  if ((gs::dist_must_grow(d->nv, gs::dist_worst_vertices(n), d->vcap) && gs::dist_slots_for(need_v) > gs::kDistMaxSlots) ||
+      (gs::dist_must_grow(d->ne, gs::dist_worst_edges(n), d->ecap) && gs::dist_slots_for(need_e) > gs::kDistMaxSlots))
+    return fail(GS_ERR_CAPACITY, "distinct fold: a table would pass 2^31 slots");
+  return GS_OK;
+}
+
+// n > 0 device edges on d->stream
+int fold_impl(gs_distinct_s* d, const int64_t* src, const int64_t* dst, uint64_t n, uint64_t stride) {
+  forget_last(d);
+  static_assert(gs::DIST_PROBE == 3 && gs::DIST_ATOMICS == 5, "the fold's words are among the first six");
+  GS_HIP(hipMemsetAsync(d->ctl, 0, 6 * 8, d->stream));
+  if (gs::dist_must_grow(d->nv, gs::dist_worst_vertices(n), d->vcap))
+    if (int rc = grow_vertices(d, gs::dist_slots_for(d->nv + gs::dist_worst_vertices(n)))) return rc;
+  if (gs::dist_must_grow(d->ne, gs::dist_worst_edges(n), d->ecap))
+    if (int rc = grow_edges(d, gs::dist_slots_for(d->ne + gs::dist_worst_edges(n)))) return rc;
+  if (int rc = ensure_scratch(d, n)) return rc;
+  const gs::DistVTable vt = d->vtable();
+  const gs::DistETable et = d->etable();
+  PhaseEvents timer;
+  timer.mark(0, d->stream);
+  gs::launch_dist_vertices(src, dst, n, stride, vt, d->vslot, d->flags, d->tbase, d->nv, d->vid,
+                           gs::dist_vid_cap(d->vcap), d->newv_entry, d->ctl, d->stream, timer.mid(1));
+  GS_HIP(hipGetLastError());
+  timer.mark(2, d->stream);
+  gs::launch_dist_edges(n, d->folded, d->mode, vt, d->vslot, et, d->eslot, d->flags, d->tbase, d->newe_index, d->ctl,
+                        d->stream, timer.mid(3));
+  GS_HIP(hipGetLastError());
+  timer.mark(4, d->stream);
+  // the fold's one host synchronisation: new vertices, new edges, overflow, longest probe
+  unsigned long long w[6] = {0, 0, 0, 0, 0, 0};
+  GS_HIP(hipMemcpyAsync(w, d->ctl, sizeof(w), hipMemcpyDeviceToHost, d->stream));
+  timer.mark(5, d->stream);
+  GS_HIP(hipStreamSynchronize(d->stream));
+  timer.read(d->phase_us);
+  d->last_atomics = w[gs::DIST_ATOMICS];
+  if (w[gs::DIST_OVERFLOW]) return fail(GS_ERR_HIP, "distinct fold: a table overflowed (the handle's state is undefined)");
+  if (w[gs::DIST_NEW_V] > 2 * n || w[gs::DIST_NEW_E] > n) return fail(GS_ERR_HIP, "distinct fold: counts out of range");
+  d->nv += w[gs::DIST_NEW_V];
+  d->ne += w[gs::DIST_NEW_E];
+  d->folded += n;
+  d->last_n = n;
+  d->last_nv = w[gs::DIST_NEW_V];
+  d->last_ne = w[gs::DIST_NEW_E];
+  d->last_probe = w[gs::DIST_PROBE];
+  d->last_tiles = gs::dist_tiles(n, gs::DISTINCT_TILE);
+  return GS_OK;
+}
+
+int truncated(size_t cap, uint64_t need) {
+  return fail(GS_ERR_TRUNCATED, "output capacity " + std::to_string(cap) + " < " + std::to_string(need));
+}
+
+int new_edges_impl(gs_distinct_s* d, uint32_t* index, int64_t* src, int64_t* dst, size_t cap, size_t* n, bool to_host) {
+  const uint64_t ne = d->last_ne;
+  *n = ne;
+  if (cap < ne) return truncated(cap, ne);
+  if (ne == 0) return GS_OK;
+  const hipMemcpyKind kind = to_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+  int64_t *ds = src, *dd = dst;
+  if (to_host && (src || dst)) {
+    if (int rc = ensure_staging(d, ne)) return rc;
+    ds = src ? d->o_a.get() : nullptr;
+    dd = dst ? d->o_b.get() : nullptr;
+  }
+  if (ds || dd) {
+    gs::launch_dist_new_edges(d->newe_index, ne, d->eslot, d->last_n, d->etable(), d->vid, d->nv, ds, dd, d->stream);
+    GS_HIP(hipGetLastError());
+  }
+  if (index) GS_HIP(hipMemcpyAsync(index, d->newe_index, ne * 4, kind, d->stream));
+  if (to_host) {
+    if (src) GS_HIP(hipMemcpyAsync(src, ds, ne * 8, hipMemcpyDeviceToHost, d->stream));
+    if (dst) GS_HIP(hipMemcpyAsync(dst, dd, ne * 8, hipMemcpyDeviceToHost, d->stream));
+    GS_HIP(hipStreamSynchronize(d->stream));
+  }
+  return GS_OK;
+}
+
+int new_vertices_impl(gs_distinct_s* d, int64_t* v, uint32_t* entry, size_t cap, size_t* n, bool to_host) {
+  const uint64_t k = d->last_nv;
+  *n = k;
+  if (cap < k) return truncated(cap, k);
+  if (k == 0) return GS_OK;
+  const hipMemcpyKind kind = to_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+  // the new vertices are the tail of the vertex list
+  if (v) GS_HIP(hipMemcpyAsync(v, d->vid + (d->nv - k), k * 8, kind, d->stream));
+  if (entry) GS_HIP(hipMemcpyAsync(entry, d->newv_entry, k * 4, kind, d->stream));
+  if (to_host) GS_HIP(hipStreamSynchronize(d->stream));
+  return GS_OK;
+}
+
+int vertices_impl(gs_distinct_s* d, int64_t* v, size_t cap, size_t* n, bool to_host) {
+  *n = d->nv;
+  if (cap < d->nv) return truncated(cap, d->nv);
+  if (d->nv == 0) return GS_OK;
+  if (!v) return fail(GS_ERR_INVALID, "null arrays");
+  GS_HIP(hipMemcpyAsync(v, d->vid, d->nv * 8, to_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, d->stream));
+  if (to_host) GS_HIP(hipStreamSynchronize(d->stream));
+  return GS_OK;
+}
+
+int edges_impl(gs_distinct_s* d, int64_t* src, int64_t* dst, uint64_t* first, size_t cap, size_t* n, bool to_host) {
+  const uint64_t ne = d->ne;
+  *n = ne;
+  if (cap < ne) return truncated(cap, ne);
+  if (ne == 0) return GS_OK;
+  if (d->x_cap < ne) {
+    GS_HIP(hipStreamSynchronize(d->stream));
+    d->x_cap = 0;
+    const uint64_t c = ne + ne / 4;
+    GS_HIP(d->x_stamp.alloc(c));
+    GS_HIP(d->x_key.alloc(c));
+    d->x_cap = c;
+  }
+  if (int rc = sort_scratch_ensure(d->sort, ne, d->stream)) return rc;
+  int64_t *ds = src, *dd = dst;
+  unsigned long long* df = reinterpret_cast<unsigned long long*>(first);
+  if (to_host) {
+    if (int rc = ensure_staging(d, ne)) return rc;
+    ds = src ? d->o_a.get() : nullptr;
+    dd = dst ? d->o_b.get() : nullptr;
+    df = first ? d->o_c.get() : nullptr;
+  }
+  // scan the table, compact, sort by stamp, decode through the vertex list
+  GS_HIP(hipMemsetAsync(d->ctl + gs::DIST_EXPORT, 0, 8, d->stream));
+  gs::launch_dist_export(d->etable(), d->x_stamp, d->x_key, ne, d->ctl, d->stream);
+  GS_HIP(hipGetLastError());
+  uint32_t* const sctl = d->sort.ctl;
+  GS_HIP(hipMemsetAsync(sctl, 0, gs::kSortCtlWords * 4, d->stream));
+  gs::launch_slice_digits(d->x_stamp, ne, sctl, d->stream);  // rows 0..7: the digit histograms of one key column
+  GS_HIP(hipGetLastError());
+  // every stamp is below 2 * folded: the digits above its bits are equal in all keys
+  bool skip[gs::kSortPasses];
+  for (int p = 0; p < (int)gs::kSortPasses; ++p) skip[p] = p > 0 && 8 * p < 64 && ((2 * d->folded) >> (8 * p)) == 0;
+  gs::SortSrc cur;  // (pay null: payload i of row i is i)
+  int side = 0;
+  if (int rc = sort_run(d->sort, d->x_stamp, ne, sctl, skip, &cur, &side, d->stream)) return rc;
+  if (!cur.key || !cur.pay) return fail(GS_ERR_HIP, "distinct edges: the sort ran no pass");
+  gs::launch_dist_decode(cur.key, cur.pay, d->x_key, ne, d->vid, d->nv, ds, dd, df, d->stream);
+  GS_HIP(hipGetLastError());
+  if (to_host) {
+    if (src) GS_HIP(hipMemcpyAsync(src, ds, ne * 8, hipMemcpyDeviceToHost, d->stream));
+    if (dst) GS_HIP(hipMemcpyAsync(dst, dd, ne * 8, hipMemcpyDeviceToHost, d->stream));
+    if (first) GS_HIP(hipMemcpyAsync(first, df, ne * 8, hipMemcpyDeviceToHost, d->stream));
+    GS_HIP(hipStreamSynchronize(d->stream));
+  }
+  return GS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gs_distinct_destroy(gs_distinct d) {
+  if (!d) return GS_OK;
+  DeviceGuard g(d->device);
+  if (d->stream) (void)hipStreamSynchronize(d->stream);
+  if (d->ext_ev) (void)hipEventDestroy(d->ext_ev);
+  const hipStream_t stream = d->stream;
+  delete d;  // frees every device buffer (DevBuf members): device current, the stream idle
+  if (stream) (void)hipStreamDestroy(stream);
+  return GS_OK;
+}
+
+int gs_distinct_create(gs_distinct* out, int device, int mode, uint64_t vertex_hint, uint64_t edge_hint) {
+  if (!out) return fail(GS_ERR_INVALID, "out is null");
+  *out = nullptr;
+  if (mode < 0 || mode >= gs::kDistModes) return fail(GS_ERR_INVALID, "unknown distinct mode");
+  if (vertex_hint > gs::kDistMaxVertices || gs::dist_slots_for(vertex_hint) > gs::kDistMaxSlots ||
+      edge_hint > gs::kDistMaxSlots / 2)
+    return fail(GS_ERR_CAPACITY, "distinct create: a hint passes 2^31 table slots");
+  int count = 0;
+  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail(GS_ERR_HIP, "no HIP device available");
+  if (device < 0 || device >= count) return fail(GS_ERR_INVALID, "bad device");
+  DeviceGuard g(device);
+  gs_distinct_s* d = new gs_distinct_s();
+  d->device = device;
+  d->mode = mode;
+  auto body = [&]() -> int {
+    GS_HIP(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
+    GS_HIP(hipEventCreateWithFlags(&d->ext_ev, hipEventDisableTiming));
+    GS_HIP(d->ctl.alloc(gs::DIST_CTL_WORDS));
+    GS_HIP(hipMemsetAsync(d->ctl, 0, gs::DIST_CTL_WORDS * 8, d->stream));
+    if (int rc = grow_vertices(d, gs::dist_slots_for(vertex_hint))) return rc;
+    if (int rc = grow_edges(d, gs::dist_slots_for(edge_hint))) return rc;
+    GS_HIP(hipStreamSynchronize(d->stream));
+    return GS_OK;
+  };
+  const int rc = body();
+  if (rc) {
+    const std::string msg = gs_last_error();
+    (void)gs_distinct_destroy(d);
+    return fail(rc, msg);
+  }
+  *out = d;
+  return GS_OK;
+}
+
+int gs_distinct_reset(gs_distinct d) {
+  if (int rc = check_distinct(d)) return rc;
+  DeviceGuard g(d->device);
+  gs::launch_dist_init(d->vtable(), d->stream);
+  GS_HIP(hipGetLastError());
+  gs::launch_dist_init(d->etable(), d->stream);
+  GS_HIP(hipGetLastError());
+  d->nv = d->ne = d->folded = 0;
+  forget_last(d);
+  return GS_OK;
+}
+
+int gs_distinct_fold_device(gs_distinct d, const int64_t* src, const int64_t* dst, size_t n, size_t stride) {
+  if (int rc = fold_guard(d, src, dst, n)) return rc;
+  if (stride == 0 || stride > 0xFFFFFFFFull) return fail(GS_ERR_INVALID, "stride must be >= 1");
+  if (n == 0) {
+    forget_last(d);
+    return GS_OK;
+  }
+  DeviceGuard g(d->device);
+  return fold_impl(d, src, dst, n, stride);
+}
+
+int gs_distinct_fold(gs_distinct d, const int64_t* src, const int64_t* dst, size_t n) {
+  if (int rc = fold_guard(d, src, dst, n)) return rc;
+  if (n == 0) {
+    forget_last(d);
+    return GS_OK;
+  }
+  DeviceGuard g(d->device);
+  if (d->h_cap < n) {
+    GS_HIP(hipStreamSynchronize(d->stream));
+    d->h_cap = 0;
+    const uint64_t c = n + n / 4;
+    GS_HIP(d->hsrc.alloc(c));
+    GS_HIP(d->hdst.alloc(c));
+    d->h_cap = c;
+  }
+  GS_HIP(hipMemcpyAsync(d->hsrc, src, n * 8, hipMemcpyHostToDevice, d->stream));
+  GS_HIP(hipMemcpyAsync(d->hdst, dst, n * 8, hipMemcpyHostToDevice, d->stream));
+  // (fold_impl waits for the stream before it returns: the host arrays are free then)
+  return fold_impl(d, d->hsrc, d->hdst, n, 1);
+}
+
+int gs_distinct_size(gs_distinct d, uint64_t* vertices, uint64_t* edges, uint64_t* folded, uint64_t* new_vertices,
+                     uint64_t* new_edges) {
+  if (int rc = check_distinct(d)) return rc;
+  if (!vertices || !edges || !folded || !new_vertices || !new_edges)
+    return fail(GS_ERR_INVALID, "null count pointers");
+  *vertices = d->nv;
+  *edges = d->ne;
+  *folded = d->folded;
+  *new_vertices = d->last_nv;
+  *new_edges = d->last_ne;
+  return GS_OK;
+}
+
+int gs_distinct_new_edges_device(gs_distinct d, uint32_t* index, int64_t* src, int64_t* dst, size_t cap, size_t* n) {
+  if (int rc = check_distinct(d)) return rc;
+  if (!n) return fail(GS_ERR_INVALID, "n is null");
+  DeviceGuard g(d->device);
+  return new_edges_impl(d, index, src, dst, cap, n, false);
+}
+
+int gs_distinct_new_edges(gs_distinct d, uint32_t* index, int64_t* src, int64_t* dst, size_t cap, size_t* n) {
+  if (int rc = check_distinct(d)) return rc;
+  if (!n) return fail(GS_ERR_INVALID, "n is null");
+  DeviceGuard g(d->device);
+  return new_edges_impl(d, index, src, dst, cap, n, true);
+}
+
+int gs_distinct_new_vertices_device(gs_distinct d, int64_t* v, uint32_t* entry, size_t cap, size_t* n) {
+  if (int rc = check_distinct(d)) return rc;
+  if (!n) return fail(GS_ERR_INVALID, "n is null");
+  DeviceGuard g(d->device);
+  return new_vertices_impl(d, v, entry, cap, n, false);
+}
+
+int gs_distinct_new_vertices(gs_distinct d, int64_t* v, uint32_t* entry, size_t cap, size_t* n) {
+  if (int rc = check_distinct(d)) return rc;
+  if (!n) return fail(GS_ERR_INVALID, "n is null");
+  DeviceGuard g(d->device);
+  return new_vertices_impl(d, v, entry, cap, n, true);
+}
+
+int gs_distinct_vertices_device(gs_distinct d, int64_t* v, size_t cap, size_t* n) {
+  if (int rc = check_distinct(d)) return rc;
+  if (!n) return fail(GS_ERR_INVALID, "n is null");
+  DeviceGuard g(d->device);
+  return vertices_impl(d, v, cap, n, false);
+}
+
+int gs_distinct_vertices(gs_distinct d, int64_t* v, size_t cap, size_t* n) {
+  if (int rc = check_distinct(d)) return rc;
+  if (!n) return fail(GS_ERR_INVALID, "n is null");
+  DeviceGuard g(d->device);
+  return vertices_impl(d, v, cap, n, true);
+}
+
+int gs_distinct_edges_device(gs_distinct d, int64_t* src, int64_t* dst, uint64_t* first, size_t cap, size_t* n) {
+  if (int rc = check_distinct(d)) return rc;
+  if (!n) return fail(GS_ERR_INVALID, "n is null");
+  DeviceGuard g(d->device);
+  return edges_impl(d, src, dst, first, cap, n, false);
+}
+
+int gs_distinct_edges(gs_distinct d, int64_t* src, int64_t* dst, uint64_t* first, size_t cap, size_t* n) {
+  if (int rc = check_distinct(d)) return rc;
+  if (!n) return fail(GS_ERR_INVALID, "n is null");
+  DeviceGuard g(d->device);
+  return edges_impl(d, src, dst, first, cap, n, true);
+}
+
+int gs_distinct_rank_device(gs_distinct d, const int64_t* v, size_t n, int64_t* rank, uint8_t* found) {
+  if (int rc = check_distinct(d)) return rc;
+  if (n == 0) return GS_OK;
+  if (!v || !rank) return fail(GS_ERR_INVALID, "null arrays");
+  DeviceGuard g(d->device);
+  gs::launch_dist_rank(d->vtable(), v, n, rank, found, d->stream);
+  GS_HIP(hipGetLastError());
+  return GS_OK;
+}
+
+int gs_distinct_contains_device(gs_distinct d, const int64_t* src, const int64_t* dst, size_t n, uint8_t* found) {
+  if (int rc = check_distinct(d)) return rc;
+  if (n == 0) return GS_OK;
+  if (!src || !dst || !found) return fail(GS_ERR_INVALID, "null arrays");
+  DeviceGuard g(d->device);
+  gs::launch_dist_contains(d->vtable(), d->etable(), d->mode, src, dst, n, found, d->stream);
+  GS_HIP(hipGetLastError());
+  return GS_OK;
+}
+
+int gs_distinct_sync(gs_distinct d) {
+  if (int rc = check_distinct(d)) return rc;
+  DeviceGuard g(d->device);
+  GS_HIP(hipStreamSynchronize(d->stream));
+  return GS_OK;
+}
+
+int gs_distinct_get_stream(gs_distinct d, void** stream) {
+  if (int rc = check_distinct(d)) return rc;
+  if (!stream) return fail(GS_ERR_INVALID, "stream is null");
+  *stream = d->stream;
+  return GS_OK;
+}
+
+int gs_distinct_wait_stream(gs_distinct d, void* stream) {
+  if (int rc = check_distinct(d)) return rc;
+  DeviceGuard g(d->device);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (st == d->stream) return GS_OK;
+  GS_HIP(hipEventRecord(d->ext_ev, st));  // (stream 0 = the device's null stream)
+  GS_HIP(hipStreamWaitEvent(d->stream, d->ext_ev, 0));
+  return GS_OK;
+}
+
+// gs_testing.h: six words, all host-known (no device call)
+int gs_testing_distinct_stats(void* handle, uint64_t* out) {
+  gs_distinct d = static_cast<gs_distinct>(handle);
+  if (int rc = check_distinct(d)) return rc;
+  if (!out) return fail(GS_ERR_INVALID, "out is null");
+  out[0] = d->vcap;
+  out[1] = d->ecap;
+  out[2] = d->v_rebuilds;
+  out[3] = d->e_rebuilds;
+  out[4] = d->last_probe;
+  out[5] = d->last_tiles;
+  return GS_OK;
+}
+
+// gs_testing.h: seven words of the last profiled fold, all host-known
+int gs_testing_distinct_phases(void* handle, uint64_t* out) {
+  gs_distinct d = static_cast<gs_distinct>(handle);
+  if (int rc = check_distinct(d)) return rc;
+  if (!out) return fail(GS_ERR_INVALID, "out is null");
+  for (int i = 0; i < 5; ++i) out[i] = d->phase_us[i];
+  out[5] = d->last_atomics;
+  out[6] = 3 * d->last_n;
+  return GS_OK;
+}
+
+}  // extern "C"

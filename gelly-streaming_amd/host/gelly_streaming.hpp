@@ -12,6 +12,8 @@
 //                               keyed window fold -> all-window reduce -> Merger)
 //   SimpleEdgeStream::aggregate SimpleEdgeStream.java:100-102
 //   SimpleEdgeStream::slice     SimpleEdgeStream.java:135-167
+//   SimpleEdgeStream::distinct  SimpleEdgeStream.java:301-323 (the pinned behaviour: first-seen pairs)
+//   SimpleEdgeStream::getVertices SimpleEdgeStream.java:116-121, 181-202
 //   SnapshotStream              SnapshotStream.java:61-131 (reduceOnEdges / foldNeighbors /
 //                               applyOnNeighbors over a GPU-resident window slice)
 //   DisjointSet                 summaries/DisjointSet.java:25-151  (GPU-resident forest)
@@ -902,7 +904,67 @@ class SimpleEdgeStream {
   // numberOfEdges (SimpleEdgeStream.java:388-404): a host count.
   long numberOfEdges() const { return (long)edges_.edges.size(); }
 
+  // distinct (SimpleEdgeStream.java:301-323): the stream of first-seen (source, target) pairs,
+  // each with the value and timestamp of its first occurrence, in arrival order. The documented
+  // and pinned behaviour (TestDistinct.java:38-44), not DistinctEdgeMapper's single set of
+  // targets (include/gs_summary.h, the gs_distinct_* section). The stream's edges are folded
+  // through a distinct handle on `device`.
+  SimpleEdgeStream<K, EV> distinct(int device = 0) const {
+    DistinctHandle h(device, edges_.edges.size());
+    fold_distinct(h.d);
+    uint64_t nv = 0, ne = 0, folded = 0, new_v = 0, new_e = 0;
+    gs_check(gs_distinct_size(h.d, &nv, &ne, &folded, &new_v, &new_e));
+    std::vector<uint32_t> index(new_e + 1);
+    size_t got = 0;
+    gs_check(gs_distinct_new_edges(h.d, index.data(), nullptr, nullptr, index.size(), &got));
+    EdgeStream<K, EV> out;
+    out.parallelism = edges_.parallelism;
+    out.edges.reserve(got);
+    for (size_t k = 0; k < got; ++k) {
+      out.edges.push_back(edges_.edges[index[k]]);
+      if (!edges_.timestamps.empty()) out.timestamps.push_back(edges_.timestamps[index[k]]);
+    }
+    return SimpleEdgeStream<K, EV>(std::move(out));
+  }
+
+  // getVertices (SimpleEdgeStream.java:116-121, 181-202): every vertex once, at its first
+  // appearance (source before target), in emission order.
+  std::vector<Vertex<K, NullValue>> getVertices(int device = 0) const {
+    DistinctHandle h(device, edges_.edges.size());
+    fold_distinct(h.d);
+    uint64_t nv = 0, ne = 0, folded = 0, new_v = 0, new_e = 0;
+    gs_check(gs_distinct_size(h.d, &nv, &ne, &folded, &new_v, &new_e));
+    std::vector<int64_t> v(nv + 1);
+    size_t got = 0;
+    gs_check(gs_distinct_vertices(h.d, v.data(), v.size(), &got));
+    std::vector<Vertex<K, NullValue>> out(got);
+    for (size_t k = 0; k < got; ++k) out[k] = Vertex<K, NullValue>{(K)v[k], NullValue{}};
+    return out;
+  }
+
+  const EdgeStream<K, EV>& getEdges() const { return edges_; }
+
  private:
+  struct DistinctHandle {
+    gs_distinct d = nullptr;
+    DistinctHandle(int device, size_t edges) {
+      gs_check(gs_distinct_create(&d, device, GS_DISTINCT_DIRECTED, 2 * edges, edges));
+    }
+    ~DistinctHandle() { gs_distinct_destroy(d); }
+    DistinctHandle(const DistinctHandle&) = delete;
+    DistinctHandle& operator=(const DistinctHandle&) = delete;
+  };
+
+  void fold_distinct(gs_distinct d) const {
+    const size_t n = edges_.edges.size();
+    std::vector<int64_t> src(n), dst(n);
+    for (size_t i = 0; i < n; ++i) {
+      src[i] = (int64_t)edges_.edges[i].getSource();
+      dst[i] = (int64_t)edges_.edges[i].getTarget();
+    }
+    gs_check(gs_distinct_fold(d, src.data(), dst.data(), n));
+  }
+
   struct DegreeHandle {
     gs_handle h = nullptr;
     DegreeHandle(int device, size_t edges) {

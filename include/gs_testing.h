@@ -48,7 +48,11 @@ enum gs_testing_knob {
   /* window slices: 1 = bracket the phases of a window, a reduce and an export with events and
    * wait for them (gs_testing_slice_stats); product: 0 */
   GS_TESTING_SLICE_PROFILE = 8,
-  GS_TESTING_KNOBS = 9
+  /* distinct streams: 1 = bracket the five phases of a fold with events, wait for them, and count
+   * the occurrences that issue an atomic minimum (gs_testing_distinct_phases; needed by
+   * tools/distinct_bench.py); product: 0 */
+  GS_TESTING_DISTINCT_PROFILE = 9,
+  GS_TESTING_KNOBS = 10
 };
 
 /* Set knob `knob` to `value` (< 0: the product value). Returns GS_OK or GS_ERR_INVALID. */
@@ -80,6 +84,21 @@ int gs_testing_triangle_bins(void* t, uint64_t* out);
  * segment of the current window, out[3..7] = microseconds of the last profiled expand, sort,
  * heads, reduce and gather phases (GS_TESTING_SLICE_PROFILE). Eight words. */
 int gs_testing_slice_stats(void* s, uint64_t* out);
+
+/* Diagnostics of a distinct handle (`d` is a gs_distinct; no device call): out[0] = slots of the
+ * vertex table, out[1] = slots of the edge table, out[2] / out[3] = rebuilds of the vertex / edge
+ * table since create, out[4] = the longest probe of the last fold in slots past the home slot
+ * (either table; kept with an atomic maximum issued only when a probe left its home slot),
+ * out[5] = tiles of the last fold's edge compaction (its entry compaction runs over twice as
+ * many positions). Six words. */
+int gs_testing_distinct_stats(void* d, uint64_t* out);
+
+/* The last fold of a distinct handle under GS_TESTING_DISTINCT_PROFILE 1 (`d` is a gs_distinct; no
+ * device call; all zero otherwise): out[0..4] = microseconds of its vertex probe, vertex
+ * compaction, edge probe, edge compaction, and control read with the host synchronisation,
+ * out[5] = occurrences that issued an atomic minimum, out[6] = its occurrences (2 n entries + n
+ * edges). Seven words. */
+int gs_testing_distinct_phases(void* d, uint64_t* out);
 
 #ifdef __cplusplus
 }
