@@ -1015,6 +1015,15 @@ static int ensure_dev_stage(gs_summary* h, size_t edges) {
 static int fold_host_impl(gs_handle h, const int64_t* src, const int64_t* dst, const uint8_t* w, size_t n) {
   bool direct_pending = false;
   const bool pinned = n > kDirectCopyEdges && host_pinned(src) && host_pinned(dst) && host_pinned(w);
+  if (h->track && n > kStageChunk) {
+    // every stage chunk is a fold of its own: a tracked call whose later chunk would pass
+    // the delta list is refused here as a whole, before its first chunk folds
+    uint64_t fill = h->delta_fill_ub[h->dset];
+    for (size_t off = 0; off < n; off += kStageChunk) fill += per_shard_edges(std::min<size_t>(kStageChunk, n - off));
+    if (!h->drec || fill > h->delta_shard_cap)
+      return fail(GS_ERR_CAPACITY, "delta list full: stage or take the delta records after at most " +
+                                       std::to_string(h->delta_edges) + " folded edges");
+  }
   if (n) {
     if (int rc = ensure_dev_stage(h, std::min<size_t>(n, kStageChunk))) return rc;
   }

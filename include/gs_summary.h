@@ -254,7 +254,11 @@ int gs_export_components(gs_handle h, int64_t* comp, uint64_t* offset, int64_t* 
 
 /* Checkpoint: compact (vertex, label, parity) image of the summary plus the
  * verdict, for Merger.snapshotState/restoreState (SummaryAggregation.java:127-135).
- * Call with buf = NULL to get *len. gs_deserialize replaces the summary. */
+ * Call with buf = NULL to get *len. gs_deserialize replaces the summary: a gs_reset,
+ * then a fold of the image's rows. On a handle with change tracking on that is what a
+ * sink sees too: the reset empties the summary (changes not yet taken are dropped, and
+ * the sink's state is to be dropped with them), and the next take emits every vertex of
+ * the image once, so a sink cleared at the deserialize holds exactly the image's rows. */
 int gs_serialize(gs_handle h, void* buf, size_t cap, size_t* len);
 int gs_deserialize(gs_handle h, const void* buf, size_t len);
 
@@ -269,7 +273,8 @@ int gs_deserialize(gs_handle h, const void* buf, size_t len);
  *
  * The delta list holds the records of gs_delta_capacity() rows (the folds of at
  * least 2^22 edges, more after gs_group_create with a larger batch) between two
- * takes/stages; a tracked fold past that fails with GS_ERR_CAPACITY.
+ * takes/stages; a tracked fold past that fails with GS_ERR_CAPACITY before it folds
+ * anything (a host fold of several staging chunks is refused as a whole).
  *
  * gs_take_delta_records packs the delta accumulated since the previous take into
  * DEVICE records {a, b, w} (24 bytes; w bit 0 = parity, w bit 7 = skip), first
