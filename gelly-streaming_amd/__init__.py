@@ -89,6 +89,14 @@ EXPORTED_SYMBOLS = (
 # sizes around it are where a tile fills exactly.
 SORT_TILE = 2048
 
+# The union-find fold (csrc/gs_device.hpp kFoldBS, kShards; csrc/gs_kernels.hip GS_COMBINE_ROUNDS):
+# edges per workgroup of k_fold (one per thread), the shards a launch's workgroups rotate their
+# appends through, and the groups of lanes sharing a larger-key root that one wave combines
+# before the rest go to the hook loop uncombined.
+FOLD_BLOCK = 256
+FOLD_SHARDS = 64
+FOLD_COMBINE_ROUNDS = 2
+
 # Edges per workgroup of the degree fold (csrc/gs_degree.hpp DEGREE_TILE): the tile whose
 # endpoint occurrences are combined on chip; sizes around it are where a tile fills exactly.
 DEGREE_TILE = 2048
