@@ -88,6 +88,11 @@ EXPORTED_SYMBOLS = (
 # Pairs per workgroup of the component export's radix-sort kernels (csrc/gs_sort.hpp kSortTile):
 # sizes around it are where a tile fills exactly.
 SORT_TILE = 2048
+# Tile counts per step of the one-workgroup scan between a flag and a write kernel (csrc/gs_sort.hpp
+# kSortScanBS, launch_tile_scan; the slices, the distinct streams and the triangle summary compact
+# through it): past TILE_SCAN_BLOCK tiles of SLICE_TILE / DISTINCT_TILE / TRIANGLE_TILE elements the
+# scan carries a sum from one step into the next.
+TILE_SCAN_BLOCK = 1024
 
 # The union-find fold (csrc/gs_device.hpp kFoldBS, kShards; csrc/gs_kernels.hip GS_COMBINE_ROUNDS):
 # edges per workgroup of k_fold (one per thread), the shards a launch's workgroups rotate their

@@ -15,15 +15,11 @@
 
 #include "gs_distinct.hpp"
 #include "gs_internal.hpp"
-#include "gs_slice.hpp"
 
 using namespace gsi;
 
-struct gs_distinct_s {
-  int device = 0;
+struct gs_distinct_s : StreamOwner {
   int mode = GS_DISTINCT_DIRECTED;
-  hipStream_t stream = nullptr;
-  hipEvent_t ext_ev = nullptr;
   DevBuf<unsigned long long> ctl;  // gs::DistCtl words
   // the two tables and the vertex list
   DevBuf<gs::DistVSlot> vtab;  // [vcap + 1]
@@ -159,31 +155,6 @@ void forget_last(gs_distinct_s* d) {
   for (uint64_t& us : d->phase_us) us = 0;
 }
 
-// The six events around the five phases of a fold when GS_TESTING_DISTINCT_PROFILE is 1.
-struct PhaseEvents {
-  bool on;
-  hipEvent_t ev[6] = {};
-  PhaseEvents() : on(testing_value(GS_TESTING_DISTINCT_PROFILE, 0) == 1) {
-    for (int i = 0; on && i < 6; ++i)
-      if (hipEventCreate(&ev[i]) != hipSuccess) on = false;
-  }
-  void mark(int i, hipStream_t st) {
-    if (on) (void)hipEventRecord(ev[i], st);
-  }
-  hipEvent_t mid(int i) const { return on ? ev[i] : nullptr; }
-  // after the stream was synchronised
-  void read(uint64_t us[5]) {
-    for (int i = 0; on && i < 5; ++i) {
-      float ms = 0;
-      if (hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess) us[i] = (uint64_t)(ms * 1000.0f);
-    }
-  }
-  ~PhaseEvents() {
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
-};
-
 int fold_guard(gs_distinct d, const void* src, const void* dst, size_t n) {
   if (int rc = check_distinct(d)) return rc;
   if (n && (!src || !dst)) return fail(GS_ERR_INVALID, "null edge arrays");
@@ -211,22 +182,22 @@ int fold_impl(gs_distinct_s* d, const int64_t* src, const int64_t* dst, uint64_t
   if (int rc = ensure_scratch(d, n)) return rc;
   const gs::DistVTable vt = d->vtable();
   const gs::DistETable et = d->etable();
-  PhaseEvents timer;
-  timer.mark(0, d->stream);
+  PhaseTimer timer(d->stream, testing_value(GS_TESTING_DISTINCT_PROFILE, 0) == 1, d->phase_us, 5);
+  timer.mark(0);
   gs::launch_dist_vertices(src, dst, n, stride, vt, d->vslot, d->flags, d->tbase, d->nv, d->vid,
-                           gs::dist_vid_cap(d->vcap), d->newv_entry, d->ctl, d->stream, timer.mid(1));
+                           gs::dist_vid_cap(d->vcap), d->newv_entry, d->ctl, d->stream, timer.event(1));
   GS_HIP(hipGetLastError());
-  timer.mark(2, d->stream);
+  timer.mark(2);
   gs::launch_dist_edges(n, d->folded, d->mode, vt, d->vslot, et, d->eslot, d->flags, d->tbase, d->newe_index, d->ctl,
-                        d->stream, timer.mid(3));
+                        d->stream, timer.event(3));
   GS_HIP(hipGetLastError());
-  timer.mark(4, d->stream);
+  timer.mark(4);
   // the fold's one host synchronisation: new vertices, new edges, overflow, longest probe
   unsigned long long w[6] = {0, 0, 0, 0, 0, 0};
   GS_HIP(hipMemcpyAsync(w, d->ctl, sizeof(w), hipMemcpyDeviceToHost, d->stream));
-  timer.mark(5, d->stream);
+  timer.mark(5);
   GS_HIP(hipStreamSynchronize(d->stream));
-  timer.read(d->phase_us);
+  timer.finish();
   d->last_atomics = w[gs::DIST_ATOMICS];
   if (w[gs::DIST_OVERFLOW]) return fail(GS_ERR_HIP, "distinct fold: a table overflowed (the handle's state is undefined)");
   if (w[gs::DIST_NEW_V] > 2 * n || w[gs::DIST_NEW_E] > n) return fail(GS_ERR_HIP, "distinct fold: counts out of range");
@@ -321,7 +292,7 @@ int edges_impl(gs_distinct_s* d, int64_t* src, int64_t* dst, uint64_t* first, si
   GS_HIP(hipGetLastError());
   uint32_t* const sctl = d->sort.ctl;
   GS_HIP(hipMemsetAsync(sctl, 0, gs::kSortCtlWords * 4, d->stream));
-  gs::launch_slice_digits(d->x_stamp, ne, sctl, d->stream);  // rows 0..7: the digit histograms of one key column
+  gs::launch_sort_digits_one(d->x_stamp, ne, sctl, d->stream);  // rows 0..7: the digit histograms of one key column
   GS_HIP(hipGetLastError());
   // every stamp is below 2 * folded: the digits above its bits are equal in all keys
   bool skip[gs::kSortPasses];
@@ -345,16 +316,7 @@ int edges_impl(gs_distinct_s* d, int64_t* src, int64_t* dst, uint64_t* first, si
 
 extern "C" {
 
-int gs_distinct_destroy(gs_distinct d) {
-  if (!d) return GS_OK;
-  DeviceGuard g(d->device);
-  if (d->stream) (void)hipStreamSynchronize(d->stream);
-  if (d->ext_ev) (void)hipEventDestroy(d->ext_ev);
-  const hipStream_t stream = d->stream;
-  delete d;  // frees every device buffer (DevBuf members): device current, the stream idle
-  if (stream) (void)hipStreamDestroy(stream);
-  return GS_OK;
-}
+int gs_distinct_destroy(gs_distinct d) { return owner_destroy(d); }
 
 int gs_distinct_create(gs_distinct* out, int device, int mode, uint64_t vertex_hint, uint64_t edge_hint) {
   if (!out) return fail(GS_ERR_INVALID, "out is null");
@@ -363,31 +325,14 @@ int gs_distinct_create(gs_distinct* out, int device, int mode, uint64_t vertex_h
   if (vertex_hint > gs::kDistMaxVertices || gs::dist_slots_for(vertex_hint) > gs::kDistMaxSlots ||
       edge_hint > gs::kDistMaxSlots / 2)
     return fail(GS_ERR_CAPACITY, "distinct create: a hint passes 2^31 table slots");
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail(GS_ERR_HIP, "no HIP device available");
-  if (device < 0 || device >= count) return fail(GS_ERR_INVALID, "bad device");
-  DeviceGuard g(device);
-  gs_distinct_s* d = new gs_distinct_s();
-  d->device = device;
-  d->mode = mode;
-  auto body = [&]() -> int {
-    GS_HIP(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
-    GS_HIP(hipEventCreateWithFlags(&d->ext_ev, hipEventDisableTiming));
+  if (int rc = check_device_index(device)) return rc;
+  return owner_create(out, device, [&](gs_distinct_s* d) -> int {
+    d->mode = mode;
     GS_HIP(d->ctl.alloc(gs::DIST_CTL_WORDS));
     GS_HIP(hipMemsetAsync(d->ctl, 0, gs::DIST_CTL_WORDS * 8, d->stream));
     if (int rc = grow_vertices(d, gs::dist_slots_for(vertex_hint))) return rc;
-    if (int rc = grow_edges(d, gs::dist_slots_for(edge_hint))) return rc;
-    GS_HIP(hipStreamSynchronize(d->stream));
-    return GS_OK;
-  };
-  const int rc = body();
-  if (rc) {
-    const std::string msg = gs_last_error();
-    (void)gs_distinct_destroy(d);
-    return fail(rc, msg);
-  }
-  *out = d;
-  return GS_OK;
+    return grow_edges(d, gs::dist_slots_for(edge_hint));
+  });
 }
 
 int gs_distinct_reset(gs_distinct d) {
@@ -539,12 +484,7 @@ int gs_distinct_get_stream(gs_distinct d, void** stream) {
 
 int gs_distinct_wait_stream(gs_distinct d, void* stream) {
   if (int rc = check_distinct(d)) return rc;
-  DeviceGuard g(d->device);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (st == d->stream) return GS_OK;
-  GS_HIP(hipEventRecord(d->ext_ev, st));  // (stream 0 = the device's null stream)
-  GS_HIP(hipStreamWaitEvent(d->stream, d->ext_ev, 0));
-  return GS_OK;
+  return d->wait_stream(stream);
 }
 
 // gs_testing.h: six words, all host-known (no device call)

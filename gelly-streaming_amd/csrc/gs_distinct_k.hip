@@ -8,8 +8,9 @@
 //                     that is not larger; the slot index goes to scratch
 //   k_dist_flag<1>  : phase 2. One flag byte per entry (new: no rank, stamp == entry + 1), kept
 //                     positions per tile
-//   k_dist_scan     : exclusive scan of the tile counts (one workgroup); the total
-//   k_dist_vwrite   : the new vertices in entry order: vid[], entry[], the slot's rank
+//   k_dist_vwrite   : the new vertices in entry order: vid[], entry[], the slot's rank; between
+//                     a flag and a write kernel, the sort's launch_tile_scan turns the tile
+//                     counts into tile bases and the total
 //   k_dist_edges    : phase 3. One edge per thread: the two ranks through the stored slot
 //                     indices, the key, insert-or-find, a minimum of arrival << 1 | swapped into
 //                     the stamp; an edge of an earlier fold is dropped without an atomic
@@ -17,7 +18,8 @@
 //   k_dist_ewrite   : the kept edge indices ascending
 //   k_dist_new_edges / k_dist_export / k_dist_decode : the emissions and the whole edge set
 //   k_dist_rank / k_dist_contains   : read-only probes
-// Encodings, predicates, key packing, home slots and tile arithmetic are gs_distinct_seq.hpp's.
+// Encodings, predicates, key packing, home slots and tile arithmetic are gs_distinct_seq.hpp's;
+// the tile count and the rank inside a tile are gs_scan.hpp's.
 //
 // Concurrency (gs_device.hpp's rules). Correctness never depends on a plain load being fresh: a
 // key changes once, EMPTY -> k, by 64-bit CAS, and a stale EMPTY is settled by the CAS's
@@ -32,27 +34,17 @@
 //     list's fill, a sort payload against the row count, before any is used as an index;
 //   * tile kernels handle kDistPer positions per thread, each tested against the count; a flag
 //     word is read inside the flag array's whole tiles (the flag kernels wrote all of them);
-//   * the scan runs over the tile count in steps of its workgroup size;
 //   * every output row is tested against the capacity of its array before the store.
 // No workgroup waits on another. No kernel reads what another workgroup of the same launch
 // writes, except through the atomics above (the write kernels set ranks that only later
 // launches read).
 #include "gs_distinct.hpp"
 #include "gs_distinct_seq.hpp"
+#include "gs_scan.hpp"
 #include "gs_sort.hpp"
 
 namespace gs {
 namespace {
-
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x) {
-  const uint32_t lane = threadIdx.x & 63u;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t y = __shfl_up(x, o, 64);
-    if ((int)lane >= o) x += y;
-  }
-  return x;
-}
 
 __device__ __forceinline__ void load_vslot(const DistVSlot* p, int64_t& id, uint32_t& rank, uint32_t& stamp) {
   const uint4 v = *reinterpret_cast<const uint4*>(p);  // one 16-byte load: key and payload together
@@ -242,8 +234,6 @@ __global__ __launch_bounds__(kDistBS) void k_dist_flag(const uint32_t* __restric
                                                        uint8_t* __restrict__ flags, uint64_t flag_cap,
                                                        uint32_t* __restrict__ tcount) {
   __shared__ uint32_t total;
-  if (threadIdx.x == 0) total = 0;
-  __syncthreads();
   uint32_t cnt = 0;
 #pragma unroll
   for (uint32_t k = 0; k < kDistPer; ++k) {
@@ -267,54 +257,7 @@ __global__ __launch_bounds__(kDistBS) void k_dist_flag(const uint32_t* __restric
     if (i < flag_cap) flags[i] = keep ? 1 : 0;
     cnt += keep ? 1u : 0u;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
-  if ((threadIdx.x & 63u) == 0 && cnt) atomicAdd(&total, cnt);
-  __syncthreads();
-  if (threadIdx.x == 0) tcount[blockIdx.x] = total;
-}
-
-constexpr uint32_t kDistScanBS = 1024;
-
-// tb[0 .. nt) -> their exclusive scan, tb[nt] = ctl[word] = the sum
-__global__ __launch_bounds__(kDistScanBS) void k_dist_scan(uint32_t* __restrict__ tb, uint64_t nt,
-                                                           unsigned long long* __restrict__ ctl, int word) {
-  __shared__ uint32_t ws[kDistScanBS / 64];
-  const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
-  uint32_t carry = 0;
-  for (uint64_t c0 = 0; c0 < nt; c0 += kDistScanBS) {
-    const uint64_t i = c0 + threadIdx.x;
-    const uint32_t x = i < nt ? tb[i] : 0;
-    const uint32_t inc = wave_incl_scan(x);
-    if (lane == 63) ws[wid] = inc;
-    __syncthreads();
-    uint32_t wbase = 0, total = 0;
-#pragma unroll
-    for (uint32_t q = 0; q < kDistScanBS / 64; ++q) {
-      if (q < wid) wbase += ws[q];
-      total += ws[q];
-    }
-    if (i < nt) tb[i] = carry + wbase + inc - x;
-    carry += total;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    tb[nt] = carry;
-    ctl[word] = carry;
-  }
-}
-
-// the output row of the thread's first kept position: kept before the tile + before the thread
-__device__ __forceinline__ uint64_t write_row(const uint32_t* tbase, uint32_t cnt, uint32_t* wsum) {
-  const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
-  const uint32_t inc = wave_incl_scan(cnt);
-  if (lane == 63) wsum[wid] = inc;
-  __syncthreads();
-  uint32_t wbase = 0;
-#pragma unroll
-  for (uint32_t q = 0; q < kDistBS / 64; ++q)
-    if (q < wid) wbase += wsum[q];
-  return dist_out_row(tbase[blockIdx.x], wbase + (inc - cnt));
+  block_count_to<kDistBS>(cnt, &total, tcount + blockIdx.x);
 }
 
 __global__ __launch_bounds__(kDistBS) void k_dist_vwrite(const uint8_t* __restrict__ flags,
@@ -327,7 +270,7 @@ __global__ __launch_bounds__(kDistBS) void k_dist_vwrite(const uint8_t* __restri
   __shared__ uint32_t wsum[kDistBS / 64];
   const uint64_t i0 = dist_write_first(blockIdx.x, DISTINCT_TILE, kDistPer, threadIdx.x);
   const uint64_t fw = *reinterpret_cast<const uint64_t*>(flags + i0);  // inside the whole tiles
-  uint64_t row = write_row(tbase, (uint32_t)__popcll(fw), wsum);
+  uint64_t row = dist_out_row(tbase[blockIdx.x], block_excl_scan<kDistBS>((uint32_t)__popcll(fw), wsum));
 #pragma unroll
   for (uint32_t k = 0; k < kDistPer; ++k) {
     if ((fw >> (8 * k)) & 1ull) {
@@ -352,7 +295,7 @@ __global__ __launch_bounds__(kDistBS) void k_dist_ewrite(const uint8_t* __restri
   __shared__ uint32_t wsum[kDistBS / 64];
   const uint64_t i0 = dist_write_first(blockIdx.x, DISTINCT_TILE, kDistPer, threadIdx.x);
   const uint64_t fw = *reinterpret_cast<const uint64_t*>(flags + i0);
-  uint64_t row = write_row(tbase, (uint32_t)__popcll(fw), wsum);
+  uint64_t row = dist_out_row(tbase[blockIdx.x], block_excl_scan<kDistBS>((uint32_t)__popcll(fw), wsum));
 #pragma unroll
   for (uint32_t k = 0; k < kDistPer; ++k) {
     if ((fw >> (8 * k)) & 1ull) {
@@ -555,7 +498,7 @@ void launch_dist_vertices(const int64_t* src, const int64_t* dst, uint64_t n, ui
   hipLaunchKernelGGL(k_dist_flag<true>, dim3((uint32_t)nt), dim3(kDistBS), 0, st, (const uint32_t*)vslot, entries,
                      (uint64_t)0, (const DistVSlot*)vt.tab, (const DistESlot*)nullptr, (uint64_t)vt.cap + 1, flags,
                      nt * DISTINCT_TILE, tbase);
-  hipLaunchKernelGGL(k_dist_scan, dim3(1), dim3(kDistScanBS), 0, st, tbase, nt, ctl, (int)DIST_NEW_V);
+  launch_tile_scan(tbase, nt, ctl + DIST_NEW_V, st);
   hipLaunchKernelGGL(k_dist_vwrite, dim3((uint32_t)nt), dim3(kDistBS), 0, st, (const uint8_t*)flags,
                      (const uint32_t*)tbase, src, dst, entries, stride, (const uint32_t*)vslot, vt, v0, vid, vid_cap,
                      entry);
@@ -571,7 +514,7 @@ void launch_dist_edges(uint64_t n, uint64_t folded, int mode, const DistVTable& 
   hipLaunchKernelGGL(k_dist_flag<false>, dim3((uint32_t)nt), dim3(kDistBS), 0, st, (const uint32_t*)eslot, n, folded,
                      (const DistVSlot*)nullptr, (const DistESlot*)et.tab, (uint64_t)et.cap, flags, nt * DISTINCT_TILE,
                      tbase);
-  hipLaunchKernelGGL(k_dist_scan, dim3(1), dim3(kDistScanBS), 0, st, tbase, nt, ctl, (int)DIST_NEW_E);
+  launch_tile_scan(tbase, nt, ctl + DIST_NEW_E, st);
   hipLaunchKernelGGL(k_dist_ewrite, dim3((uint32_t)nt), dim3(kDistBS), 0, st, (const uint8_t*)flags,
                      (const uint32_t*)tbase, n, index);
 }

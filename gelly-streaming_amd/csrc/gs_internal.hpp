@@ -1,6 +1,8 @@
 // gs_internal.hpp -- the summary handle and the internal entry points shared by
 // gs_capi.cpp (include/gs_summary.h), gs_group.cpp (include/gs_group.h),
-// gs_changes.cpp (per-window change emission), gs_degree.cpp, gs_triangle.cpp and gs_sort.cpp.
+// gs_changes.cpp (per-window change emission), gs_degree.cpp, gs_triangle.cpp and gs_sort.cpp;
+// the phase timer and the stream owner of the handles with one stream of their own
+// (gs_slice.cpp, gs_triangle.cpp, gs_distinct.cpp).
 // Every device array a handle owns is a DevBuf (gs_devbuf.hpp): deleting the handle frees it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -94,6 +96,111 @@ struct DeviceGuard {
     if (prev >= 0) (void)hipSetDevice(prev);
   }
 };
+
+// Times up to kMaxPhases consecutive phases of a call with events on its stream when `on`
+// (a profiling knob of gs_testing.h); does nothing otherwise. Event i ends phase i - 1 and
+// begins phase i. finish() waits for the stream and sets all `phases` words of phase_us:
+// microseconds for a phase whose two events were recorded, zero for one that did not run.
+struct PhaseTimer {
+  static constexpr int kMaxPhases = 5;
+  hipStream_t st;
+  bool on;
+  uint64_t* us;
+  int phases;
+  hipEvent_t ev[kMaxPhases + 1] = {};
+  uint32_t recorded = 0;  // bit i: event i
+  PhaseTimer(hipStream_t stream, bool enable, uint64_t* phase_us, int n)
+      : st(stream), on(enable && n <= kMaxPhases), us(phase_us), phases(n) {
+    for (int i = 0; on && i <= phases; ++i)
+      if (hipEventCreate(&ev[i]) != hipSuccess) on = false;
+  }
+  PhaseTimer(const PhaseTimer&) = delete;
+  PhaseTimer& operator=(const PhaseTimer&) = delete;
+  // event i for a launcher that records it between two of its own kernels (null when off)
+  hipEvent_t event(int i) {
+    if (!on) return nullptr;
+    recorded |= 1u << i;
+    return ev[i];
+  }
+  void mark(int i) {
+    if (on) (void)hipEventRecord(event(i), st);
+  }
+  void finish() {
+    if (!on) return;
+    (void)hipStreamSynchronize(st);
+    for (int i = 0; i < phases; ++i) {
+      float ms = 0;
+      const bool ran = ((recorded >> i) & 3u) == 3u && hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess;
+      us[i] = ran ? (uint64_t)(ms * 1000.0f) : 0;
+    }
+  }
+  ~PhaseTimer() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+
+// What a summary that works on one stream of its own owns beside its arrays (the window slices,
+// the triangle summary, the distinct streams; their handles derive from it).
+struct StreamOwner {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  hipEvent_t ext_ev = nullptr;  // *_wait_stream: recorded on a producer's stream
+
+  // work queued on the handle's stream from here on runs after what `producer` holds now
+  int wait_stream(void* producer) {
+    DeviceGuard g(device);
+    hipStream_t st = static_cast<hipStream_t>(producer);
+    if (st == stream) return GS_OK;
+    GS_HIP(hipEventRecord(ext_ev, st));  // (stream 0 = the device's null stream)
+    GS_HIP(hipStreamWaitEvent(stream, ext_ev, 0));
+    return GS_OK;
+  }
+};
+
+inline int check_device_index(int device) {
+  int count = 0;
+  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail(GS_ERR_HIP, "no HIP device available");
+  if (device < 0 || device >= count) return fail(GS_ERR_INVALID, "bad device");
+  return GS_OK;
+}
+
+// Handles of type H, derived from StreamOwner (h may be null).
+template <class H>
+int owner_destroy(H* h) {
+  if (!h) return GS_OK;
+  DeviceGuard g(h->device);
+  if (h->stream) (void)hipStreamSynchronize(h->stream);
+  if (h->ext_ev) (void)hipEventDestroy(h->ext_ev);
+  const hipStream_t stream = h->stream;
+  delete h;  // frees every device buffer (DevBuf members): device current, the stream idle
+  if (stream) (void)hipStreamDestroy(stream);
+  return GS_OK;
+}
+
+// *out = a new handle on `device` (checked with check_device_index before): its stream and
+// event, then init(h) with the device current, then a wait for the stream. A failure destroys
+// the handle and keeps the failure's message.
+template <class H, class Init>
+int owner_create(H** out, int device, Init init) {
+  DeviceGuard g(device);
+  H* h = new H();
+  h->device = device;
+  const int rc = [&]() -> int {
+    GS_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    GS_HIP(hipEventCreateWithFlags(&h->ext_ev, hipEventDisableTiming));
+    if (int r = init(h)) return r;
+    GS_HIP(hipStreamSynchronize(h->stream));
+    return GS_OK;
+  }();
+  if (rc) {
+    const std::string msg = gs_last_error();
+    (void)owner_destroy(h);
+    return fail(rc, msg);
+  }
+  *out = h;
+  return GS_OK;
+}
 
 }  // namespace gsi
 

@@ -18,10 +18,7 @@
 
 using namespace gsi;
 
-struct gs_slices_s {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ext_ev = nullptr;
+struct gs_slices_s : StreamOwner {
   DevBuf<unsigned long long> ctl;  // gs::SliceCtl words
   // the window's edges, n_cap each (eval is written only by a window with values)
   uint64_t n_cap = 0;
@@ -104,37 +101,10 @@ int ensure_staging(gs_slices_s* s, uint64_t rows) {
   return GS_OK;
 }
 
-// Brackets the phases of a call with events when GS_TESTING_SLICE_PROFILE is 1 (and waits for them).
-struct PhaseTimer {
-  gs_slices_s* s;
-  bool on;
-  hipEvent_t ev[4] = {};
-  int first = -1, marks = 0;
-  explicit PhaseTimer(gs_slices_s* h) : s(h), on(testing_value(GS_TESTING_SLICE_PROFILE, 0) == 1) {
-    for (int i = 0; on && i < 4; ++i)
-      if (hipEventCreate(&ev[i]) != hipSuccess) on = false;
-  }
-  // the work queued until the next mark (or finish) is phase `phase`; phases are consecutive
-  void mark(int phase) {
-    if (!on || marks >= 3) return;
-    if (first < 0) first = phase;
-    (void)hipEventRecord(ev[marks++], s->stream);
-  }
-  void finish() {
-    if (!on || marks == 0) return;
-    (void)hipEventRecord(ev[marks], s->stream);
-    (void)hipStreamSynchronize(s->stream);
-    for (int i = 0; i < marks; ++i) {
-      float ms = 0;
-      s->phase_us[first + i] = 0;
-      if (hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess) s->phase_us[first + i] = (uint64_t)(ms * 1000.0f);
-    }
-  }
-  ~PhaseTimer() {
-    for (int i = 0; i < 4; ++i)
-      if (ev[i]) (void)hipEventDestroy(ev[i]);
-  }
-};
+// a call's timer over `phases` words of s->phase_us from word `first` on
+PhaseTimer phase_timer(gs_slices_s* s, int first, int phases) {
+  return PhaseTimer(s->stream, testing_value(GS_TESTING_SLICE_PROFILE, 0) == 1, s->phase_us + first, phases);
+}
 
 void set_empty(gs_slices_s* s, int dir) {
   s->n = s->entries = s->nv = 0;
@@ -159,14 +129,14 @@ int window_impl(gs_slices_s* s, const int64_t* src, const int64_t* dst, const in
                 uint64_t stride, int dir) {
   const uint64_t entries = gs::slice_entries(n, dir);
   set_empty(s, dir);  // (a failure below leaves an empty window)
-  PhaseTimer timer(s);
+  PhaseTimer timer = phase_timer(s, PH_EXPAND, 3);
   timer.mark(PH_EXPAND);
   gs::launch_slice_expand(src, dst, val, n, stride, dir, s->esrc, s->edst, s->eval, s->kid, s->stream);
   GS_HIP(hipGetLastError());
   timer.mark(PH_SORT);
   uint32_t* const sctl = s->sort.ctl;
   GS_HIP(hipMemsetAsync(sctl, 0, gs::kSortCtlWords * 4, s->stream));
-  gs::launch_slice_digits(s->kid, entries, sctl, s->stream);  // rows 0..7: the keys
+  gs::launch_sort_digits_one(s->kid, entries, sctl, s->stream);  // rows 0..7: the keys
   GS_HIP(hipGetLastError());
   gs::SortSrc cur;  // (pay null: payload i of entry i is i)
   int side = 0;
@@ -179,6 +149,7 @@ int window_impl(gs_slices_s* s, const int64_t* src, const int64_t* dst, const in
   unsigned long long nv = 0;
   GS_HIP(hipMemcpyAsync(&nv, s->ctl + gs::SLICE_NV, 8, hipMemcpyDeviceToHost, s->stream));
   GS_HIP(hipStreamSynchronize(s->stream));
+  timer.mark(PH_HEADS + 1);
   timer.finish();
   if (nv == 0 || nv > entries) return fail(GS_ERR_HIP, "slice window: vertex count out of range");
   s->n = n;
@@ -203,8 +174,8 @@ int reduce_impl(gs_slices_s* s, int op, int64_t* v, int64_t* out, size_t cap, si
     if (int rc = ensure_staging(s, s->nv)) return rc;
     dout = s->o_a;
   }
-  PhaseTimer timer(s);
-  timer.mark(PH_REDUCE);
+  PhaseTimer timer = phase_timer(s, PH_REDUCE, 1);
+  timer.mark(0);
   if (op == GS_SLICE_COUNT) {
     gs::launch_slice_count(s->off, s->nv, dout, s->stream);
   } else {
@@ -213,6 +184,7 @@ int reduce_impl(gs_slices_s* s, int op, int64_t* v, int64_t* out, size_t cap, si
     s->reduce_tiles = gs::slice_tiles(s->entries, gs::SLICE_TILE);
   }
   GS_HIP(hipGetLastError());
+  timer.mark(1);
   timer.finish();
   GS_HIP(hipMemcpyAsync(v, s->vtx, s->nv * 8, to_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, s->stream));
   if (to_host) {
@@ -243,11 +215,12 @@ int neighborhoods_impl(gs_slices_s* s, int64_t* v, uint64_t* offset, int64_t* ne
     dn = s->o_a;
     dv = val ? s->o_b.get() : nullptr;
   }
-  PhaseTimer timer(s);
-  timer.mark(PH_GATHER);
+  PhaseTimer timer = phase_timer(s, PH_GATHER, 1);
+  timer.mark(0);
   gs::launch_slice_gather(s->spay, s->entries, s->n, s->dir, s->esrc, s->edst, s->eval, dn, dv, s->entries,
                           s->stream);
   GS_HIP(hipGetLastError());
+  timer.mark(1);
   timer.finish();
   const hipMemcpyKind kind = to_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
   GS_HIP(hipMemcpyAsync(v, s->vtx, s->nv * 8, kind, s->stream));
@@ -264,45 +237,18 @@ int neighborhoods_impl(gs_slices_s* s, int64_t* v, uint64_t* offset, int64_t* ne
 
 extern "C" {
 
-int gs_slice_destroy(gs_slices s) {
-  if (!s) return GS_OK;
-  DeviceGuard g(s->device);
-  if (s->stream) (void)hipStreamSynchronize(s->stream);
-  if (s->ext_ev) (void)hipEventDestroy(s->ext_ev);
-  const hipStream_t stream = s->stream;
-  delete s;  // frees every device buffer (DevBuf members): device current, the stream idle
-  if (stream) (void)hipStreamDestroy(stream);
-  return GS_OK;
-}
+int gs_slice_destroy(gs_slices s) { return owner_destroy(s); }
 
 int gs_slice_create(gs_slices* out, int device, uint64_t edge_hint) {
   if (!out) return fail(GS_ERR_INVALID, "out is null");
   *out = nullptr;
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail(GS_ERR_HIP, "no HIP device available");
-  if (device < 0 || device >= count) return fail(GS_ERR_INVALID, "bad device");
+  if (int rc = check_device_index(device)) return rc;
   if (edge_hint > kSliceMaxEntries) return fail(GS_ERR_CAPACITY, "edge hint beyond 2^32 - 1 entries");
-  DeviceGuard g(device);
-  gs_slices_s* s = new gs_slices_s();
-  s->device = device;
-  auto body = [&]() -> int {
-    GS_HIP(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-    GS_HIP(hipEventCreateWithFlags(&s->ext_ev, hipEventDisableTiming));
+  return owner_create(out, device, [&](gs_slices_s* s) -> int {
     GS_HIP(s->ctl.alloc(gs::SLICE_CTL_WORDS));
     GS_HIP(hipMemsetAsync(s->ctl, 0, gs::SLICE_CTL_WORDS * 8, s->stream));
-    if (edge_hint)
-      if (int r = ensure_window(s, edge_hint, edge_hint)) return r;
-    GS_HIP(hipStreamSynchronize(s->stream));
-    return GS_OK;
-  };
-  const int rc = body();
-  if (rc) {
-    const std::string msg = gs_last_error();
-    (void)gs_slice_destroy(s);
-    return fail(rc, msg);
-  }
-  *out = s;
-  return GS_OK;
+    return edge_hint ? ensure_window(s, edge_hint, edge_hint) : GS_OK;
+  });
 }
 
 int gs_slice_window_device(gs_slices s, const int64_t* src, const int64_t* dst, const int64_t* val, size_t n,
@@ -389,12 +335,7 @@ int gs_slice_get_stream(gs_slices s, void** stream) {
 
 int gs_slice_wait_stream(gs_slices s, void* stream) {
   if (int rc = check_slice(s)) return rc;
-  DeviceGuard g(s->device);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (st == s->stream) return GS_OK;
-  GS_HIP(hipEventRecord(s->ext_ev, st));  // (stream 0 = the device's null stream)
-  GS_HIP(hipStreamWaitEvent(s->stream, s->ext_ev, 0));
-  return GS_OK;
+  return s->wait_stream(stream);
 }
 
 // gs_testing.h: out[0] = tiles of the last reduce (0: none, or only the count op), out[1] = tiles

@@ -1,7 +1,8 @@
 // gs_slice.hpp -- host-side launchers of the window slices' kernels (gs_slice_k.hip): expand a
 // window of (src, dst, value) into keyed entries, find the heads of the sorted entries and
 // write the vertices and offsets, reduce the values of every neighbourhood in one pass, and
-// gather neighbours and values into sorted order. The sort in between is gs_sort.hpp's. Every
+// gather neighbours and values into sorted order. The sort in between, its one-column digit
+// histogram and the scan of the tile counts are gs_sort.hpp's. Every
 // launch is queued on the given stream; kernel boundaries carry all ordering between
 // workgroups (no workgroup waits on another inside a launch).
 //
@@ -39,10 +40,6 @@ enum SliceCtl : int {
 // (the edges are in place already), the edges into esrc / edst / eval.
 void launch_slice_expand(const int64_t* src, const int64_t* dst, const int64_t* val, uint64_t n, uint64_t stride,
                          int dir, int64_t* esrc, int64_t* edst, int64_t* eval, int64_t* kid, hipStream_t st);
-// ctl[0 .. 8 * 256) += the digit histograms of the entry keys (rows 0..7 of the sort's control
-// words, the `hist` of sort_run); ctl must be zero before. One key column: launch_sort_digits
-// builds two, and every workgroup of either ends with one global add per bin.
-void launch_slice_digits(const int64_t* kid, uint64_t entries, uint32_t* ctl, hipStream_t st);
 // Over E sorted keys: flags[i] = position i is a head (whole tiles are written, 0 from E on),
 // tbase[t] = heads before tile t and tbase[tiles] = ctl[SLICE_NV] = all heads; vtx / off =
 // the vertices and the first position of each, off[heads] = E. Writes are bounded by cap_v heads.

@@ -1,10 +1,9 @@
 // gs_slice_k.hip -- kernels of the window slices (gfx950).
 //
 //   k_slice_expand : edges -> entry keys (and the handle's copy of the edges)
-//   k_slice_digits : the histograms of all 8 digits of the entry keys, for the sort
 //   k_slice_flag   : over the sorted keys: one head flag byte per position, heads per tile
-//   k_slice_scan   : exclusive scan of the tile counts (one workgroup); the vertex count
-//   k_slice_write  : the heads in order: vertex[] and offset[]
+//   k_slice_write  : the heads in order: vertex[] and offset[]; between the two, the sort's
+//                    launch_tile_scan turns the tile counts into tile bases and the vertex count
 //   k_slice_reduce : the hot kernel. A workgroup takes a tile of SLICE_TILE sorted positions,
 //                    a thread kSlicePer consecutive ones: it gathers their values through the
 //                    payload, combines its own run serially, the wave scans the threads'
@@ -16,34 +15,25 @@
 //                    began in an earlier tile ends
 //   k_slice_count / k_slice_gather / k_slice_stats : the COUNT op, the neighbourhood export,
 //                    the diagnostics
-// The segmented-combine operator and all tile / carry index arithmetic are gs_slice_seg.hpp's.
+// The segmented-combine operator and all tile / carry index arithmetic are gs_slice_seg.hpp's;
+// the tile count and the rank inside a tile are gs_scan.hpp's.
 //
 // What bounds every loop:
 //   * per-element kernels handle one element per thread, its index tested against the count;
 //   * tile kernels handle kSlicePer positions per thread, each tested against the entry count;
 //     a flag word is read inside the flag array's whole tiles (k_slice_flag wrote all of them);
-//   * the two scans run over the tile count in steps of their workgroup size; the digit
-//     histogram strides over the entries, each index tested against their count;
+//   * the carry scan runs over the tile count in steps of its workgroup size;
 //   * a payload is tested against the entry count, the edge it names against the edge count,
 //     before either is used as an index;
 //   * every output position is tested against the capacity of its array before the store.
 // No kernel reads what another workgroup of the same launch writes.
+#include "gs_scan.hpp"
 #include "gs_slice.hpp"
 #include "gs_slice_seg.hpp"
 #include "gs_sort.hpp"
 
 namespace gs {
 namespace {
-
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x) {
-  const uint32_t lane = threadIdx.x & 63u;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t y = __shfl_up(x, o, 64);
-    if ((int)lane >= o) x += y;
-  }
-  return x;
-}
 
 __device__ __forceinline__ SegPair seg_shfl_up(const SegPair& p, int o) {
   SegPair r;
@@ -98,57 +88,10 @@ __global__ __launch_bounds__(kSliceBS) void k_slice_expand(const int64_t* src, c
   }
 }
 
-// LDS histogram add of a whole wave (every lane calls it), as gs_sort_k.hip's: a wave whose
-// valid lanes all hold one digit adds once instead of 64 times to one address.
-__device__ __forceinline__ void digit_add(uint32_t* h, uint32_t d, bool valid) {
-  const unsigned long long m = __ballot(valid);
-  if (!m) return;  // wave-uniform
-  const int first = __ffsll((long long)m) - 1;
-  const uint32_t d0 = (uint32_t)__shfl((int)d, first, 64);
-  if (__ballot(valid && d != d0) == 0ull) {
-    if ((int)(threadIdx.x & 63) == first) atomicAdd(&h[d0], (uint32_t)__popcll(m));
-  } else if (valid) {
-    atomicAdd(&h[d], 1u);
-  }
-}
-
-constexpr uint32_t kSliceDigitBins = kSortPasses * kSortRadix;  // the eight 256-bin rows of one key column
-constexpr uint32_t kSliceDigitsPer = 4;                         // keys per thread and iteration
-constexpr uint32_t kSliceDigitBlocks = 256;  // at most: every workgroup ends with one global add per bin
-
-// ctl[0 .. kSliceDigitBins) += the histograms of all 8 digits of the entry keys (ctl zero before)
-__global__ __launch_bounds__(kSliceBS) void k_slice_digits(const int64_t* __restrict__ kid, uint64_t entries,
-                                                           uint32_t* __restrict__ ctl) {
-  __shared__ uint32_t h[kSliceDigitBins];
-  for (uint32_t k = threadIdx.x; k < kSliceDigitBins; k += kSliceBS) h[k] = 0;
-  __syncthreads();
-  const uint64_t step = (uint64_t)gridDim.x * (kSliceBS * kSliceDigitsPer);
-  for (uint64_t base = (uint64_t)blockIdx.x * (kSliceBS * kSliceDigitsPer); base < entries; base += step) {
-    unsigned long long key[kSliceDigitsPer];
-#pragma unroll
-    for (uint32_t j = 0; j < kSliceDigitsPer; ++j) {  // the loads of an iteration in flight together
-      const uint64_t i = base + j * kSliceBS + threadIdx.x;
-      key[j] = i < entries ? (unsigned long long)kid[i] ^ kSortSignBit : 0ull;
-    }
-#pragma unroll
-    for (uint32_t j = 0; j < kSliceDigitsPer; ++j) {
-      const bool valid = base + j * kSliceBS + threadIdx.x < entries;
-#pragma unroll
-      for (uint32_t p = 0; p < kSortPasses; ++p)
-        digit_add(h + p * kSortRadix, (uint32_t)(key[j] >> (8 * p)) & 255u, valid);
-    }
-  }
-  __syncthreads();
-  for (uint32_t k = threadIdx.x; k < kSliceDigitBins; k += kSliceBS)
-    if (h[k]) atomicAdd(&ctl[k], h[k]);
-}
-
 __global__ __launch_bounds__(kSliceBS) void k_slice_flag(const unsigned long long* __restrict__ key, uint64_t entries,
                                                          uint8_t* __restrict__ flags, uint64_t flag_cap,
                                                          uint32_t* __restrict__ tcount) {
   __shared__ uint32_t total;
-  if (threadIdx.x == 0) total = 0;
-  __syncthreads();
   const uint64_t base = slice_tile_begin(blockIdx.x, SLICE_TILE);
   uint32_t cnt = 0;
 #pragma unroll
@@ -159,41 +102,7 @@ __global__ __launch_bounds__(kSliceBS) void k_slice_flag(const unsigned long lon
     if (i < flag_cap) flags[i] = head ? 1 : 0;
     cnt += head ? 1u : 0u;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
-  if ((threadIdx.x & 63u) == 0 && cnt) atomicAdd(&total, cnt);
-  __syncthreads();
-  if (threadIdx.x == 0) tcount[blockIdx.x] = total;
-}
-
-constexpr uint32_t kSliceScanBS = 1024;
-
-// tb[0 .. nt) -> their exclusive scan, tb[nt] = ctl[SLICE_NV] = the sum
-__global__ __launch_bounds__(kSliceScanBS) void k_slice_scan(uint32_t* __restrict__ tb, uint64_t nt,
-                                                             unsigned long long* __restrict__ ctl) {
-  __shared__ uint32_t ws[kSliceScanBS / 64];
-  const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
-  uint32_t carry = 0;
-  for (uint64_t c0 = 0; c0 < nt; c0 += kSliceScanBS) {
-    const uint64_t i = c0 + threadIdx.x;
-    const uint32_t x = i < nt ? tb[i] : 0;
-    const uint32_t inc = wave_incl_scan(x);
-    if (lane == 63) ws[wid] = inc;
-    __syncthreads();
-    uint32_t wbase = 0, total = 0;
-#pragma unroll
-    for (uint32_t q = 0; q < kSliceScanBS / 64; ++q) {
-      if (q < wid) wbase += ws[q];
-      total += ws[q];
-    }
-    if (i < nt) tb[i] = carry + wbase + inc - x;
-    carry += total;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    tb[nt] = carry;
-    ctl[SLICE_NV] = carry;
-  }
+  block_count_to<kSliceBS>(cnt, &total, tcount + blockIdx.x);
 }
 
 // the 8 flag bytes of the thread's positions i0 .. i0 + 7 (i0 a multiple of 8 inside the whole
@@ -207,18 +116,9 @@ __global__ __launch_bounds__(kSliceBS) void k_slice_write(const uint8_t* __restr
                                                           const uint32_t* __restrict__ tbase, int64_t* __restrict__ vtx,
                                                           unsigned long long* __restrict__ off, uint64_t cap_v) {
   __shared__ uint32_t wsum[kSliceBS / 64];
-  const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
   const uint64_t i0 = slice_tile_begin(blockIdx.x, SLICE_TILE) + (uint64_t)threadIdx.x * kSlicePer;
   const uint64_t fw = flag_word(flags, i0);
-  const uint32_t cnt = (uint32_t)__popcll(fw);
-  const uint32_t inc = wave_incl_scan(cnt);
-  if (lane == 63) wsum[wid] = inc;
-  __syncthreads();
-  uint32_t wbase = 0;
-#pragma unroll
-  for (uint32_t q = 0; q < kSliceBS / 64; ++q)
-    if (q < wid) wbase += wsum[q];
-  uint64_t pos = (uint64_t)tbase[blockIdx.x] + wbase + (inc - cnt);
+  uint64_t pos = (uint64_t)tbase[blockIdx.x] + block_excl_scan<kSliceBS>((uint32_t)__popcll(fw), wsum);
 #pragma unroll
   for (uint32_t k = 0; k < kSlicePer; ++k) {
     if ((fw >> (8 * k)) & 1ull) {
@@ -399,19 +299,13 @@ void launch_slice_expand(const int64_t* src, const int64_t* dst, const int64_t* 
                      src == esrc ? 0 : 1, esrc, edst, eval, kid);
 }
 
-void launch_slice_digits(const int64_t* kid, uint64_t entries, uint32_t* ctl, hipStream_t st) {
-  const uint64_t tiles = (entries + kSliceBS * kSliceDigitsPer - 1) / (kSliceBS * kSliceDigitsPer);
-  const uint32_t grid = (uint32_t)(tiles < kSliceDigitBlocks ? (tiles ? tiles : 1) : kSliceDigitBlocks);
-  hipLaunchKernelGGL(k_slice_digits, dim3(grid), dim3(kSliceBS), 0, st, kid, entries, ctl);
-}
-
 void launch_slice_heads(const unsigned long long* key, uint64_t entries, uint8_t* flags, uint32_t* tbase,
                         unsigned long long* ctl, int64_t* vtx, unsigned long long* off, uint64_t cap_v,
                         hipStream_t st) {
   const uint64_t nt = slice_tiles(entries, SLICE_TILE);
   hipLaunchKernelGGL(k_slice_flag, dim3((uint32_t)nt), dim3(kSliceBS), 0, st, key, entries, flags, nt * SLICE_TILE,
                      tbase);
-  hipLaunchKernelGGL(k_slice_scan, dim3(1), dim3(kSliceScanBS), 0, st, tbase, nt, ctl);
+  launch_tile_scan(tbase, nt, ctl + SLICE_NV, st);
   hipLaunchKernelGGL(k_slice_write, dim3((uint32_t)nt), dim3(kSliceBS), 0, st, (const uint8_t*)flags, key, entries,
                      (const uint32_t*)tbase, vtx, off, cap_v);
 }

@@ -1,7 +1,9 @@
 // gs_sort.hpp -- host-side launchers of the grouped component export's kernels
 // (gs_sort_k.hip): a stable LSD radix sort of (uint64 key, uint32 payload) pairs with
 // 8-bit digits, and the tail that turns rows sorted by (label, vertex) into the CSR of
-// gs_export_components*. Every launch is queued on the given stream; kernel boundaries
+// gs_export_components*; beside them the two launches every summary with a sort or a compaction
+// shares: the one-column digit histogram and the scan of tile counts (the device side of the
+// flag / scan / compact idiom is gs_scan.hpp). Every launch is queued on the given stream; kernel boundaries
 // carry all ordering between workgroups (no workgroup waits on another inside a launch).
 // The host part at the end (gs_sort.cpp) owns the sort's scratch and drives its passes for
 // every caller: the component export, the degree exports, the triangle fold and the window slices.
@@ -18,7 +20,8 @@ constexpr uint32_t kSortItems = 8;                        // pairs per thread
 constexpr uint32_t kSortTile = kSortBS * kSortItems;      // pairs per workgroup (gs_sort_tile)
 constexpr uint32_t kSortRadix = 256;                      // 8-bit digits
 constexpr uint32_t kSortPasses = 8;                       // digits of a 64-bit key
-constexpr uint32_t kSortScanBS = 1024;                    // threads of a k_sort_scan workgroup (4 entries each)
+constexpr uint32_t kSortScanBS = 1024;                    // threads of a k_sort_scan (4 entries each) / k_tile_scan
+                                                          // (one tile count each) workgroup: gsamd.TILE_SCAN_BLOCK
 constexpr uint32_t kCompTile = 1024;                      // rows per k_comp_heads / k_comp_write workgroup
 constexpr unsigned long long kSortSignBit = 1ull << 63;   // key = id ^ sign bit: unsigned digit order = signed order
 
@@ -45,6 +48,13 @@ struct SortSrc {
 // ctl[0 .. kSortCtlRoots) += digit histograms of v (rows 0..7) and label (rows 8..15);
 // ctl[kSortCtlRoots] += rows with v == label. ctl must be zero before.
 void launch_sort_digits(const int64_t* v, const int64_t* label, uint64_t n, uint32_t* ctl, hipStream_t st);
+// ctl[0 .. 8 * 256) += the digit histograms of one key column (rows 0..7 of the control words,
+// the `hist` of sort_run); ctl must be zero before. launch_sort_digits builds two columns, and
+// every workgroup of either ends with one global add per bin.
+void launch_sort_digits_one(const int64_t* key, uint64_t n, uint32_t* ctl, hipStream_t st);
+// The scan step of a flag / scan / compact pass (gs_scan.hpp), one workgroup: the tile counts
+// tb[0 .. nt) become their exclusive scan, tb[nt] = *total = their sum (below 2^32).
+void launch_tile_scan(uint32_t* tb, uint64_t nt, unsigned long long* total, hipStream_t st);
 // rows with v == label added into *out (gs_num_components)
 void launch_comp_roots(const int64_t* v, const int64_t* label, uint64_t n, unsigned long long* out, hipStream_t st);
 

@@ -14,10 +14,16 @@
 //                    orders the workgroups.
 //   k_comp_roots   : rows with v == label (gs_num_components; no sort).
 //   k_comp_heads / k_comp_write : the CSR tail over rows sorted by (label, vertex).
+// and two kernels every summary with a sort or a compaction shares:
+//   k_sort_digits_one : the histograms of all 8 digits of one key column (the window slices,
+//                    the distinct streams' edge export).
+//   k_tile_scan    : exclusive scan of the tile counts of a flag / scan / compact pass, one
+//                    workgroup; the wave and workgroup scans are gs_scan.hpp's.
 //
 // A pass is three launches; kernel boundaries give all ordering between workgroups, so no
 // workgroup waits on another and nothing relies on coherence between the per-XCD L2s
 // inside a launch. Keys are id ^ 2^63: unsigned digit order is signed id order.
+#include "gs_scan.hpp"
 #include "gs_sort.hpp"
 
 namespace gs {
@@ -82,6 +88,36 @@ __global__ __launch_bounds__(256) void k_sort_digits(const int64_t* __restrict__
   if (threadIdx.x == 0 && roots) atomicAdd(&ctl[kSortCtlRoots], roots);
 }
 
+constexpr uint32_t kDigitsOneBins = kSortPasses * kSortRadix;  // the eight 256-bin rows of one key column
+constexpr uint32_t kDigitsOneBlocks = 256;  // at most: every workgroup ends with one global add per bin
+
+// ctl[0 .. kDigitsOneBins) += the histograms of all 8 digits of the keys (ctl zero before)
+__global__ __launch_bounds__(256) void k_sort_digits_one(const int64_t* __restrict__ id, uint64_t n,
+                                                         uint32_t* __restrict__ ctl) {
+  __shared__ uint32_t h[kDigitsOneBins];
+  for (uint32_t k = threadIdx.x; k < kDigitsOneBins; k += 256) h[k] = 0;
+  __syncthreads();
+  const uint64_t step = (uint64_t)gridDim.x * (256 * kDigitsPer);
+  for (uint64_t base = (uint64_t)blockIdx.x * (256 * kDigitsPer); base < n; base += step) {
+    unsigned long long key[kDigitsPer];
+#pragma unroll
+    for (uint32_t j = 0; j < kDigitsPer; ++j) {  // the loads of an iteration in flight together
+      const uint64_t i = base + j * 256 + threadIdx.x;
+      key[j] = i < n ? (unsigned long long)id[i] ^ kSortSignBit : 0ull;
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < kDigitsPer; ++j) {
+      const bool valid = base + j * 256 + threadIdx.x < n;
+#pragma unroll
+      for (uint32_t p = 0; p < kSortPasses; ++p)
+        hist_add(h + p * kSortRadix, (uint32_t)(key[j] >> (8 * p)) & 255u, valid);
+    }
+  }
+  __syncthreads();
+  for (uint32_t k = threadIdx.x; k < kDigitsOneBins; k += 256)
+    if (h[k]) atomicAdd(&ctl[k], h[k]);
+}
+
 __global__ __launch_bounds__(256) void k_comp_roots(const int64_t* __restrict__ v, const int64_t* __restrict__ l,
                                                     uint64_t n, unsigned long long* __restrict__ out) {
   __shared__ uint32_t roots;
@@ -126,9 +162,9 @@ __global__ __launch_bounds__(kSortScanBS) void k_sort_scan(uint32_t* __restrict_
                                                            uint64_t stride, const uint32_t* __restrict__ ghist) {
   __shared__ uint32_t ws[kSortScanBS / 64];
   __shared__ uint32_t base_sh;
-  const uint32_t lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const uint32_t lane = threadIdx.x & 63;
   const uint32_t d = blockIdx.x;
-  if (wid == 0) {
+  if (threadIdx.x < 64) {
     uint32_t x = 0;
     if (ghist)
       for (uint32_t k = lane * 4; k < lane * 4 + 4; ++k)
@@ -148,29 +184,41 @@ __global__ __launch_bounds__(kSortScanBS) void k_sort_scan(uint32_t* __restrict_
     if (c + 1 >= entries) x.y = 0;
     if (c + 2 >= entries) x.z = 0;
     if (c + 3 >= entries) x.w = 0;
-    const uint32_t sum = x.x + x.y + x.z + x.w;
-    uint32_t inc = sum;
+    const uint32_t before = block_excl_scan<kSortScanBS>(x.x + x.y + x.z + x.w, ws);
+    uint32_t total = 0;
 #pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t y = __shfl_up(inc, o, 64);
-      if ((int)lane >= o) inc += y;
-    }
-    if (lane == 63) ws[wid] = inc;
-    __syncthreads();
-    uint32_t wbase = 0, total = 0;
-#pragma unroll
-    for (uint32_t q = 0; q < kSortScanBS / 64; ++q) {
-      if (q < wid) wbase += ws[q];
-      total += ws[q];
-    }
+    for (uint32_t q = 0; q < kSortScanBS / 64; ++q) total += ws[q];
     uint4 o;
-    o.x = carry + wbase + (inc - sum);
+    o.x = carry + before;
     o.y = o.x + x.x;
     o.z = o.y + x.y;
     o.w = o.z + x.z;
     if (c < stride) *reinterpret_cast<uint4*>(row + c) = o;
     carry += total;
     __syncthreads();
+  }
+}
+
+// tb[0 .. nt) -> their exclusive scan, tb[nt] = *total_out = the sum. The carry has 32 bits:
+// the counts are of kept elements, and every caller bounds its elements by 2^32 - 1
+// (kSliceMaxEntries, kTriMaxEntries, 2 kDistMaxFold), so the sum fits.
+__global__ __launch_bounds__(kSortScanBS) void k_tile_scan(uint32_t* __restrict__ tb, uint64_t nt,
+                                                           unsigned long long* __restrict__ total_out) {
+  __shared__ uint32_t ws[kSortScanBS / 64];
+  uint32_t carry = 0;
+  for (uint64_t c0 = 0; c0 < nt; c0 += kSortScanBS) {  // block-uniform
+    const uint64_t i = c0 + threadIdx.x;
+    const uint32_t before = block_excl_scan<kSortScanBS>(i < nt ? tb[i] : 0u, ws);
+    uint32_t total = 0;
+#pragma unroll
+    for (uint32_t q = 0; q < kSortScanBS / 64; ++q) total += ws[q];
+    if (i < nt) tb[i] = carry + before;
+    carry += total;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    tb[nt] = carry;
+    *total_out = carry;
   }
 }
 
@@ -265,17 +313,10 @@ __device__ __forceinline__ uint32_t comp_load(const SortSrc& s, uint64_t n, uint
 
 __global__ __launch_bounds__(256) void k_comp_heads(SortSrc s, uint64_t n, uint32_t* __restrict__ bcount) {
   __shared__ uint32_t total;
-  if (threadIdx.x == 0) total = 0;
-  __syncthreads();
   unsigned long long key[kCompPer];
   uint32_t pay[kCompPer];
   const uint32_t heads = comp_load(s, n, (uint64_t)blockIdx.x * kCompTile + (uint64_t)threadIdx.x * kCompPer, key, pay);
-  uint32_t x = (uint32_t)__popc(heads);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-  if ((threadIdx.x & 63) == 0 && x) atomicAdd(&total, x);
-  __syncthreads();
-  if (threadIdx.x == 0) bcount[blockIdx.x] = total;
+  block_count_to<256>((uint32_t)__popc(heads), &total, bcount + blockIdx.x);
 }
 
 // bbase = the scanned head counts: heads of workgroup b take comp / offset entries from bbase[b]
@@ -286,7 +327,6 @@ __global__ __launch_bounds__(256) void k_comp_write(SortSrc s, uint64_t n, const
                                                     int64_t* __restrict__ member, uint8_t* __restrict__ sign,
                                                     uint64_t cap_c) {
   __shared__ uint32_t wsum[256 / 64];
-  const uint32_t lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const uint64_t i0 = (uint64_t)blockIdx.x * kCompTile + (uint64_t)threadIdx.x * kCompPer;
   unsigned long long key[kCompPer];
   uint32_t pay[kCompPer];
@@ -298,23 +338,11 @@ __global__ __launch_bounds__(256) void k_comp_write(SortSrc s, uint64_t n, const
       if (sign) sign[i0 + k] = (sign_kind && !parity[pay[k]]) ? 1 : 0;  // parity 0 <=> the colour of the minimum
     }
   }
-  const uint32_t cnt = (uint32_t)__popc(heads);
-  uint32_t x = cnt;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t y = __shfl_up(x, o, 64);
-    if ((int)lane >= o) x += y;
-  }
-  if (lane == 63) wsum[wid] = x;
-  __syncthreads();
-  uint32_t wbase = 0, total = 0;
-#pragma unroll
-  for (uint32_t q = 0; q < 256 / 64; ++q) {
-    if (q < wid) wbase += wsum[q];
-    total += wsum[q];
-  }
   const uint64_t first = bbase[blockIdx.x];
-  uint64_t pos = first + wbase + (x - cnt);
+  uint64_t pos = first + block_excl_scan<256>((uint32_t)__popc(heads), wsum);
+  uint32_t total = 0;
+#pragma unroll
+  for (uint32_t q = 0; q < 256 / 64; ++q) total += wsum[q];
 #pragma unroll
   for (uint32_t k = 0; k < kCompPer; ++k) {
     if (heads & (1u << k)) {
@@ -334,6 +362,16 @@ void launch_sort_digits(const int64_t* v, const int64_t* label, uint64_t n, uint
   const uint64_t tiles = (n + 256 * kDigitsPer - 1) / (256 * kDigitsPer);
   const uint32_t grid = (uint32_t)(tiles < 1024 ? (tiles ? tiles : 1) : 1024);
   hipLaunchKernelGGL(k_sort_digits, dim3(grid), dim3(256), 0, st, v, label, n, ctl);
+}
+
+void launch_sort_digits_one(const int64_t* key, uint64_t n, uint32_t* ctl, hipStream_t st) {
+  const uint64_t tiles = (n + 256 * kDigitsPer - 1) / (256 * kDigitsPer);
+  const uint32_t grid = (uint32_t)(tiles < kDigitsOneBlocks ? (tiles ? tiles : 1) : kDigitsOneBlocks);
+  hipLaunchKernelGGL(k_sort_digits_one, dim3(grid), dim3(256), 0, st, key, n, ctl);
+}
+
+void launch_tile_scan(uint32_t* tb, uint64_t nt, unsigned long long* total, hipStream_t st) {
+  hipLaunchKernelGGL(k_tile_scan, dim3(1), dim3(kSortScanBS), 0, st, tb, nt, total);
 }
 
 void launch_comp_roots(const int64_t* v, const int64_t* label, uint64_t n, unsigned long long* out, hipStream_t st) {

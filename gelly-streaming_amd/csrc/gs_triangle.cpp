@@ -20,10 +20,7 @@
 
 using namespace gsi;
 
-struct gs_triangles_s {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ext_ev = nullptr;
+struct gs_triangles_s : StreamOwner {
   // relabel table with the counters t(v)
   DevBuf<gs::Slot> tab;
   uint64_t cap = 0;
@@ -159,32 +156,6 @@ int grow_table(gs_triangles_s* t, uint64_t new_cap) {
   return GS_OK;
 }
 
-struct PhaseTimer {
-  gs_triangles_s* t;
-  bool on;
-  hipEvent_t ev[5] = {};
-  PhaseTimer(gs_triangles_s* h, bool enable) : t(h), on(enable) {
-    for (int i = 0; on && i < 5; ++i)
-      if (hipEventCreate(&ev[i]) != hipSuccess) on = false;
-  }
-  void mark(int i) {
-    if (on) (void)hipEventRecord(ev[i], t->stream);
-  }
-  void finish(int last) {
-    if (!on) return;
-    (void)hipStreamSynchronize(t->stream);
-    for (int i = 0; i < 4; ++i) {
-      float ms = 0;
-      t->phase_us[i] = 0;
-      if (i < last && hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess) t->phase_us[i] = (uint64_t)(ms * 1000.0f);
-    }
-  }
-  ~PhaseTimer() {
-    for (int i = 0; i < 5; ++i)
-      if (ev[i]) (void)hipEventDestroy(ev[i]);
-  }
-};
-
 // n > 0 device elements src[i * stride], dst[i * stride] on t->stream
 int fold_impl(gs_triangles_s* t, const int64_t* src, const int64_t* dst, uint64_t n, uint64_t stride) {
   if (int rc = ensure_fold_scratch(t, n)) return rc;
@@ -192,7 +163,7 @@ int fold_impl(gs_triangles_s* t, const int64_t* src, const int64_t* dst, uint64_
     if (t->entries) GS_HIP(hipMemsetAsync(t->aseq[t->cur], 0, t->entries * 4, t->stream));
     t->seq = 1;
   }
-  PhaseTimer timer(t, testing_value(GS_TESTING_TRIANGLE_PROFILE, 0) == 1);
+  PhaseTimer timer(t->stream, testing_value(GS_TESTING_TRIANGLE_PROFILE, 0) == 1, t->phase_us, 4);
   timer.mark(0);
   // 1. canonise
   gs::launch_tri_canon(src, dst, n, stride, t->lo, t->hi, t->stream);
@@ -211,7 +182,7 @@ int fold_impl(gs_triangles_s* t, const int64_t* src, const int64_t* dst, uint64_
   if (int rc = sort_run(t->sort, t->lo, n, sctl, nullptr, &cur, &side, t->stream)) return rc;
   gs::launch_tri_flag_new(cur.pay, t->lo, t->hi, n, t->adj(), t->flags, t->blk, t->stream);
   GS_HIP(hipGetLastError());
-  gs::launch_tri_scan(t->blk, gs::tri_blocks(n), t->ctl, gs::TRI_NEW, -1, t->stream);
+  gs::launch_tile_scan(t->blk, gs::tri_blocks(n), t->ctl + gs::TRI_NEW, t->stream);
   GS_HIP(hipGetLastError());
   gs::launch_tri_compact_new(cur.pay, t->lo, t->hi, n, t->flags, t->blk, t->nx, t->ny, t->f_cap, t->stream);
   GS_HIP(hipGetLastError());
@@ -226,7 +197,7 @@ int fold_impl(gs_triangles_s* t, const int64_t* src, const int64_t* dst, uint64_
   const uint64_t m = words[gs::TRI_NEW], nv = words[gs::TRI_NV];
   if (m > n) return fail(GS_ERR_HIP, "triangle fold: more new edges than elements");
   if (m == 0) {
-    timer.finish(2);
+    timer.finish();
     return GS_OK;
   }
   // (a failure below -- out of device memory while growing -- leaves G and its counts as they were)
@@ -269,7 +240,7 @@ int fold_impl(gs_triangles_s* t, const int64_t* src, const int64_t* dst, uint64_
                        t->stream);
   GS_HIP(hipGetLastError());
   timer.mark(4);
-  timer.finish(4);
+  timer.finish();
   return GS_OK;
 }
 
@@ -291,7 +262,7 @@ int export_impl(gs_triangles_s* t, int64_t* v, int64_t* count, size_t cap, size_
   const gs::TriAdj A = t->adj();
   gs::launch_tri_flag_heads(t->table(), t->ctl, A, nonzero_only ? 1 : 0, t->flags, t->blk, t->stream);
   GS_HIP(hipGetLastError());
-  gs::launch_tri_scan(t->blk, gs::tri_blocks(A.n), t->ctl, gs::TRI_ROWS, -1, t->stream);
+  gs::launch_tile_scan(t->blk, gs::tri_blocks(A.n), t->ctl + gs::TRI_ROWS, t->stream);
   GS_HIP(hipGetLastError());
   unsigned long long rows = 0;
   GS_HIP(hipMemcpyAsync(&rows, t->ctl + gs::TRI_ROWS, 8, hipMemcpyDeviceToHost, t->stream));
@@ -327,49 +298,22 @@ int export_impl(gs_triangles_s* t, int64_t* v, int64_t* count, size_t cap, size_
 
 extern "C" {
 
-int gs_triangle_destroy(gs_triangles t) {
-  if (!t) return GS_OK;
-  DeviceGuard g(t->device);
-  if (t->stream) (void)hipStreamSynchronize(t->stream);
-  if (t->ext_ev) (void)hipEventDestroy(t->ext_ev);
-  const hipStream_t stream = t->stream;
-  delete t;  // frees every device buffer (DevBuf members): device current, the stream idle
-  if (stream) (void)hipStreamDestroy(stream);
-  return GS_OK;
-}
+int gs_triangle_destroy(gs_triangles t) { return owner_destroy(t); }
 
 int gs_triangle_create(gs_triangles* out, int device, uint64_t edge_hint) {
   if (!out) return fail(GS_ERR_INVALID, "out is null");
   *out = nullptr;
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail(GS_ERR_HIP, "no HIP device available");
-  if (device < 0 || device >= count) return fail(GS_ERR_INVALID, "bad device");
+  if (int rc = check_device_index(device)) return rc;
   if (2 * edge_hint > kTriMaxEntries) return fail(GS_ERR_CAPACITY, "edge hint beyond 2^31 - 1 edges");
-  DeviceGuard g(device);
-  gs_triangles_s* t = new gs_triangles_s();
-  t->device = device;
-  int rc = GS_OK;
-  auto body = [&]() -> int {
-    GS_HIP(hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking));
-    GS_HIP(hipEventCreateWithFlags(&t->ext_ev, hipEventDisableTiming));
+  return owner_create(out, device, [&](gs_triangles_s* t) -> int {
     GS_HIP(t->ctr.alloc((uint64_t)gs::CTR_COUNT * gs::kCtrStride));
     GS_HIP(hipMemsetAsync(t->ctr, 0, (size_t)gs::CTR_COUNT * gs::kCtrStride * 4, t->stream));
     GS_HIP(t->ctl.alloc(gs::TRI_CTL_WORDS));
     GS_HIP(hipMemsetAsync(t->ctl, 0, gs::TRI_CTL_WORDS * 8, t->stream));
     const uint64_t e = std::max<uint64_t>(edge_hint, kTriMinCap / 2);
     if (int r = alloc_table(t, std::min<uint64_t>(kMaxCap, next_pow2(2 * e)))) return r;
-    if (int r = ensure_adj(t, 0, 2 * e)) return r;
-    GS_HIP(hipStreamSynchronize(t->stream));
-    return GS_OK;
-  };
-  rc = body();
-  if (rc) {
-    const std::string msg = gs_last_error();
-    (void)gs_triangle_destroy(t);
-    return fail(rc, msg);
-  }
-  *out = t;
-  return GS_OK;
+    return ensure_adj(t, 0, 2 * e);
+  });
 }
 
 int gs_triangle_reset(gs_triangles t) {
@@ -467,12 +411,7 @@ int gs_triangle_get_stream(gs_triangles t, void** stream) {
 
 int gs_triangle_wait_stream(gs_triangles t, void* stream) {
   if (int rc = check_tri(t)) return rc;
-  DeviceGuard g(t->device);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (st == t->stream) return GS_OK;
-  GS_HIP(hipEventRecord(t->ext_ev, st));  // (stream 0 = the device's null stream)
-  GS_HIP(hipStreamWaitEvent(t->stream, t->ext_ev, 0));
-  return GS_OK;
+  return t->wait_stream(stream);
 }
 
 // gs_testing.h: out[0] = intersection steps since reset, out[1] = the longest row a new edge

@@ -27,7 +27,7 @@ namespace gs {
 constexpr uint32_t TRIANGLE_LANES = 8;
 // Edges per workgroup of the per-edge passes (gsamd.TRIANGLE_TILE): canonise, flag, compact.
 constexpr uint32_t TRIANGLE_TILE = 1024;
-constexpr uint32_t kTriBS = 256;                       // threads of every workgroup but the scan's
+constexpr uint32_t kTriBS = 256;                       // threads of every workgroup
 constexpr uint32_t kTriPer = TRIANGLE_TILE / kTriBS;   // consecutive elements per thread
 static_assert(TRIANGLE_TILE == kTriBS * kTriPer, "tile = threads x elements per thread");
 constexpr uint32_t kTriShortRow = 4 * TRIANGLE_LANES;  // binned: shorter rows up to here take a lane group
@@ -90,11 +90,8 @@ void launch_tri_canon(const int64_t* src, const int64_t* dst, uint64_t n, uint64
 // to the row before, not in A; blk[b] = flagged rows of tile b.
 void launch_tri_flag_new(const uint32_t* pay, const int64_t* lo, const int64_t* hi, uint64_t n, const TriAdj& A,
                          uint8_t* flags, uint32_t* blk, hipStream_t st);
-// Exclusive scan of blk[0 .. nb) in place (one workgroup); ctl[total_word] = the sum, also
-// added to ctl[add_word] when add_word >= 0.
-void launch_tri_scan(uint32_t* blk, uint64_t nb, unsigned long long* ctl, int total_word, int add_word,
-                     hipStream_t st);
-// the flagged rows in order into (nx, ny), at most cap of them
+// the flagged rows in order into (nx, ny), at most cap of them; blk: the tile counts after
+// gs_sort.hpp's launch_tile_scan (tri_blocks(n) + 1 words)
 void launch_tri_compact_new(const uint32_t* pay, const int64_t* lo, const int64_t* hi, uint64_t n,
                             const uint8_t* flags, const uint32_t* blk, int64_t* nx, int64_t* ny, uint64_t cap,
                             hipStream_t st);

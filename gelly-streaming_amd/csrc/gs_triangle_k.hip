@@ -3,8 +3,9 @@
 //   k_tri_canon        : (src, dst) -> (min, max)
 //   k_tri_flag_new     : over the fold's pairs sorted by (min, max): keep a pair that is no loop,
 //                        differs from the pair before it and is not in A yet; count per tile
-//   k_tri_scan         : exclusive scan of the tile counts (one workgroup)
-//   k_tri_compact_new  : the kept pairs in order: N, the fold's new edges
+//   k_tri_compact_new  : the kept pairs in order: N, the fold's new edges; between a flag and
+//                        a compact kernel, the sort's launch_tile_scan turns the tile counts
+//                        into tile bases and the total
 //   k_tri_reverse      : N's reverse entries (max, min), through the sort by max
 //   k_tri_merge        : A' = merge(A, N, reverse N): every entry finds its position by binary
 //                        search in the two other lists (gs_triangle_rows.hpp tri_merge_pos)
@@ -22,11 +23,11 @@
 //   * a row walk runs q from the row's first to its last index, both at most A.n, read from
 //     TriRowInfo that k_tri_rows computed from the same A;
 //   * list-driven loops run to min(list length word, n_new) and test each list element < n_new;
-//   * the scan runs over nb tile counts in steps of its workgroup size;
 //   * table probes are gs_device.hpp's (at most cap + 1 steps);
 //   * every output position is tested against the capacity of its array before the store.
 // Counters change by atomic adds only; the count kernels read A and the table that earlier
-// launches wrote, never a counter.
+// launches wrote, never a counter. The tile count and the rank inside a tile are gs_scan.hpp's.
+#include "gs_scan.hpp"
 #include "gs_triangle.hpp"
 #include "gs_triangle_rows.hpp"
 
@@ -58,41 +59,6 @@ __device__ __forceinline__ uint32_t tri_insert_slot(const Table& t, unsigned lon
   }
   uint32_t link;
   return lookup_insert(t, key, link, fresh);
-}
-
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x) {
-  const uint32_t lane = threadIdx.x & 63u;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t y = __shfl_up(x, o, 64);
-    if ((int)lane >= o) x += y;
-  }
-  return x;
-}
-
-// rank of the thread's first flagged element among the flagged elements of its workgroup's
-// tile, threads owning kTriPer consecutive elements (cnt: the thread's flagged elements)
-__device__ __forceinline__ uint32_t tile_rank(uint32_t cnt, uint32_t* wsum) {
-  const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
-  const uint32_t x = wave_incl_scan(cnt);
-  if (lane == 63) wsum[wid] = x;
-  __syncthreads();
-  uint32_t wbase = 0;
-#pragma unroll
-  for (uint32_t q = 0; q < kTriBS / 64; ++q)
-    if (q < wid) wbase += wsum[q];
-  return wbase + x - cnt;
-}
-
-// tile count of flagged elements into blk[blockIdx.x]
-__device__ __forceinline__ void tile_count(uint32_t cnt, uint32_t* total, uint32_t* blk) {
-  if (threadIdx.x == 0) *total = 0;
-  __syncthreads();
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
-  if ((threadIdx.x & 63u) == 0 && cnt) atomicAdd(total, cnt);
-  __syncthreads();
-  if (threadIdx.x == 0) blk[blockIdx.x] = *total;
 }
 
 __global__ __launch_bounds__(kTriBS) void k_tri_init(Table t) {
@@ -146,37 +112,7 @@ __global__ __launch_bounds__(kTriBS) void k_tri_flag_new(const uint32_t* __restr
     flags[i] = keep ? 1 : 0;
     cnt += keep ? 1u : 0u;
   }
-  tile_count(cnt, &total, blk);
-}
-
-constexpr uint32_t kTriScanBS = 1024;
-
-__global__ __launch_bounds__(kTriScanBS) void k_tri_scan(uint32_t* __restrict__ blk, uint64_t nb,
-                                                         unsigned long long* __restrict__ ctl, int total_word,
-                                                         int add_word) {
-  __shared__ uint32_t ws[kTriScanBS / 64];
-  const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
-  uint64_t carry = 0;
-  for (uint64_t base = 0; base < nb; base += kTriScanBS) {  // block-uniform
-    const uint64_t i = base + threadIdx.x;
-    const uint32_t v = i < nb ? blk[i] : 0u;
-    const uint32_t x = wave_incl_scan(v);
-    if (lane == 63) ws[wid] = x;
-    __syncthreads();
-    uint32_t wbase = 0, total = 0;
-#pragma unroll
-    for (uint32_t q = 0; q < kTriScanBS / 64; ++q) {
-      if (q < wid) wbase += ws[q];
-      total += ws[q];
-    }
-    if (i < nb) blk[i] = (uint32_t)carry + wbase + x - v;
-    carry += total;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    ctl[total_word] = carry;
-    if (add_word >= 0) ctl[add_word] += carry;
-  }
+  block_count_to<kTriBS>(cnt, &total, blk + blockIdx.x);
 }
 
 __global__ __launch_bounds__(kTriBS) void k_tri_compact_new(const uint32_t* __restrict__ pay,
@@ -191,7 +127,7 @@ __global__ __launch_bounds__(kTriBS) void k_tri_compact_new(const uint32_t* __re
 #pragma unroll
   for (uint32_t k = 0; k < kTriPer; ++k)
     if (i0 + k < n && flags[i0 + k]) bits |= 1u << k;
-  uint64_t pos = (uint64_t)blk[blockIdx.x] + tile_rank((uint32_t)__popc(bits), wsum);
+  uint64_t pos = (uint64_t)blk[blockIdx.x] + block_excl_scan<kTriBS>((uint32_t)__popc(bits), wsum);
 #pragma unroll
   for (uint32_t k = 0; k < kTriPer; ++k) {
     if (!(bits & (1u << k))) continue;
@@ -454,7 +390,7 @@ __global__ __launch_bounds__(kTriBS) void k_tri_flag_heads(Table t, const unsign
     flags[i] = head ? 1 : 0;
     cnt += head ? 1u : 0u;
   }
-  tile_count(cnt, &total, blk);
+  block_count_to<kTriBS>(cnt, &total, blk + blockIdx.x);
 }
 
 __global__ __launch_bounds__(kTriBS) void k_tri_compact_rows(Table t, const unsigned long long* __restrict__ ctl,
@@ -467,7 +403,7 @@ __global__ __launch_bounds__(kTriBS) void k_tri_compact_rows(Table t, const unsi
 #pragma unroll
   for (uint32_t k = 0; k < kTriPer; ++k)
     if (i0 + k < A.n && flags[i0 + k]) bits |= 1u << k;
-  uint64_t pos = (uint64_t)blk[blockIdx.x] + tile_rank((uint32_t)__popc(bits), wsum);
+  uint64_t pos = (uint64_t)blk[blockIdx.x] + block_excl_scan<kTriBS>((uint32_t)__popc(bits), wsum);
 #pragma unroll
   for (uint32_t k = 0; k < kTriPer; ++k) {
     if (!(bits & (1u << k))) continue;
@@ -514,11 +450,6 @@ void launch_tri_flag_new(const uint32_t* pay, const int64_t* lo, const int64_t* 
   if (!n) return;
   hipLaunchKernelGGL(k_tri_flag_new, dim3((uint32_t)tri_blocks(n)), dim3(kTriBS), 0, st, pay, lo, hi, n, A, flags,
                      blk);
-}
-
-void launch_tri_scan(uint32_t* blk, uint64_t nb, unsigned long long* ctl, int total_word, int add_word,
-                     hipStream_t st) {
-  hipLaunchKernelGGL(k_tri_scan, dim3(1), dim3(kTriScanBS), 0, st, blk, nb, ctl, total_word, add_word);
 }
 
 void launch_tri_compact_new(const uint32_t* pay, const int64_t* lo, const int64_t* hi, uint64_t n,

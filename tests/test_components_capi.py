@@ -52,3 +52,16 @@ def test_sort_tile_constant_matches_the_kernels(gs):
     bs = int(re.search(r"kSortBS = (\d+);", text).group(1))
     items = int(re.search(r"kSortItems = (\d+);", text).group(1))
     assert gs.SORT_TILE == bs * items
+
+
+def test_tile_scan_block_constant_matches_the_kernels(gs):
+    """gsamd.TILE_SCAN_BLOCK (the step test_gpu_slice.py, test_gpu_distinct.py and
+    test_gpu_triangles.py cross) is kSortScanBS, the workgroup of k_tile_scan."""
+    csrc = os.path.join(ROOT, "gelly-streaming_amd", "csrc")
+    with open(os.path.join(csrc, "gs_sort.hpp")) as f:
+        assert gs.TILE_SCAN_BLOCK == int(re.search(r"kSortScanBS = (\d+);", f.read()).group(1))
+    with open(os.path.join(csrc, "gs_sort_k.hip")) as f:
+        text = f.read()
+    assert re.search(r"__launch_bounds__\(kSortScanBS\) void k_tile_scan\(", text)
+    assert re.search(r"hipLaunchKernelGGL\(k_tile_scan, dim3\(1\), dim3\(kSortScanBS\)", text)
+    assert re.search(r"c0 < nt; c0 \+= kSortScanBS\)", text)

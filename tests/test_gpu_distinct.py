@@ -510,3 +510,24 @@ def test_triangles_of_the_kept_edges(gs):
         assert kept.count() == full.count() and kept.count()[0] > 0
         for x, y in zip(kept.local_counts(), full.local_counts()):
             assert np.array_equal(x, y)
+
+
+# ---- more tiles than one step (edges) and two steps (entries) of the tile-count scan
+@pytest.mark.parametrize("edges", ["all-distinct", "all-equal"])
+def test_tile_scan_past_its_steps(gs, edges):
+    """One fold of T * TILE_SCAN_BLOCK + 1 edges: the edge compaction scans one tile count more
+    than a step of gsamd.TILE_SCAN_BLOCK, the vertex compaction one more than two steps; the
+    bases of the later tiles are sums the scan carries from step to step."""
+    n = gsamd.TILE_SCAN_BLOCK * T + 1
+    i = np.arange(n, dtype=np.int64)
+    src, dst = (2 * i, 2 * i + 1) if edges == "all-distinct" else (np.full(n, 5, np.int64), np.full(n, 9, np.int64))
+    assert -(-n // T) == gsamd.TILE_SCAN_BLOCK + 1 and -(-2 * n // T) == 2 * gsamd.TILE_SCAN_BLOCK + 1
+    entries = np.stack([src, dst], axis=1).ravel()  # entry 2 i = src, 2 i + 1 = dst of edge i
+    new_entry = np.sort(np.unique(entries, return_index=True)[1])
+    kept = np.sort(np.unique((src << 32) | dst, return_index=True)[1])  # (ids below 2^31)
+    with gs.Distinct(vertex_hint=len(new_entry), edge_hint=len(kept)) as ds:
+        assert ds.fold(src, dst) == (len(new_entry), len(kept))
+        assert ds.stats()["tiles"] == gsamd.TILE_SCAN_BLOCK + 1
+        v, ent = ds.new_vertices()
+        assert np.array_equal(v, entries[new_entry]) and np.array_equal(ent, new_entry)
+        assert np.array_equal(ds.new_edges()[0], kept)

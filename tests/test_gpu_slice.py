@@ -335,3 +335,23 @@ def test_device_entry_points(gs, direction):
         # the host forms read the same window
         gv, gr = sl.reduce("max")
         assert np.array_equal(gv, v) and np.array_equal(gr, red["max"])
+
+
+# ---- 11. more tiles than one step of the tile-count scan (gsamd.TILE_SCAN_BLOCK tile counts)
+@pytest.mark.parametrize("keys", ["heads-in-every-tile", "one-head-past-the-step"])
+def test_tile_scan_past_one_step(gs, keys):
+    """T * TILE_SCAN_BLOCK + 1 edges: the last tile's base is the sum the scan carries out of its
+    first step -- every head of the window, or (src = 0 but for the last edge) the one of tile 0."""
+    n = gsamd.TILE_SCAN_BLOCK * T + 1
+    i = np.arange(n, dtype=np.int64)
+    src = i // 3 if keys == "heads-in-every-tile" else (i == n - 1).astype(np.int64)
+    val = np.random.default_rng(11).integers(I64_MIN, I64_MAX, n, dtype=np.int64, endpoint=True)
+    v, off, nb, wv, red = _truth(src, i, val, "out")
+    with gs.Slice(edge_hint=n) as sl:
+        sl.window(src, i, val, "out")
+        assert sl.size() == (len(v), n)
+        gv, gr = sl.reduce("sum")
+        assert sl.stats()["tiles"] == gsamd.TILE_SCAN_BLOCK + 1
+        assert np.array_equal(gv, v) and np.array_equal(gr, red["sum"])
+        gv, goff, gnb, gw = sl.neighborhoods()
+        assert np.array_equal(gv, v) and np.array_equal(goff, off)

@@ -730,3 +730,22 @@ def test_hub_and_core_stream_in_three_folds(gs, variant, order):
             cd = np.concatenate([p[1] for p in parts[:i + 1]])
             _check(T, cs, cd, truth=_shared_truth(("hub and core", order, i), cs, cd))
             _check_assignment(T, parts[:i + 1], variant)
+
+
+# ---- 12. more tiles than one step (new edges) and two steps (export) of the tile-count scan
+def test_tile_scan_past_its_steps(gs):
+    """TILE * TILE_SCAN_BLOCK + 2 edges forming disjoint triangles, in one fold: the dedup scans
+    one tile count more than a step of gsamd.TILE_SCAN_BLOCK, the export of the 2 |G| adjacency
+    entries one more than two steps. T = the number of triangles, t(v) = 1 for every vertex, and
+    folding the same edges again adds nothing."""
+    n = gsamd.TILE_SCAN_BLOCK * TILE + 2
+    assert n % 3 == 0 and -(-n // TILE) == gsamd.TILE_SCAN_BLOCK + 1 and -(-2 * n // TILE) == 2 * gsamd.TILE_SCAN_BLOCK + 1
+    k = 3 * np.arange(n // 3, dtype=np.int64)
+    src = np.stack([k, k + 1, k], axis=1).ravel()
+    dst = np.stack([k + 1, k + 2, k + 2], axis=1).ravel()
+    with gs.Triangles(edge_hint=n) as T:
+        for fold in range(2):
+            T.fold(src, dst)
+            assert T.count() == (n // 3, n, n), fold
+            v, c = T.local_counts()
+            assert np.array_equal(v, np.arange(n, dtype=np.int64)) and bool((c == 1).all()), fold
