@@ -78,49 +78,25 @@ int64_t testing_value(int knob, int64_t product) {
 
 namespace {
 
-hipEvent_t take_event(gs_summary* h) {
-  if (!h->ev_pool.empty()) {
-    hipEvent_t e = h->ev_pool.back();
-    h->ev_pool.pop_back();
-    return e;
-  }
-  hipEvent_t e = nullptr;
-  (void)hipEventCreate(&e);
-  return e;
-}
-
-// Bracket one launch with events on stream st when profiling.
+// Bracket one launch with a span on stream st when profiling.
 struct Prof {
   gs_summary* h;
   int kid;
   hipStream_t st;
   hipEvent_t a = nullptr;
   Prof(gs_summary* h_, int k, hipStream_t s = nullptr) : h(h_), kid(k), st(s ? s : h_->stream) {
-    if (h->profiling) {
-      a = take_event(h);
-      (void)hipEventRecord(a, st);
-    }
+    if (h->profiling) a = h->spans.begin(st);
   }
   ~Prof() {
-    if (h->profiling) {
-      hipEvent_t b = take_event(h);
-      (void)hipEventRecord(b, st);
-      h->prof_pending.push_back({kid, a, b});
-    }
+    if (a) h->spans.end(kid, a, st);
   }
 };
 
 void drain_profile(gs_summary* h) {
-  for (auto& p : h->prof_pending) {
-    float ms = 0.f;
-    if (hipEventSynchronize(p.b) == hipSuccess && hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) {
-      h->launches[p.kid] += 1;
-      h->total_ms[p.kid] += ms;
-    }
-    h->ev_pool.push_back(p.a);
-    h->ev_pool.push_back(p.b);
-  }
-  h->prof_pending.clear();
+  h->spans.drain([h](int kid, float ms) {
+    h->launches[kid] += 1;
+    h->total_ms[kid] += ms;
+  });
 }
 
 // Order the handle's stream behind every fold still running on a lane (every lane
@@ -129,8 +105,8 @@ void drain_profile(gs_summary* h) {
 int join_pipe_lanes(gs_summary* h) {
   if (!h->lanes_dirty) return GS_OK;
   for (int i = 0; i < gs_summary::kLanes && h->lane[i]; ++i) {
-    GS_HIP(hipEventRecord(h->lane_ev[i], h->lane[i]));
-    GS_HIP(hipStreamWaitEvent(h->stream, h->lane_ev[i], 0));
+    GS_HIP(hipEventRecord(h->lane[i].ev, h->lane[i]));
+    GS_HIP(hipStreamWaitEvent(h->stream, h->lane[i].ev, 0));
   }
   h->xwait = true;
   h->lanes_dirty = false;
@@ -141,7 +117,7 @@ int join_pipe_lanes(gs_summary* h) {
 // previous export (another summary's fold) has read it.
 int wait_x_consumer(gs_summary* h) {
   if (!h->x_pending) return GS_OK;
-  GS_HIP(hipStreamWaitEvent(h->stream, h->x_used, 0));
+  GS_HIP(hipStreamWaitEvent(h->stream, h->xs.used, 0));
   h->xwait = true;
   h->x_pending = false;
   return GS_OK;
@@ -149,10 +125,12 @@ int wait_x_consumer(gs_summary* h) {
 
 // Combine scratch of at least `rows` rows (v, label, parity), allocated on growth only.
 int ensure_x(gs_summary* h, uint64_t rows) {
-  if (!h->x_cnt) {
-    GS_HIP(h->x_cnt.alloc(2));
-    GS_HIP(hipEventCreateWithFlags(&h->x_ready, hipEventDisableTiming));
-    GS_HIP(hipEventCreateWithFlags(&h->x_used, hipEventDisableTiming));
+  if (!h->xs.cnt) {
+    CombineSync xs;
+    GS_HIP(xs.cnt.alloc(2));
+    GS_HIP(xs.ready.create());
+    GS_HIP(xs.used.create());
+    h->xs = std::move(xs);
   }
   if (h->x_cap >= rows) return GS_OK;
   if (h->x_v) {
@@ -393,8 +371,10 @@ bool side_ok(const gs_summary* h) { return h->side && !h->profiling; }
 int ensure_lanes(gs_summary* h, int n) {
   for (int i = 0; i < n && i < gs_summary::kLanes; ++i) {
     if (h->lane[i]) continue;
-    GS_HIP(hipStreamCreateWithFlags(&h->lane[i], hipStreamNonBlocking));
-    GS_HIP(hipEventCreateWithFlags(&h->lane_ev[i], hipEventDisableTiming));
+    Lane l;
+    GS_HIP(l.st.create());
+    GS_HIP(l.ev.create());
+    h->lane[i] = std::move(l);
   }
   return GS_OK;
 }
@@ -403,7 +383,7 @@ int ensure_lanes(gs_summary* h, int n) {
 // Stop: the stop word, then the stream (the launch leaves within a poll interval).
 int server_stop(gs_summary* h) {
   if (!h->srv_running) return GS_OK;
-  __atomic_store_n(&h->srv_box->seq, gs::kServerStop | h->srv_seq, __ATOMIC_RELEASE);
+  __atomic_store_n(&h->srv.box.get()->seq, gs::kServerStop | h->srv_seq, __ATOMIC_RELEASE);
   h->srv_running = false;
   GS_HIP(hipStreamSynchronize(h->stream));
   return GS_OK;
@@ -413,11 +393,11 @@ int server_stop(gs_summary* h) {
 // at srv_seq (copied on the stream from the pinned mailbox, before the launch), so no
 // block mistakes the previous session's stop word for this session's.
 int server_start(gs_summary* h) {
-  gs::ServerBox* b = h->srv_box;
+  gs::ServerBox* b = h->srv.box;
   memset(b, 0, sizeof(gs::ServerBox));
   b->seq = h->srv_seq;
   b->bc_init = h->srv_seq;
-  GS_HIP(hipMemcpyAsync(&h->srv_bc.get()->seq, &b->bc_init, 8, hipMemcpyHostToDevice, h->stream));
+  GS_HIP(hipMemcpyAsync(&h->srv.bc.get()->seq, &b->bc_init, 8, hipMemcpyHostToDevice, h->stream));
   // ~2 ms without a window: the launch leaves on its own (wall clock 100 MHz). It holds
   // its stream's hardware queue while resident, so another stream that shares the queue
   // waits at most that long behind an idle server (the config-5 windows arrive
@@ -425,7 +405,7 @@ int server_start(gs_summary* h) {
   // (GS_TESTING_SERVER_IDLE_US, include/gs_testing.h).
   const int64_t idle_us = testing_value(GS_TESTING_SERVER_IDLE_US, 2000);
   const unsigned long long idle_ticks = (unsigned long long)std::max<int64_t>(idle_us, 1) * 100ull;
-  gs::launch_window_server(h->kind == GS_KIND_SIGNED, h->table(), h->delta(), h->srv_box, h->srv_bc, h->done_dev,
+  gs::launch_window_server(h->kind == GS_KIND_SIGNED, h->table(), h->delta(), h->srv.box, h->srv.bc, h->done_dev,
                            h->srv_seq, idle_ticks, h->stream);
   GS_HIP(hipGetLastError());
   h->srv_running = true;
@@ -562,7 +542,7 @@ hipStream_t report_stream_of(const gs_summary* h, int rs) {
 int launch_report_now(gs_summary* h, int rs, hipStream_t st) {
   const uint64_t claim = h->rep_pending[rs];
   if (!claim) return GS_OK;
-  gs::launch_report(h->ctr, claim, h->rep_dev + (h->rep_seq++ % gs_summary::kRepRing), (unsigned)(h->rep_epoch & 7u),
+  gs::launch_report(h->ctr, claim, h->rep.dev() + (h->rep_seq++ % gs_summary::kRepRing), (unsigned)(h->rep_epoch & 7u),
                     st);
   GS_HIP(hipGetLastError());
   h->rep_pending_edges -= claim;
@@ -705,7 +685,7 @@ int fold_device_impl(gs_summary* h, const int64_t* src, const int64_t* dst, cons
     const int rs = report_stream(h, st);
     const bool carry = check_cap && units && !fs.take_out && !fs.n_dev && h->rep_pending[rs];
     if (carry) {
-      f.rep_out = h->rep_dev + (h->rep_seq++ % gs_summary::kRepRing);
+      f.rep_out = h->rep.dev() + (h->rep_seq++ % gs_summary::kRepRing);
       f.rep_claim = h->rep_pending[rs];
       f.rep_epoch = (unsigned)(h->rep_epoch & 7u);
     }
@@ -752,8 +732,8 @@ int join_into_last_lane(gs_summary* h, hipStream_t* es, bool* on_lane) {
   *es = h->lane[h->last_lane];
   for (int i = 0; i < gs_summary::kLanes && h->lane[i]; ++i) {
     if (i == h->last_lane) continue;
-    GS_HIP(hipEventRecord(h->lane_ev[i], h->lane[i]));
-    GS_HIP(hipStreamWaitEvent(*es, h->lane_ev[i], 0));
+    GS_HIP(hipEventRecord(h->lane[i].ev, h->lane[i]));
+    GS_HIP(hipStreamWaitEvent(*es, h->lane[i].ev, 0));
   }
   GS_HIP(hipEventRecord(h->main_ev, h->stream));
   if (h->xwait || hipEventQuery(h->main_ev) != hipSuccess) GS_HIP(hipStreamWaitEvent(*es, h->main_ev, 0));
@@ -837,75 +817,26 @@ int gs_create(gs_handle* out, int device, int kind, uint64_t capacity_hint) {
   int ndev = 0;
   GS_HIP(hipGetDeviceCount(&ndev));
   if (device < 0 || device >= ndev) return fail(GS_ERR_HIP, "no HIP device " + std::to_string(device));
-  DeviceGuard g(device);
-  gs_summary* h = new gs_summary();
-  h->device = device;
-  h->kind = kind;
-  const uint64_t cap = create_capacity(capacity_hint);
-  auto bail = [&](int code) {
-    gs_destroy(h);
-    return code;
-  };
-  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess)
-    return bail(fail(GS_ERR_HIP, "hipStreamCreate failed"));
-  if (h->ctr.alloc(gs::CTR_COUNT * gs::kCtrStride) != hipSuccess)
-    return bail(fail(GS_ERR_HIP, "hipMalloc(counters) failed"));
-  if (h->d_scratch.alloc(8) != hipSuccess) return bail(fail(GS_ERR_HIP, "hipMalloc(scratch) failed"));
-  if (hipHostMalloc(&h->h_flags, 64, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-      hipHostGetDevicePointer(reinterpret_cast<void**>(&h->hflags_dev), h->h_flags, 0) != hipSuccess)
-    return bail(fail(GS_ERR_HIP, "hipHostMalloc(flags) failed"));
-  memset(h->h_flags, 0, 64);
-  h->h_done = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(h->h_flags) + 32);
-  h->done_dev = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(h->hflags_dev) + 32);
-  for (int i = 0; i < 2; ++i)
-    if (hipEventCreateWithFlags(&h->stage_ev[i], hipEventDisableTiming) != hipSuccess)
-      return bail(fail(GS_ERR_HIP, "hipEventCreate failed"));
-  if (hipEventCreateWithFlags(&h->main_ev, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&h->ext_ev, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&h->idle_ev, hipEventDisableTiming) != hipSuccess)
-    return bail(fail(GS_ERR_HIP, "hipEventCreate failed"));
-  memset(h->h_flags, 0, 16);
-  if (hipHostMalloc(&h->rep, gs_summary::kRepRing * 8, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-      hipHostGetDevicePointer(reinterpret_cast<void**>(&h->rep_dev), h->rep, 0) != hipSuccess)
-    return bail(fail(GS_ERR_HIP, "capacity report buffer allocation failed"));
-  memset(h->rep, 0, gs_summary::kRepRing * 8);
-  if (int rc = alloc_table(h, cap)) return bail(rc);
-  if (hipStreamSynchronize(h->stream) != hipSuccess) return bail(fail(GS_ERR_HIP, "init failed"));
-  *out = h;
-  return GS_OK;
+  return owner_create(out, device, [&](gs_summary* h) -> int {
+    constexpr unsigned kMapped = hipHostMallocMapped | hipHostMallocCoherent;
+    h->kind = kind;
+    GS_HIP(h->ctr.alloc(gs::CTR_COUNT * gs::kCtrStride));
+    GS_HIP(h->d_scratch.alloc(8));
+    GS_HIP(h->h_flags.alloc(16, kMapped));
+    h->h_done = reinterpret_cast<unsigned long long*>(h->h_flags + 8);
+    h->done_dev = reinterpret_cast<unsigned long long*>(h->h_flags.dev() + 8);
+    for (Event* e : {&h->stage_ev[0], &h->stage_ev[1], &h->main_ev, &h->idle_ev}) GS_HIP(e->create());
+    GS_HIP(h->rep.alloc(gs_summary::kRepRing, kMapped));
+    return alloc_table(h, create_capacity(capacity_hint));
+  });
 }
 
 int gs_destroy(gs_handle h) {
   if (!h) return GS_OK;
   DeviceGuard g(h->device);
   (void)join_lanes(h);
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
   drain_profile(h);
-  for (int i = 0; i < gs_summary::kLanes; ++i) {
-    if (h->lane_ev[i]) (void)hipEventDestroy(h->lane_ev[i]);
-    if (h->lane[i]) (void)hipStreamDestroy(h->lane[i]);
-  }
-  if (h->main_ev) (void)hipEventDestroy(h->main_ev);
-  if (h->ext_ev) (void)hipEventDestroy(h->ext_ev);
-  if (h->idle_ev) (void)hipEventDestroy(h->idle_ev);
-  if (h->srv_box) (void)hipHostFree(h->srv_box);
-  for (auto e : h->ev_pool) (void)hipEventDestroy(e);
-  for (int i = 0; i < 2; ++i) {
-    if (h->stage_ev[i]) (void)hipEventDestroy(h->stage_ev[i]);
-    if (h->text_ev[i]) (void)hipEventDestroy(h->text_ev[i]);
-  }
-  if (h->x_ready) (void)hipEventDestroy(h->x_ready);
-  if (h->x_used) (void)hipEventDestroy(h->x_used);
-  if (h->rep) (void)hipHostFree(h->rep);
-  if (h->h_flags) (void)hipHostFree(h->h_flags);
-  if (h->h_stage) (void)hipHostFree(h->h_stage);
-  if (h->h_wstage) (void)hipHostFree(h->h_wstage);
-  if (h->h_text) (void)hipHostFree(h->h_text);
-  if (h->h_tres) (void)hipHostFree(h->h_tres);
-  const hipStream_t stream = h->stream;
-  delete h;  // frees every device buffer (DevBuf members): device current, every stream joined and idle
-  if (stream) (void)hipStreamDestroy(stream);
-  return GS_OK;
+  return owner_destroy(h);  // (waits for the stream, every other one joined to it)
 }
 
 int gs_reset(gs_handle h) {
@@ -987,9 +918,11 @@ static bool host_pinned(const void* p) {
 }
 
 static int ensure_host_stage(gs_summary* h) {
-  if (h->h_stage) return GS_OK;
-  GS_HIP(hipHostMalloc(&h->h_stage, sizeof(int64_t) * 4 * kStageChunk, hipHostMallocDefault));
-  GS_HIP(hipHostMalloc(&h->h_wstage, 2 * kStageChunk, hipHostMallocDefault));
+  if (h->hstage.e) return GS_OK;
+  HostStage s;
+  GS_HIP(s.e.alloc(4 * kStageChunk, hipHostMallocDefault));
+  GS_HIP(s.w.alloc(2 * kStageChunk, hipHostMallocDefault));
+  h->hstage = std::move(s);
   return GS_OK;
 }
 
@@ -1042,13 +975,13 @@ static int fold_host_impl(gs_handle h, const int64_t* src, const int64_t* dst, c
     } else {
       if (int rc = ensure_host_stage(h)) return rc;
       GS_HIP(hipEventSynchronize(h->stage_ev[b]));  // the pinned buffer's previous copy is done
-      int64_t* hs = h->h_stage + (size_t)b * 2 * kStageChunk;
+      int64_t* hs = h->hstage.e + (size_t)b * 2 * kStageChunk;
       memcpy(hs, src + off, c * 8);
       memcpy(hs + kStageChunk, dst + off, c * 8);
       GS_HIP(hipMemcpyAsync(ds, hs, c * 8, hipMemcpyHostToDevice, h->stream));
       GS_HIP(hipMemcpyAsync(ds + sc, hs + kStageChunk, c * 8, hipMemcpyHostToDevice, h->stream));
       if (w) {
-        uint8_t* hw = h->h_wstage + (size_t)b * kStageChunk;
+        uint8_t* hw = h->hstage.w + (size_t)b * kStageChunk;
         memcpy(hw, w + off, c);
         GS_HIP(hipMemcpyAsync(dwp, hw, c, hipMemcpyHostToDevice, h->stream));
       }
@@ -1117,12 +1050,10 @@ int gs_wait_event(gs_handle h, void* event) {
 
 int gs_wait_stream(gs_handle h, void* stream) {
   if (int rc = check_any(h)) return rc;
+  if (static_cast<hipStream_t>(stream) == h->stream) return GS_OK;
   DeviceGuard g(h->device);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (st == h->stream) return GS_OK;
   if (int rc = server_stop(h)) return rc;
-  GS_HIP(hipEventRecord(h->ext_ev, st));  // (stream 0 = the device's null stream)
-  GS_HIP(hipStreamWaitEvent(h->stream, h->ext_ev, 0));
+  if (int rc = h->wait_stream(stream)) return rc;
   for (int i = 0; i < gs_summary::kLanes && h->lane[i]; ++i) GS_HIP(hipStreamWaitEvent(h->lane[i], h->ext_ev, 0));
   h->xwait = true;
   return GS_OK;
@@ -1486,7 +1417,7 @@ int gs_combine(gs_handle dst, gs_handle src) {
     if (int rc = wait_x_consumer(src)) return rc;
     if (!src->export_ctr_zero) GS_HIP(hipMemsetAsync(src->ctr + gs::ctr_index(gs::CTR_EXPORT), 0, 4, src->stream));
     src->export_ctr_zero = false;  // (the count stays behind for the copy below)
-    GS_HIP(hipMemsetAsync(src->x_cnt, 0, 16, src->stream));
+    GS_HIP(hipMemsetAsync(src->xs.cnt, 0, 16, src->stream));
     {
       Prof pr(src, KID_EXPORT);
       if (use_vertex_list(src, bound))
@@ -1495,36 +1426,36 @@ int gs_combine(gs_handle dst, gs_handle src) {
         gs::launch_export(src->table(), src->x_v, src->x_l, src->x_p, src->x_cap, src->stream, 0, 1, src->vlist_ok);
     }
     GS_HIP(hipGetLastError());
-    GS_HIP(hipMemcpyAsync(src->x_cnt, src->ctr + gs::ctr_index(gs::CTR_EXPORT), 4, hipMemcpyDeviceToDevice,
+    GS_HIP(hipMemcpyAsync(src->xs.cnt, src->ctr + gs::ctr_index(gs::CTR_EXPORT), 4, hipMemcpyDeviceToDevice,
                           src->stream));
-    GS_HIP(hipMemcpyAsync(src->x_cnt + 1, src->ctr + gs::ctr_index(gs::CTR_FAIL), 4, hipMemcpyDeviceToDevice,
+    GS_HIP(hipMemcpyAsync(src->xs.cnt + 1, src->ctr + gs::ctr_index(gs::CTR_FAIL), 4, hipMemcpyDeviceToDevice,
                           src->stream));
-    GS_HIP(hipEventRecord(src->x_ready, src->stream));
+    GS_HIP(hipEventRecord(src->xs.ready, src->stream));
   }
   DeviceGuard g(dst->device);
   if (int rc = join_lanes(dst)) return rc;
-  GS_HIP(hipStreamWaitEvent(dst->stream, src->x_ready, 0));
+  GS_HIP(hipStreamWaitEvent(dst->stream, src->xs.ready, 0));
   gs_summary* rows = src;
   if (dst->device != src->device) {  // rows to dst's own scratch over xGMI
     if (int rc = ensure_x(dst, bound + 1)) return rc;
     if (int rc = wait_x_consumer(dst)) return rc;
-    GS_HIP(hipMemcpyPeerAsync(dst->x_cnt, dst->device, src->x_cnt, src->device, 16, dst->stream));
+    GS_HIP(hipMemcpyPeerAsync(dst->xs.cnt, dst->device, src->xs.cnt, src->device, 16, dst->stream));
     if (bound) {
       GS_HIP(hipMemcpyPeerAsync(dst->x_v, dst->device, src->x_v, src->device, bound * 8, dst->stream));
       GS_HIP(hipMemcpyPeerAsync(dst->x_l, dst->device, src->x_l, src->device, bound * 8, dst->stream));
       GS_HIP(hipMemcpyPeerAsync(dst->x_p, dst->device, src->x_p, src->device, bound, dst->stream));
     }
-    GS_HIP(hipEventRecord(src->x_used, dst->stream));  // src's scratch is free again
+    GS_HIP(hipEventRecord(src->xs.used, dst->stream));  // src's scratch is free again
     src->x_pending = true;
     rows = dst;
   }
   FoldSource fs;
-  fs.n_dev = rows->x_cnt;
-  fs.fail_in = sign ? reinterpret_cast<const uint32_t*>(rows->x_cnt + 1) : nullptr;
+  fs.n_dev = rows->xs.cnt;
+  fs.fail_in = sign ? reinterpret_cast<const uint32_t*>(rows->xs.cnt + 1) : nullptr;
   // at least one thread reads the verdict of an empty failed summary (Candidates(false))
   const size_t n = std::max<uint64_t>(bound, sign ? 1 : 0);
   if (int rc = fold_device_impl(dst, rows->x_v, rows->x_l, rows->x_p, n, 1, 1, dst->track, true, fs)) return rc;
-  GS_HIP(hipEventRecord(rows->x_used, dst->stream));
+  GS_HIP(hipEventRecord(rows->xs.used, dst->stream));
   rows->x_pending = true;
   return GS_OK;
 }
@@ -1647,7 +1578,7 @@ static int server_take(gs_handle h, const int64_t* src, const int64_t* dst, size
       if (int rc = server_start(h)) return rc;
     // the descriptor words tagged with seq (the server reads the whole line in one load
     // round and takes it when every tag matches), then seq itself
-    gs::ServerBox* b = h->srv_box;
+    gs::ServerBox* b = h->srv.box;
     b->src = gs::tag_word(seq, (unsigned long long)src);
     b->dst = gs::tag_word(seq, (unsigned long long)dst);
     b->n = gs::tag_word(seq, n);
@@ -1700,10 +1631,11 @@ int gs_set_window_server(gs_handle h, int on) {
   if (int rc = check(h)) return rc;
   DeviceGuard g(h->device);
   if (int rc = join_lanes(h)) return rc;  // stops a running server
-  if (on && !h->srv_box) {
-    GS_HIP(hipHostMalloc(&h->srv_box, sizeof(gs::ServerBox), hipHostMallocMapped | hipHostMallocCoherent));
-    GS_HIP(h->srv_bc.alloc(1));
-    memset(h->srv_box, 0, sizeof(gs::ServerBox));
+  if (on && !h->srv.box) {
+    WindowServer srv;
+    GS_HIP(srv.box.alloc(1, hipHostMallocMapped | hipHostMallocCoherent));
+    GS_HIP(srv.bc.alloc(1));
+    h->srv = std::move(srv);
   }
   h->srv_on = on != 0;
   return GS_OK;
@@ -1916,33 +1848,35 @@ int gs_fold_text(gs_handle h, const char* text, size_t len, int sep, uint64_t* n
   *n_edges = 0;
   *bad_line = -1;
   const size_t max_lines = kTextChunk / 2 + 2;  // every line has >= 1 byte + '\n'
-  if (!h->h_text) {
+  if (!h->text.h_text) {
     size_t cub = 0;
     const size_t sb = gs::parse_scratch_bytes(kTextChunk, &cub);
-    GS_HIP(hipHostMalloc(&h->h_text, 2 * kTextChunk, hipHostMallocDefault));
-    GS_HIP(hipHostMalloc(&h->h_tres, 4 * sizeof(uint64_t), hipHostMallocDefault));
-    GS_HIP(h->d_text.alloc(2 * kTextChunk));
-    GS_HIP(h->d_tsrc.alloc(max_lines));
-    GS_HIP(h->d_tdst.alloc(max_lines));
-    GS_HIP(h->d_tscratch.alloc(sb));
-    for (int i = 0; i < 2; ++i) GS_HIP(hipEventCreateWithFlags(&h->text_ev[i], hipEventDisableTiming));
-    gs::parse_scratch_init(h->tscratch, h->d_tscratch, kTextChunk);
+    TextIngest t;
+    GS_HIP(t.h_text.alloc(2 * kTextChunk, hipHostMallocDefault));
+    GS_HIP(t.h_res.alloc(4, hipHostMallocDefault));
+    GS_HIP(t.d_text.alloc(2 * kTextChunk));
+    GS_HIP(t.d_src.alloc(max_lines));
+    GS_HIP(t.d_dst.alloc(max_lines));
+    GS_HIP(t.d_scratch.alloc(sb));
+    for (Event& e : t.ev) GS_HIP(e.create());
+    gs::parse_scratch_init(t.scratch, t.d_scratch, kTextChunk);
+    h->text = std::move(t);
   }
   // Double-buffered: while chunk k is copied to the device, parsed and folded, the
   // host copies chunk k+1 into the other pinned buffer.
   auto enqueue = [&](int b, size_t c) -> int {
-    char* dt = h->d_text + (size_t)b * kTextChunk;
-    GS_HIP(hipMemcpyAsync(dt, h->h_text + (size_t)b * kTextChunk, c, hipMemcpyHostToDevice, h->stream));
-    if (gs::parse_text_enqueue(h->stream, dt, c, sep, h->d_tsrc, h->d_tdst, max_lines, h->tscratch))
+    char* dt = h->text.d_text + (size_t)b * kTextChunk;
+    GS_HIP(hipMemcpyAsync(dt, h->text.h_text + (size_t)b * kTextChunk, c, hipMemcpyHostToDevice, h->stream));
+    if (gs::parse_text_enqueue(h->stream, dt, c, sep, h->text.d_src, h->text.d_dst, max_lines, h->text.scratch))
       return fail(GS_ERR_HIP, "text parse launch failed");
-    GS_HIP(hipMemcpyAsync(h->h_tres + 2 * b, h->tscratch.res, 16, hipMemcpyDeviceToHost, h->stream));
-    GS_HIP(hipEventRecord(h->text_ev[b], h->stream));
+    GS_HIP(hipMemcpyAsync(h->text.h_res + 2 * b, h->text.scratch.res, 16, hipMemcpyDeviceToHost, h->stream));
+    GS_HIP(hipEventRecord(h->text.ev[b], h->stream));
     return GS_OK;
   };
   if (len == 0) return GS_OK;
   size_t end = chunk_end(text, len, 0);
   if (!end) return fail(GS_ERR_INVALID, "a line is longer than the 16 MiB ingest chunk");
-  staged_copy(h->h_text, text, end);
+  staged_copy(h->text.h_text, text, end);
   if (int rc = enqueue(0, end)) return rc;
   uint64_t line0 = 0;
   for (int b = 0;; b ^= 1) {
@@ -1950,14 +1884,14 @@ int gs_fold_text(gs_handle h, const char* text, size_t len, int sep, uint64_t* n
     // that chunk's event was waited for in the previous iteration)
     const size_t noff = end, nend = noff < len ? chunk_end(text, len, noff) : noff;
     if (noff < len && !nend) return fail(GS_ERR_INVALID, "a line is longer than the 16 MiB ingest chunk");
-    if (noff < len) staged_copy(h->h_text + (size_t)(b ^ 1) * kTextChunk, text + noff, nend - noff);
-    GS_HIP(hipEventSynchronize(h->text_ev[b]));
-    const uint64_t nl = h->h_tres[2 * b], bad = h->h_tres[2 * b + 1];
+    if (noff < len) staged_copy(h->text.h_text + (size_t)(b ^ 1) * kTextChunk, text + noff, nend - noff);
+    GS_HIP(hipEventSynchronize(h->text.ev[b]));
+    const uint64_t nl = h->text.h_res[2 * b], bad = h->text.h_res[2 * b + 1];
     if (bad != ~0ull) {
       *bad_line = (int64_t)(line0 + bad);
       return fail(GS_ERR_PARSE, "malformed edge line " + std::to_string(*bad_line));
     }
-    if (int rc = fold_device_impl(h, h->d_tsrc, h->d_tdst, nullptr, nl, 1, 1, h->track)) return rc;
+    if (int rc = fold_device_impl(h, h->text.d_src, h->text.d_dst, nullptr, nl, 1, 1, h->track)) return rc;
     *n_edges += nl;
     line0 += nl;
     if (noff >= len) break;

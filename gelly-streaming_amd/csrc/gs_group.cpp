@@ -30,6 +30,7 @@
 #include <cstring>
 #include <deque>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -189,17 +190,17 @@ struct gs_group {
   bool prev_track = false;       // the summary's delta tracking before the group turned it on
   bool self_apply = false;       // test knob (GS_TESTING_GROUP_SELF_APPLY): also fold this rank's own rows back
   uint64_t batch = 0, rows_cap = 0;
+  // (the streams and the headers ahead of every DevBuf: deleting the group releases them last)
+  Stream xc, xd, as;                                    // counts, data, apply (the summary's side stream)
+  HostBuf<long long> hdr_host;                          // pinned host-mapped [kLag][nranks + 1]
   // exchange b uses buffer set b % kLag (send, counts, headers, receive) and delta set b % kDeltaSets
   DevBuf<int64_t> send[kLag];                           // [rows_cap * width]
   DevBuf<int64_t> recv[kLag];                           // [nranks * rows_cap * width]
   DevBuf<unsigned long long> cnt;                       // device: [kLag] send counts, then [kLag][nranks] gathered
-  long long* hdr_host = nullptr;                        // pinned host-mapped [kLag][nranks + 1]
-  long long* hdr_dev = nullptr;
-  hipStream_t xc = nullptr, xd = nullptr, as = nullptr;  // counts, data, apply (the summary's side stream)
-  hipEvent_t as_ev = nullptr;
-  hipEvent_t folded[gs::kDeltaSets][kGroupLanes] = {}, staged[gs::kDeltaSets] = {};  // per delta set (folded: per lane)
+  Event as_ev;
+  Event folded[gs::kDeltaSets][kGroupLanes], staged[gs::kDeltaSets];  // per delta set (folded: per lane)
   uint64_t chunks = 0;                                  // own micro-batches launched (lane = chunks % 2)
-  hipEvent_t counted[kLag] = {}, gathered[kLag] = {}, applied[kLag] = {};  // per buffer set
+  Event counted[kLag], gathered[kLag], applied[kLag];   // per buffer set
   uint64_t b = 0;       // exchanges since create / finish
   uint64_t own_edges = 0;  // own edges folded since create / finish (the ramp's position)
   uint64_t ramp_edges = 1ull << 22, ramp_batch = 1ull << 20;  // gs_group_set_ramp
@@ -221,12 +222,7 @@ struct gs_group {
   // [2] stage + count collective + headers, [3] data collective. Host wait for gathered
   // counts is always timed (wait_s).
   bool phases = false;
-  struct PhaseEv {
-    int ph;
-    hipEvent_t a, b;
-  };
-  std::vector<PhaseEv> ph_pending;
-  std::vector<hipEvent_t> ph_pool;
+  SpanTimer spans;  // one span per phase run, its id the phase
   double ph_ms[8] = {};
   uint64_t ph_exchanges = 0;
   double wait_s = 0;
@@ -243,12 +239,12 @@ struct gs_group {
   DevBuf<uint32_t> pflags;       // device: [0] owner-table overflow, [1] odd cycle found by an owner
   DevBuf<unsigned long long> pdev;     // device: [0..2] snap out, [3] pairs, [4] count word, [5] label rows,
                                        // [8, 8 + N) send counts, then N x N all send counts, then N count words
-  unsigned long long* phost = nullptr;  // pinned host mirror of pdev's words
+  HostBuf<unsigned long long> phost;    // pinned host mirror of pdev's words
   DevBuf<int64_t> stage, sendbuf, recvbuf, pairs, pairs_all;  // grow-only (ensure_buf)
   DevBuf<uint32_t> bcnt;
   DevBuf<gs::PairSlot> pset;     // the owner step's set of label pairs emitted this combine (N > 1)
   uint64_t cap_seen = 0;         // the local table's capacity at the previous combine (a rebuild re-exports all)
-  hipEvent_t pev = nullptr;      // the combine's pair gather -> the label forest's fold
+  Event pev;                     // the combine's pair gather -> the label forest's fold
   uint64_t combines = 0, rows_exported = 0, rows_owned = 0, pairs_sent = 0, pairs_folded = 0;
 
   unsigned long long* cnt_send(int k) const { return cnt + k; }
@@ -271,38 +267,11 @@ struct HostTimer {
   ~HostTimer() { lap(nullptr); }
 };
 
-hipEvent_t ph_event(gs_group* g) {
-  if (!g->ph_pool.empty()) {
-    hipEvent_t e = g->ph_pool.back();
-    g->ph_pool.pop_back();
-    return e;
-  }
-  hipEvent_t e = nullptr;
-  (void)hipEventCreate(&e);
-  return e;
-}
 // phase timing: an event on st now (the phase's start), or nullptr when timing is off
-hipEvent_t ph_begin(gs_group* g, hipStream_t st) {
-  if (!g->phases) return nullptr;
-  hipEvent_t a = ph_event(g);
-  (void)hipEventRecord(a, st);
-  return a;
-}
-void ph_end(gs_group* g, int ph, hipEvent_t a, hipStream_t st) {
-  if (!a) return;
-  hipEvent_t b = ph_event(g);
-  (void)hipEventRecord(b, st);
-  g->ph_pending.push_back({ph, a, b});
-}
+hipEvent_t ph_begin(gs_group* g, hipStream_t st) { return g->phases ? g->spans.begin(st) : nullptr; }
+void ph_end(gs_group* g, int ph, hipEvent_t a, hipStream_t st) { g->spans.end(ph, a, st); }
 void ph_drain(gs_group* g) {
-  for (auto& p : g->ph_pending) {
-    float ms = 0.f;
-    if (hipEventSynchronize(p.b) == hipSuccess && hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess)
-      g->ph_ms[p.ph] += ms;
-    g->ph_pool.push_back(p.a);
-    g->ph_pool.push_back(p.b);
-  }
-  g->ph_pending.clear();
+  g->spans.drain([g](int ph, float ms) { g->ph_ms[ph] += ms; });
 }
 
 // The data half of exchange e: wait for its gathered counts (host-mapped), gather
@@ -373,14 +342,17 @@ int finish_data(gs_group* g, uint64_t e) {
 // stream, were exact in every run.
 // A diagnostic build with -DGS_GROUP_HIPRIO=1 (tools/lostwork_probe.py) brings the highest
 // priority back.
-hipError_t create_comm_stream(hipStream_t* st) {
+hipError_t create_comm_stream(Stream& st) {
   if (GS_GROUP_HIPRIO) {
     int lo = 0, hi = 0;
     if (hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess)
-      return hipStreamCreateWithPriority(st, hipStreamNonBlocking, hi);
+      return st.create_with_priority(hipStreamNonBlocking, hi);
   }
-  return hipStreamCreateWithFlags(st, hipStreamNonBlocking);
+  return st.create();
 }
+
+// A group under construction: destroyed on every return path until released into *out.
+using GroupGuard = std::unique_ptr<gs_group, int (*)(gs_group*)>;
 
 }  // namespace
 
@@ -416,7 +388,8 @@ int gs_group_create(gs_group_t* out, gs_handle h, const void* id, int nranks, in
   gs_comm_api api;
   if (int rc = comm_api(&api)) return rc;
   DeviceGuard dg(h->device);
-  gs_group* g = new gs_group();
+  GroupGuard guard(new gs_group(), gs_group_destroy);
+  gs_group* g = guard.get();
   g->h = h;
   g->api = api;
   g->nranks = nranks;
@@ -426,50 +399,40 @@ int gs_group_create(gs_group_t* out, gs_handle h, const void* id, int nranks, in
   g->batch = batch_edges;
   g->self_apply = testing_value(GS_TESTING_GROUP_SELF_APPLY, 0) != 0;
   g->data_lag = (int)std::min<int64_t>(kLag, std::max<int64_t>(1, testing_value(GS_TESTING_GROUP_DATA_LAG, 2)));
-  auto bail = [&](int code) {
-    gs_group_destroy(g);
-    return code;
-  };
   if (g->exchange) {
-    if (h->side) return bail(fail(GS_ERR_INVALID, "the summary already belongs to an exchange group"));
-    if (int rc = join_lanes(h)) return bail(rc);
-    if (int rc = ensure_lanes(h, kGroupLanes)) return bail(rc);  // own folds rotate over the lanes
-    if (int rc = ensure_delta_list(h, batch_edges)) return bail(rc);
+    if (h->side) return fail(GS_ERR_INVALID, "the summary already belongs to an exchange group");
+    if (int rc = join_lanes(h)) return rc;
+    if (int rc = ensure_lanes(h, kGroupLanes)) return rc;  // own folds rotate over the lanes
+    if (int rc = ensure_delta_list(h, batch_edges)) return rc;
     g->prev_track = h->track;
-    if (int rc = gs_set_delta_tracking(h, 1)) return bail(rc);
+    if (int rc = gs_set_delta_tracking(h, 1)) return rc;
     g->rows_cap = (uint64_t)gs::kShards * h->delta_shard_cap;
-    bool ok = hipHostMalloc(&g->hdr_host, kLag * (size_t)(nranks + 1) * 8,
-                            hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess &&
-              hipHostGetDevicePointer(reinterpret_cast<void**>(&g->hdr_dev), g->hdr_host, 0) == hipSuccess &&
-              g->cnt.alloc(kLag + kLag * (uint64_t)nranks) == hipSuccess &&
-              create_comm_stream(&g->xc) == hipSuccess && create_comm_stream(&g->xd) == hipSuccess &&
-              hipStreamCreateWithFlags(&g->as, hipStreamNonBlocking) == hipSuccess &&
-              hipEventCreateWithFlags(&g->as_ev, hipEventDisableTiming) == hipSuccess;
-    for (int k = 0; k < gs::kDeltaSets && ok; ++k) {
-      for (int i = 0; i < kGroupLanes && ok; ++i)
-        ok = hipEventCreateWithFlags(&g->folded[k][i], hipEventDisableTiming) == hipSuccess;
-      ok = ok && hipEventCreateWithFlags(&g->staged[k], hipEventDisableTiming) == hipSuccess;
+    GS_HIP(g->hdr_host.alloc(kLag * (size_t)(nranks + 1), hipHostMallocMapped | hipHostMallocCoherent));
+    GS_HIP(g->cnt.alloc(kLag + kLag * (uint64_t)nranks));
+    GS_HIP(create_comm_stream(g->xc));
+    GS_HIP(create_comm_stream(g->xd));
+    GS_HIP(g->as.create());
+    GS_HIP(g->as_ev.create());
+    for (int k = 0; k < gs::kDeltaSets; ++k) {
+      for (Event& e : g->folded[k]) GS_HIP(e.create());
+      GS_HIP(g->staged[k].create());
     }
-    for (int k = 0; k < kLag && ok; ++k)
-      ok = g->send[k].alloc(g->rows_cap * g->width) == hipSuccess &&
-           g->recv[k].alloc((uint64_t)nranks * g->rows_cap * g->width) == hipSuccess &&
-           hipEventCreateWithFlags(&g->counted[k], hipEventDisableTiming) == hipSuccess &&
-           hipEventCreateWithFlags(&g->gathered[k], hipEventDisableTiming) == hipSuccess &&
-           hipEventCreateWithFlags(&g->applied[k], hipEventDisableTiming) == hipSuccess;
-    if (!ok) return bail(fail(GS_ERR_HIP, "group buffer allocation failed"));
+    for (int k = 0; k < kLag; ++k) {
+      GS_HIP(g->send[k].alloc(g->rows_cap * g->width));
+      GS_HIP(g->recv[k].alloc((uint64_t)nranks * g->rows_cap * g->width));
+      for (Event* e : {&g->counted[k], &g->gathered[k], &g->applied[k]}) GS_HIP(e->create());
+    }
     for (int k = 0; k < kLag; ++k) g->hdr(k)[nranks] = -1;  // no exchange yet
     h->side = g->as;
     h->side_ev = g->as_ev;
     h->side_dirty = false;
     h->group_lanes = kGroupLanes;
-  }
-  if (g->exchange) {
     const int r = api.comm_init_rank(&g->comm_c, nranks, id, rank);
-    if (r != 0) return bail(rccl_fail(&api, "ncclCommInitRank(counts)", r));
+    if (r != 0) return rccl_fail(&api, "ncclCommInitRank(counts)", r);
   }
   const int r = api.comm_init_rank(&g->comm_d, nranks, static_cast<const char*>(id) + kIdBytes, rank);
-  if (r != 0) return bail(rccl_fail(&api, "ncclCommInitRank(data)", r));
-  *out = g;
+  if (r != 0) return rccl_fail(&api, "ncclCommInitRank(data)", r);
+  *out = guard.release();
   return GS_OK;
 }
 
@@ -519,8 +482,7 @@ int gs_group_fold_device(gs_group_t g, const int64_t* src, const int64_t* dst, s
   int frc = GS_OK;
   bool used_lane[kGroupLanes] = {};
   hipEvent_t po[kGroupLanes] = {};
-  if (g->phases)
-    for (int i = 0; i < kGroupLanes; ++i) po[i] = ph_begin(g, lanes ? h->lane[i] : h->stream);
+  for (int i = 0; i < kGroupLanes; ++i) po[i] = ph_begin(g, lanes ? h->lane[i] : h->stream);
   for (size_t off = 0; off < n && !frc; off += kMicro) {
     FoldSource fs;
     if (lanes) {
@@ -536,9 +498,8 @@ int gs_group_fold_device(gs_group_t g, const int64_t* src, const int64_t* dst, s
   int nev = 0;
   hipEvent_t evs[kGroupLanes];
   for (int i = 0; i < kGroupLanes; ++i) {
-    if (!po[i]) continue;
     if (lanes ? used_lane[i] : i == 0) ph_end(g, 0, po[i], lanes ? h->lane[i] : h->stream);
-    else g->ph_pool.push_back(po[i]);  // (recorded, never timed)
+    else g->spans.cancel(po[i]);  // (recorded, never timed)
   }
   if (!lanes) {
     GS_HIP(hipEventRecord(g->folded[d][0], h->stream));
@@ -562,7 +523,7 @@ int gs_group_fold_device(gs_group_t g, const int64_t* src, const int64_t* dst, s
   GS_HIP(hipEventRecord(g->staged[d], g->xc));
   const int r = g->api.all_gather(g->cnt_send(k), g->cnt_recv(k), 1, kNcclInt64, g->comm_c, g->xc);
   if (r != 0) return rccl_fail(&g->api, "ncclAllGather(counts)", r);
-  gs::launch_headers(g->cnt_recv(k), g->nranks, g->hdr_dev + (size_t)k * (g->nranks + 1), (long long)b, g->xc);
+  gs::launch_headers(g->cnt_recv(k), g->nranks, g->hdr_host.dev() + (size_t)k * (g->nranks + 1), (long long)b, g->xc);
   GS_HIP(hipGetLastError());
   ph_end(g, 2, pc, g->xc);
   GS_HIP(hipEventRecord(g->counted[k], g->xc));
@@ -796,34 +757,15 @@ int gs_group_destroy(gs_group_t g) {
       g->h->group_lanes = 0;
       if (!g->prev_track) (void)gs_set_delta_tracking(g->h, 0);  // as before the group
     }
-    (void)hipStreamDestroy(g->as);
-  }
-  if (g->as_ev) (void)hipEventDestroy(g->as_ev);
-  for (int k = 0; k < gs::kDeltaSets; ++k) {
-    for (hipEvent_t e : g->folded[k])
-      if (e) (void)hipEventDestroy(e);
-    if (g->staged[k]) (void)hipEventDestroy(g->staged[k]);
-  }
-  for (int k = 0; k < kLag; ++k) {
-    for (hipEvent_t e : {g->counted[k], g->gathered[k], g->applied[k]})
-      if (e) (void)hipEventDestroy(e);
   }
   if (g->part) {
-    if (g->G) (void)gs_destroy(g->G);
-    if (g->phost) (void)hipHostFree(g->phost);
-    if (g->pev) (void)hipEventDestroy(g->pev);
+    (void)gs_destroy(g->G);
     if (g->window && !g->prev_track) (void)gs_set_delta_tracking(g->h, 0);
   }
   ph_drain(g);
-  for (hipEvent_t e : g->ph_pool) (void)hipEventDestroy(e);
-  const hipStream_t xc = g->xc, xd = g->xd;
-  long long* const hdr_host = g->hdr_host;
-  // frees the group's device buffers (DevBuf members): g->h's device is current (dg), its
-  // stream, the side stream and the two communication streams are idle
+  // releases every member, the streams and the headers after the device buffers: g->h's device
+  // is current (dg), its stream, the side stream and the two communication streams are idle
   delete g;
-  if (xc) (void)hipStreamDestroy(xc);
-  if (xd) (void)hipStreamDestroy(xd);
-  if (hdr_host) (void)hipHostFree(hdr_host);
   return GS_OK;
 }
 
@@ -891,7 +833,8 @@ int gs_group_create_partitioned(gs_group_t* out, gs_handle h, const void* id, in
   gs_comm_api api;
   if (int rc = comm_api(&api)) return rc;
   DeviceGuard dg(h->device);
-  gs_group* g = new gs_group();
+  GroupGuard guard(new gs_group(), gs_group_destroy);
+  gs_group* g = guard.get();
   g->h = h;
   g->api = api;
   g->nranks = nranks;
@@ -899,42 +842,38 @@ int gs_group_create_partitioned(gs_group_t* out, gs_handle h, const void* id, in
   g->width = h->kind == GS_KIND_SIGNED ? 3 : 2;
   g->part = true;
   g->window = window_edges;
-  auto bail = [&](int code) {
-    gs_group_destroy(g);
-    return code;
-  };
-  if (int rc = join_lanes(h)) return bail(rc);
   g->prev_track = h->track;
+  if (int rc = join_lanes(h)) return rc;
   if (window_edges) {  // records of the window: roots hooked away since the previous combine
-    if (int rc = ensure_delta_list(h, window_edges)) return bail(rc);
-    if (int rc = gs_set_delta_tracking(h, 1)) return bail(rc);
+    if (int rc = ensure_delta_list(h, window_edges)) return rc;
+    if (int rc = gs_set_delta_tracking(h, 1)) return rc;
   }
   // the label forest: grows on its own (capacity checks of its folds)
-  if (int rc = gs_create(&g->G, h->device, h->kind, std::max<uint64_t>(vertices_hint / 64, 1u << 12)))
-    return bail(rc);
+  if (int rc = gs_create(&g->G, h->device, h->kind, std::max<uint64_t>(vertices_hint / 64, 1u << 12))) return rc;
   uint64_t ocap = 1024;
   while (ocap < 4 * (vertices_hint / (uint64_t)nranks)) ocap <<= 1;  // load <= 1/4 at the hinted count
-  if (ocap > (1ull << 31)) return bail(fail(GS_ERR_INVALID, "vertices_hint too large for the owner table"));
+  if (ocap > (1ull << 31)) return fail(GS_ERR_INVALID, "vertices_hint too large for the owner table");
   g->ot.cap = (uint32_t)ocap;
   g->ot.mask = (uint32_t)(ocap - 1);
   g->ot.shift = 64 - log2_ceil(ocap);
   g->ot.r0 = (uint32_t)ocap;
   const size_t pwords = 8 + (size_t)nranks + (size_t)nranks * nranks + nranks;
-  bool ok = g->ot_tab.alloc(ocap + 1) == hipSuccess && g->mark.alloc(gs::kShards) == hipSuccess &&
-            g->snap.alloc(gs::kShards) == hipSuccess && g->pflags.alloc(4) == hipSuccess &&
-            g->pdev.alloc(pwords) == hipSuccess &&
-            hipHostMalloc(&g->phost, pwords * 8, hipHostMallocDefault) == hipSuccess &&
-            hipEventCreateWithFlags(&g->pev, hipEventDisableTiming) == hipSuccess;
-  if (!ok) return bail(fail(GS_ERR_HIP, "partitioned group allocation failed"));
+  GS_HIP(g->ot_tab.alloc(ocap + 1));
+  GS_HIP(g->mark.alloc(gs::kShards));
+  GS_HIP(g->snap.alloc(gs::kShards));
+  GS_HIP(g->pflags.alloc(4));
+  GS_HIP(g->pdev.alloc(pwords));
+  GS_HIP(g->phost.alloc(pwords, hipHostMallocDefault));
+  GS_HIP(g->pev.create());
   g->ot.tab = g->ot_tab;
   g->ot.err = g->pflags;
-  if (int rc = part_init_tables(g)) return bail(rc);
+  if (int rc = part_init_tables(g)) return rc;
   GS_HIP(hipStreamSynchronize(h->stream));
   int r = api.comm_init_rank(&g->comm_c, nranks, id, rank);
-  if (r != 0) return bail(rccl_fail(&api, "ncclCommInitRank(counts)", r));
+  if (r != 0) return rccl_fail(&api, "ncclCommInitRank(counts)", r);
   r = api.comm_init_rank(&g->comm_d, nranks, static_cast<const char*>(id) + kIdBytes, rank);
-  if (r != 0) return bail(rccl_fail(&api, "ncclCommInitRank(data)", r));
-  *out = g;
+  if (r != 0) return rccl_fail(&api, "ncclCommInitRank(data)", r);
+  *out = guard.release();
   return GS_OK;
 }
 

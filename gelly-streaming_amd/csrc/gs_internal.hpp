@@ -1,9 +1,10 @@
 // gs_internal.hpp -- the summary handle and the internal entry points shared by
 // gs_capi.cpp (include/gs_summary.h), gs_group.cpp (include/gs_group.h),
 // gs_changes.cpp (per-window change emission), gs_degree.cpp, gs_triangle.cpp and gs_sort.cpp;
-// the phase timer and the stream owner of the handles with one stream of their own
-// (gs_slice.cpp, gs_triangle.cpp, gs_distinct.cpp).
-// Every device array a handle owns is a DevBuf (gs_devbuf.hpp): deleting the handle frees it.
+// the phase timer and the stream owner every handle derives from (the summary here, and
+// gs_slice.cpp, gs_triangle.cpp, gs_distinct.cpp).
+// Every device array a handle owns is a DevBuf (gs_devbuf.hpp), every event, stream and pinned
+// host block an Event, Stream or HostBuf (gs_own.hpp): deleting the handle releases them.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -13,6 +14,7 @@
 #include "gs_devbuf.hpp"
 #include "gs_ingest.hpp"
 #include "gs_kernels.hpp"
+#include "gs_own.hpp"
 #include "gs_sort.hpp"
 #include "gs_summary.h"
 #include "gs_testing.h"
@@ -107,15 +109,13 @@ struct PhaseTimer {
   bool on;
   uint64_t* us;
   int phases;
-  hipEvent_t ev[kMaxPhases + 1] = {};
+  Event ev[kMaxPhases + 1];
   uint32_t recorded = 0;  // bit i: event i
   PhaseTimer(hipStream_t stream, bool enable, uint64_t* phase_us, int n)
       : st(stream), on(enable && n <= kMaxPhases), us(phase_us), phases(n) {
     for (int i = 0; on && i <= phases; ++i)
-      if (hipEventCreate(&ev[i]) != hipSuccess) on = false;
+      if (ev[i].create(hipEventDefault) != hipSuccess) on = false;
   }
-  PhaseTimer(const PhaseTimer&) = delete;
-  PhaseTimer& operator=(const PhaseTimer&) = delete;
   // event i for a launcher that records it between two of its own kernels (null when off)
   hipEvent_t event(int i) {
     if (!on) return nullptr;
@@ -134,18 +134,16 @@ struct PhaseTimer {
       us[i] = ran ? (uint64_t)(ms * 1000.0f) : 0;
     }
   }
-  ~PhaseTimer() {
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
 };
 
-// What a summary that works on one stream of its own owns beside its arrays (the window slices,
-// the triangle summary, the distinct streams; their handles derive from it).
+// What every handle owns beside its arrays: its device, its stream and the event of its
+// *_wait_stream. The handles derive from it, and a base subobject is destroyed last: deleting a
+// handle releases its members in reverse order of declaration, then ext_ev, then the stream,
+// after every DevBuf.
 struct StreamOwner {
   int device = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ext_ev = nullptr;  // *_wait_stream: recorded on a producer's stream
+  Stream stream;
+  Event ext_ev;  // *_wait_stream: recorded on a producer's stream
 
   // work queued on the handle's stream from here on runs after what `producer` holds now
   int wait_stream(void* producer) {
@@ -171,10 +169,7 @@ int owner_destroy(H* h) {
   if (!h) return GS_OK;
   DeviceGuard g(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  if (h->ext_ev) (void)hipEventDestroy(h->ext_ev);
-  const hipStream_t stream = h->stream;
-  delete h;  // frees every device buffer (DevBuf members): device current, the stream idle
-  if (stream) (void)hipStreamDestroy(stream);
+  delete h;  // releases every member, the stream last: device current, the stream idle
   return GS_OK;
 }
 
@@ -187,8 +182,8 @@ int owner_create(H** out, int device, Init init) {
   H* h = new H();
   h->device = device;
   const int rc = [&]() -> int {
-    GS_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    GS_HIP(hipEventCreateWithFlags(&h->ext_ev, hipEventDisableTiming));
+    GS_HIP(h->stream.create());
+    GS_HIP(h->ext_ev.create());
     if (int r = init(h)) return r;
     GS_HIP(hipStreamSynchronize(h->stream));
     return GS_OK;
@@ -202,12 +197,38 @@ int owner_create(H** out, int device, Init init) {
   return GS_OK;
 }
 
+// Resource sets a call creates on first use: filled in a local, move-assigned into the handle
+// only when complete, so a failed first use leaves the handle as it was.
+struct Lane {  // a pipelining lane: usable wherever its stream is
+  Stream st;
+  Event ev;
+  operator hipStream_t() const { return st; }
+};
+struct HostStage {  // pinned staging of large host folds, the shape of d_stage / d_wstage
+  HostBuf<int64_t> e;
+  HostBuf<uint8_t> w;
+};
+struct CombineSync {
+  DevBuf<unsigned long long> cnt;  // device: exported rows (u64) + failure flag (u32 at word 1)
+  Event ready, used;
+};
+struct TextIngest {  // pinned + device text chunks, parse results, parsed edges, scratch
+  HostBuf<char> h_text;
+  HostBuf<uint64_t> h_res;
+  Event ev[2];
+  DevBuf<char> d_text;
+  DevBuf<int64_t> d_src, d_dst;
+  DevBuf<void> d_scratch;  // (bytes)
+  gs::ParseScratch scratch;
+};
+struct WindowServer {
+  HostBuf<gs::ServerBox> box;  // host-mapped mailbox
+  DevBuf<gs::ServerBcast> bc;  // device: block 0 -> other blocks
+};
 }  // namespace gsi
 
-struct gs_summary {
-  int device = 0;
+struct gs_summary : gsi::StreamOwner {
   int kind = GS_KIND_CC;
-  hipStream_t stream = nullptr;
   // table + vertex list
   gsi::DevBuf<gs::Slot> tab;  // [cap + 1]: hashed slots + the reserved slot of INT64_MIN
   uint64_t cap = 0;
@@ -217,10 +238,9 @@ struct gs_summary {
   uint32_t vshard_cap = 0;
   uint32_t shard0 = 0;        // first shard of the next fold launch (rotates)
   bool vlist_ok = true;       // false once a shard of the vertex list overflowed (until reset)
-  uint32_t* h_flags = nullptr;     // host-mapped mirror of CTR_ERR / CTR_OVF / CTR_VOVF (raise_flag)
-  uint32_t* hflags_dev = nullptr;  // its device address
+  gsi::HostBuf<uint32_t> h_flags;  // [16] host-mapped mirror of CTR_ERR / CTR_OVF / CTR_VOVF (raise_flag)
   // host waits (wait_stream): completion word {seq, value} in the same host-mapped
-  // allocation (bytes 32..47), written by k_signal
+  // allocation (bytes 32..47), written by k_signal; views, host and device
   unsigned long long* h_done = nullptr;
   unsigned long long* done_dev = nullptr;
   unsigned long long done_seq = 0;
@@ -230,8 +250,7 @@ struct gs_summary {
   uint64_t cap_waits = 0, cap_syncs = 0;  // capacity checks that waited for reports / joined every stream
   double cap_wait_s = 0;                  // host seconds spent in those waits
   static constexpr int kRepRing = 16;
-  unsigned long long* rep = nullptr;      // host pointer
-  unsigned long long* rep_dev = nullptr;  // its device mapping
+  gsi::HostBuf<unsigned long long> rep;  // [kRepRing] host-mapped
   uint64_t rep_seq = 0;
   uint64_t rep_epoch = 0;  // resets since create: tags reports (k_report) so late ones are ignored
   static constexpr int kRepEvery = 4;    // each stream reports every 4th capacity-checked chunk
@@ -267,9 +286,8 @@ struct gs_summary {
   gsi::DevBuf<int64_t> d_stage;   // [2][2][d_stage_chunk] (allocated by the first host fold)
   gsi::DevBuf<uint8_t> d_wstage;  // [2][d_stage_chunk]
   uint64_t d_stage_chunk = 0;  // edges per staging buffer
-  int64_t* h_stage = nullptr;  // pinned, same shape: large host folds (allocated on first use)
-  uint8_t* h_wstage = nullptr;
-  hipEvent_t stage_ev[2] = {nullptr, nullptr};  // after each buffer's copies
+  gsi::HostStage hstage;       // (first use: a host fold too large for direct copies)
+  gsi::Event stage_ev[2];      // after each buffer's copies
   int stage_next = 0;
   gsi::DevBuf<int64_t> d_scratch;  // small scratch (find_one)
   // combine export scratch (gs_combine source side): reused across calls
@@ -277,9 +295,8 @@ struct gs_summary {
   gsi::DevBuf<int64_t> x_l;
   gsi::DevBuf<uint8_t> x_p;
   uint64_t x_cap = 0;
-  gsi::DevBuf<unsigned long long> x_cnt;  // device: exported rows (u64) + failure flag (u32 at word 1)
-  hipEvent_t x_ready = nullptr, x_used = nullptr;
-  bool x_pending = false;  // x_used recorded by a consumer not yet waited for
+  gsi::CombineSync xs;     // (first use: ensure_x)
+  bool x_pending = false;  // xs.used recorded by a consumer not yet waited for
   // grouped component export (gs_export_components*) and the degree exports: the radix sort's
   // scratch, sized by the first call that needs it; co_*: device staging of the host-array form
   gsi::SortScratch sort;
@@ -291,15 +308,7 @@ struct gs_summary {
   // degree summary (GS_KIND_DEGREE, gs_degree.cpp): endpoint occurrences folded since reset --
   // the host-side bound that keeps every 32-bit counter below 2^31
   uint64_t deg_total = 0;
-  // text ingest (gs_fold_text): pinned + device text chunks, parsed edges, scratch
-  char* h_text = nullptr;
-  uint64_t* h_tres = nullptr;
-  hipEvent_t text_ev[2] = {nullptr, nullptr};
-  gsi::DevBuf<char> d_text;
-  gsi::DevBuf<int64_t> d_tsrc;
-  gsi::DevBuf<int64_t> d_tdst;
-  gsi::DevBuf<void> d_tscratch;  // (bytes)
-  gs::ParseScratch tscratch;
+  gsi::TextIngest text;  // (first use: gs_fold_text)
   // pipelined folds (gs_set_pipelining): consecutive plain device folds alternate
   // over lane streams so that fold b+1 may start while fold b drains; every other
   // entry point joins the lanes onto `stream` first (join_lanes)
@@ -307,11 +316,9 @@ struct gs_summary {
   uint64_t api_calls = 0;  // gs_* calls made on the handle (gs_group_fold_device orders its lanes after any)
   int group_lanes = 0;  // own-fold lanes of an exchange group using this summary (0: none)
   static constexpr int kLanes = 4;
-  hipStream_t lane[kLanes] = {};
-  hipEvent_t lane_ev[kLanes] = {};
-  hipEvent_t main_ev = nullptr;
-  hipEvent_t ext_ev = nullptr;  // gs_wait_stream: recorded on a producer's stream
-  hipEvent_t idle_ev = nullptr;  // stream_idle: recorded and queried
+  gsi::Lane lane[kLanes];  // (first use: ensure_lanes)
+  gsi::Event main_ev;
+  gsi::Event idle_ev;  // stream_idle: recorded and queried
   // h->stream holds waits on other streams' events queued since its last completion-kernel wait:
   // only a kernel queued behind them observes them (an event recorded there completed at once
   // in the multi-rank replay), so an idle check must not be taken then
@@ -322,7 +329,8 @@ struct gs_summary {
   bool export_ctr_zero = false;  // CTR_EXPORT is zero behind the queued work (no fill before an export)
   // side stream (a multi-GPU group's apply stream): folds of remote rows run there,
   // overlapping this rank's own folds; every reader joins it (join_lanes), the
-  // handle's own folds do not (union commutes)
+  // handle's own folds do not (union commutes). Views: the group owns both and takes them
+  // back (null) before it releases them
   hipStream_t side = nullptr;
   hipEvent_t side_ev = nullptr;
   bool side_dirty = false;
@@ -338,18 +346,12 @@ struct gs_summary {
   // latency path's windows; every other entry point stops it first (join_lanes)
   bool srv_on = false, srv_running = false;
   int srv_fits = -1;                     // all kServerBlocks workgroups co-resident (-1: not yet checked)
-  gs::ServerBox* srv_box = nullptr;      // host-mapped mailbox
-  gsi::DevBuf<gs::ServerBcast> srv_bc;   // device: block 0 -> other blocks
+  gsi::WindowServer srv;                 // (first use: gs_set_window_server)
   unsigned long long srv_seq = 0;        // last window posted and completed
   uint64_t srv_launches = 0, srv_windows = 0;
   // profiling
   bool profiling = false;
-  struct Pending {
-    int kid;
-    hipEvent_t a, b;
-  };
-  std::vector<Pending> prof_pending;
-  std::vector<hipEvent_t> ev_pool;
+  gsi::SpanTimer spans;  // one span per launch, its id the kernel's KID_*
   uint64_t launches[gsi::KID_N] = {0, 0, 0, 0};
   double total_ms[gsi::KID_N] = {0, 0, 0, 0};
 
@@ -358,7 +360,7 @@ struct gs_summary {
     t.vlist = vlist;
     t.vshard_cap = vshard_cap;
     t.mark_new = changes ? 1 : 0;
-    t.hflags = hflags_dev;
+    t.hflags = h_flags.dev();
     return t;
   }
   gs::Delta delta(int set = -1) const {

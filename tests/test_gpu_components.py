@@ -422,3 +422,77 @@ def test_scratch_is_counted_and_released(gs):
     finally:
         s.close()
     assert gs.hbm_bytes() == start
+
+
+# ------------------------------------------------------------- case 8: every first-use group
+def _first_use_round(gs, kind):
+    """One summary through every resource set that a call creates on first use, then closed:
+    the result equals a fresh summary's of the same edges, and no device byte stays behind."""
+    import torch
+    dev = torch.device("cuda", 0)
+    rng = np.random.default_rng(0xF1257)
+
+    def edges(n):  # even -> odd ids below 4,096: bipartite, so the signed verdict holds
+        return 2 * rng.integers(0, 2048, size=n, dtype=np.int64), 2 * rng.integers(0, 2048, size=n, dtype=np.int64) + 1
+
+    lanes, big, prof, win, other = edges(4000), edges((1 << 18) + 1), edges(100), edges(64), edges(500)
+    text_s, text_d = np.array([1, 3, 5], dtype=np.int64), np.array([2, 4, 6], dtype=np.int64)
+    gc.collect()  # (no summary of an earlier test is released while this one counts)
+    start = gs.hbm_bytes()
+    s, t = gs.Summary(kind, capacity_hint=4096), gs.Summary(kind, capacity_hint=4096)
+    try:
+        # pipelining lanes
+        ts, td = torch.from_numpy(lanes[0]).to(dev), torch.from_numpy(lanes[1]).to(dev)
+        ws, wd = torch.from_numpy(win[0]).to(dev), torch.from_numpy(win[1]).to(dev)
+        rec = torch.empty((64, 3), dtype=torch.int64, device=dev)
+        cnt = torch.zeros(1, dtype=torch.int64, device=dev)
+        torch.cuda.synchronize()
+        s.set_pipelining(4)
+        for i in range(0, 4000, 1000):
+            s.fold_device(ts[i:i + 1000], td[i:i + 1000])
+        # pinned host staging: the smallest host fold that is copied through it
+        s.fold(*big)
+        # text ingest
+        assert s.fold_text(b"1 2\n3 4\n5 6\n") == 3
+        # profiling
+        s.set_profiling(True)
+        s.fold(*prof)
+        launches, ms = s.kernel_stats("fold")
+        assert launches >= 1 and ms > 0
+        s.set_profiling(False)
+        # window server
+        s.set_delta_tracking(True)
+        s.set_window_server(True)
+        assert s.fold_take(ws, wd, 64, rec, 64, cnt) <= 64
+        assert s.window_server_stats()["windows"] == 1
+        # combine scratch (the source's), host staging of components
+        t.fold(*other)
+        s.combine(t)
+        ok, comp, offset, member, sign = s.components()
+        assert ok and len(member) == s.num_vertices()
+        parts = (lanes, big, (text_s, text_d), prof, win, other)
+        src, dst = np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
+        with gs.Summary(kind, capacity_hint=4096) as fresh:
+            fresh.fold(src[:1 << 17], dst[:1 << 17])  # (plain folds, each a direct copy)
+            fresh.fold(src[1 << 17:], dst[1 << 17:])
+            if kind == "cc":
+                for a, b in zip(s.labels(), fresh.labels()):
+                    assert np.array_equal(a, b)
+            else:
+                got, want = s.colouring(), fresh.colouring()
+                assert got[0] is True and want[0] is True
+                for a, b in zip(got[1:], want[1:]):
+                    assert np.array_equal(a, b)
+    finally:
+        s.close()
+        t.close()
+    assert gs.hbm_bytes() == start
+
+
+def test_every_first_use_group_is_released(gs):
+    """Twice in one process: a handle whose destroy left a stream or an event behind shows up as
+    a HIP error at a later create. (That a closed summary returns its component staging is
+    test_scratch_is_counted_and_released's; here every other set is in play as well.)"""
+    for _ in range(2):
+        for kind in ("cc", "signed"):
+            _first_use_round(gs, kind)
