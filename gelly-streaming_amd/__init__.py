@@ -52,7 +52,7 @@ EXPORTED_SYMBOLS = (
     "gs_combine", "gs_sync", "gs_num_vertices", "gs_find", "gs_export_labels", "gs_export_labels_device",
     "gs_bip_status", "gs_export_colouring", "gs_serialize", "gs_deserialize", "gs_set_delta_tracking",
     "gs_take_delta_records", "gs_fold_take_device", "gs_delta_stage", "gs_fold_records_device", "gs_fold_exchange_device",
-    "gs_get_stream", "gs_set_pipelining", "gs_set_profiling", "gs_kernel_stats", "gs_table_capacity", "gs_counters", "gs_debug_counters",
+    "gs_get_stream", "gs_set_pipelining", "gs_set_hot_index", "gs_hot_index_stats", "gs_set_profiling", "gs_kernel_stats", "gs_table_capacity", "gs_counters", "gs_debug_counters",
     "gs_gen_rmat", "gs_gen_er", "gs_gen_bip",
     "gs_parse_edges_device", "gs_fold_text", "gs_parse_set_profiling", "gs_parse_profile", "gs_parse_release",
     "gs_group_unique_id", "gs_group_create", "gs_group_fold_device", "gs_group_finish", "gs_group_stats",
@@ -211,6 +211,8 @@ def lib():
     L.gs_get_stream.argtypes = [_vp, ctypes.POINTER(_vp)]
     L.gs_set_profiling.argtypes = [_vp, ctypes.c_int]
     L.gs_set_pipelining.argtypes = [_vp, ctypes.c_int]
+    L.gs_set_hot_index.argtypes = [_vp, ctypes.c_int, _u64, ctypes.c_uint32]
+    L.gs_hot_index_stats.argtypes = [_vp, ctypes.POINTER(_u64)]
     L.gs_kernel_stats.argtypes = [_vp, ctypes.c_int, ctypes.POINTER(_u64), ctypes.POINTER(ctypes.c_double)]
     L.gs_table_capacity.argtypes = [_vp, ctypes.POINTER(_u64)]
     L.gs_counters.argtypes = [_vp, ctypes.POINTER(_u64)]
@@ -456,6 +458,9 @@ class Summary:
         h = _vp()
         _check(lib().gs_create(ctypes.byref(h), device, self.kind, capacity_hint))
         self._h = h
+        # A/B runs: GS_HOT_INDEX=0 turns the hot index's default off (set_hot_index still forces it)
+        if self.kind == KIND_CC and os.environ.get("GS_HOT_INDEX") == "0":
+            _check(lib().gs_set_hot_index(h, -1, 0, 0))
 
     # --- lifecycle
     def close(self):
@@ -792,6 +797,20 @@ class Summary:
         device (pipelined windows); any read orders behind them."""
         _check(lib().gs_set_pipelining(self._h, int(depth)))
 
+    def set_hot_index(self, log2_entries=0, first_after_edges=0, rebuild_every_folds=1):
+        """gs_set_hot_index: the plain CC fold's index of frequent ids. log2_entries < 0 turns it
+        off, 0 restores the defaults (on for tables of at least 256 MiB), 1..20 forces an index
+        of that size whatever the table's, first built after first_after_edges edges and then
+        every rebuild_every_folds folds."""
+        _check(lib().gs_set_hot_index(self._h, int(log2_entries), int(first_after_edges), int(rebuild_every_folds)))
+
+    def hot_index_stats(self):
+        """gs_hot_index_stats: builds queued, entries the live index holds, log2 of its size
+        (0: none), refreshes queued."""
+        a = (_u64 * 4)()
+        _check(lib().gs_hot_index_stats(self._h, a))
+        return dict(zip(("builds", "entries", "log2_entries", "refreshes"), list(a)))
+
     def kernel_stats(self, name):
         n = _u64()
         ms = ctypes.c_double()
@@ -811,7 +830,7 @@ class Summary:
         a = (_u64 * 16)()
         _check(lib().gs_debug_counters(self._h, a, 16))
         keys = ("edges", "key_cas", "key_cas_lost", "ttas", "shortcut", "same_root", "find_loads", "hooks_ok",
-                "extra_probes")
+                "extra_probes", "hot_hits", "hot_fallbacks")
         return dict(zip(keys, list(a)))
 
     def table_capacity(self):

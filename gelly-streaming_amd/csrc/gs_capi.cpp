@@ -159,6 +159,106 @@ void reset_capacity_tracking(gs_summary* h, uint64_t nv) {
   h->rep_pending_edges = 0;
 }
 
+// ---- hot index of the plain CC fold (gs_hot_k.hip) ----
+// Defaults from the calibration under concurrency (profiles/hot_index_calib.txt): 2^16 entries
+// (1 MiB, inside every XCD's L2); never more by default (2^17: a wash, 2^18: slower,
+// profiles/r04_calib_hot.txt). A table below 256 MiB probes fast enough without it.
+constexpr int kHotLog2 = 16;
+constexpr int kHotMaxLog2 = 20;
+constexpr uint64_t kHotFirstEdges = 1ull << 26;
+constexpr uint32_t kHotEvery = 2048;
+constexpr uint32_t kHotRefreshPerBuild = 16;  // refreshes between two builds (every / 16 folds apart)
+constexpr uint64_t kHotMinTableBytes = 256ull << 20;
+constexpr size_t kHotSampleEdges = 1u << 18;  // of the sampled micro-batch
+
+// log2 entries of the index this summary's plain folds use as it is set up now (0: none)
+int hot_log2(const gs_summary* h) {
+  if (h->kind != GS_KIND_CC || h->hot_cfg < 0) return 0;
+  if (h->track || h->changes || h->srv_on || h->side || h->group_lanes) return 0;
+  if (h->hot_cfg > 0) return h->hot_cfg;
+  if (h->cap * sizeof(gs::Slot) < kHotMinTableBytes) return 0;
+  return kHotLog2;
+}
+
+// The life of the table ends (reset, rebuild, combine, deserialize: slots or links are rewritten
+// outside k_fold): no index, and the build cadence starts again. Called with every lane joined
+// onto the handle stream, so whatever still reads or builds a buffer is ordered before the work
+// that follows.
+void hot_drop(gs_summary* h) {
+  h->hot_live = -1;
+  h->hot_building = -1;
+  h->hot_read_on[0] = h->hot_read_on[1] = false;
+  h->hot_edges = 0;
+  h->hot_folds = 0;
+  h->hot_folds_r = 0;
+}
+
+// Before a fold that may use the index: a finished build is adopted. The folds queued so far
+// read the buffer it replaces; an event behind them on every stream guards its next rewrite.
+int hot_before_fold(gs_summary* h) {
+  if (h->hot_building < 0 || hipEventQuery(h->hot_built) != hipSuccess) return GS_OK;
+  const int old = h->hot_live;
+  h->hot_live = h->hot_building;
+  h->hot_building = -1;
+  if (old < 0) return GS_OK;
+  for (int i = 0; i <= gs_summary::kLanes; ++i) {
+    hipStream_t st = i < gs_summary::kLanes ? (hipStream_t)h->lane[i] : (hipStream_t)h->stream;
+    if (i < gs_summary::kLanes && !h->lane[i]) continue;
+    GS_HIP(hipEventRecord(h->hot_read[old][i], st));
+  }
+  h->hot_read_on[old] = true;
+  return GS_OK;
+}
+
+// After a fold of c edges queued on st (hl = hot_log2(h) > 0): when a build is due it is queued
+// behind that fold, on its stream, from its edges, into the buffer no fold reads. No fold waits
+// for it: the folds go on with the live buffer (or none) until hot_before_fold sees it done.
+// Between two builds, every 1/16 of their distance, a refresh renews the live entries'
+// ancestors the same way (a cadence below 16 folds needs none).
+int hot_after_fold(gs_summary* h, const int64_t* src, const int64_t* dst, size_t c, size_t stride, hipStream_t st,
+                   int hl) {
+  h->hot_edges += c;
+  h->hot_folds++;
+  h->hot_folds_r++;
+  if (h->hot_building >= 0) return GS_OK;
+  const uint64_t first = h->hot_cfg ? h->hot_first : kHotFirstEdges;
+  const uint32_t every = h->hot_cfg ? h->hot_every : kHotEvery;
+  const bool build = h->hot_live < 0 ? h->hot_edges >= first : h->hot_folds >= every;
+  const uint32_t refresh_every = every / kHotRefreshPerBuild;
+  if (!build && !(h->hot_live >= 0 && refresh_every && h->hot_folds_r >= refresh_every)) return GS_OK;
+  if (h->hot_alloc_log2 != hl) {  // first use (gs_set_hot_index freed the buffers of another size)
+    h->hot_alloc_log2 = 0;
+    for (auto& b : h->hot_buf) GS_HIP(b.alloc(1ull << hl));
+    GS_HIP(h->hot_scratch.alloc(gs::hot_scratch_words(hl)));
+    if (!h->hot_built) {
+      GS_HIP(h->hot_built.create());
+      for (auto& r : h->hot_read)
+        for (Event& e : r) GS_HIP(e.create());
+    }
+    h->hot_alloc_log2 = hl;
+  }
+  const int b = h->hot_live < 0 ? 0 : h->hot_live ^ 1;
+  if (h->hot_read_on[b]) {
+    for (int i = 0; i <= gs_summary::kLanes; ++i)
+      if (i == gs_summary::kLanes || h->lane[i]) GS_HIP(hipStreamWaitEvent(st, h->hot_read[b][i], 0));
+    h->hot_read_on[b] = false;
+  }
+  if (build) {
+    gs::launch_hot_build(h->table(), src, dst, (uint32_t)std::min(c, kHotSampleEdges), (uint32_t)stride, h->hot_buf[b],
+                         hl, h->hot_scratch, st);
+    h->hot_folds = 0;
+    h->hot_builds++;
+  } else {
+    gs::launch_hot_refresh(h->table(), h->hot_buf[h->hot_live], h->hot_buf[b], hl, st);
+    h->hot_refreshes++;
+  }
+  GS_HIP(hipGetLastError());
+  GS_HIP(hipEventRecord(h->hot_built, st));
+  h->hot_building = b;
+  h->hot_folds_r = 0;
+  return GS_OK;
+}
+
 }  // namespace
 
 // gs_create's table for a hint: kSlotsPerHintedVertex slots per expected vertex, a power of
@@ -190,6 +290,7 @@ int alloc_table(gs_summary* h, uint64_t cap, bool keep_delta = false) {
   GS_HIP(h->tab.alloc(cap + 1));
   if (int rc = alloc_vlist(h)) return rc;
   memset(h->h_flags, 0, 16);  // the device flags are cleared below (no kernel of the old table runs)
+  hot_drop(h);
   if (keep_delta) {
     GS_HIP(hipMemsetAsync(h->ctr, 0, gs::ctr_index(gs::CTR_DELTA) * 4, h->stream));
     GS_HIP(hipMemsetAsync(h->ctr + gs::ctr_index(gs::CTR_FAIL), 0,
@@ -607,6 +708,12 @@ int fold_device_impl(gs_summary* h, const int64_t* src, const int64_t* dst, cons
     if (int rc = join_pipe_lanes(h)) return rc;  // the side stream is NOT joined: union commutes
   }
   const bool sign = h->kind == GS_KIND_SIGNED;
+  // the hot index serves the ordinary plain fold only (its own arrays, capacity-checked, on the
+  // handle stream or a pipelining lane)
+  const int hot = (check_cap && !track && !fs.take_out && fs.rows == 0 && !fs.on_side && fs.lane < 0 && !fs.n_dev &&
+                   stride != 3)
+                      ? hot_log2(h)
+                      : 0;
   for (size_t off = 0, c = 0; off < n; off += c) {
     const bool head = young_head && off == 0;
     c = head ? ((size_t)1 << young_head_log2) : std::min<size_t>(kMaxChunk, n - off);
@@ -689,6 +796,13 @@ int fold_device_impl(gs_summary* h, const int64_t* src, const int64_t* dst, cons
       f.rep_claim = h->rep_pending[rs];
       f.rep_epoch = (unsigned)(h->rep_epoch & 7u);
     }
+    if (hot) {
+      if (int rc = hot_before_fold(h)) return rc;
+      if (h->hot_live >= 0 && h->hot_alloc_log2 == hot) {
+        f.hot.e = h->hot_buf[h->hot_live];
+        f.hot.shift = 64 - hot;
+      }
+    }
     {
       Prof p(h, KID_FOLD, st);
       gs::launch_fold(sign, track, h->table(), h->delta(), f, st);
@@ -709,6 +823,8 @@ int fold_device_impl(gs_summary* h, const int64_t* src, const int64_t* dst, cons
       if (fs.n_dev && !fs.take_out)
         if (int rc = launch_report_now(h, rs, st)) return rc;
     }
+    if (hot)
+      if (int rc = hot_after_fold(h, f.src, f.dst, c, stride, st, hot)) return rc;
   }
   return GS_OK;
 }
@@ -862,6 +978,7 @@ int gs_reset(gs_handle h) {
   // that fold's epoch and surfaces at the next check
   memset(h->h_flags, 0, 16);
   h->vlist_ok = true;
+  hot_drop(h);
   reset_capacity_tracking(h, 0);
   for (uint64_t& f : h->delta_fill_ub) f = 0;
   h->deg_total = 0;
@@ -884,6 +1001,7 @@ int gs_reset_config(gs_handle h) {
   h->dedup = false;
   h->pipe_depth = 1;
   h->lane_next = 0;
+  h->hot_cfg = 0;  // the hot index's default rule (gs_reset below drops a live index)
   return gs_reset(h);
 }
 
@@ -1434,6 +1552,7 @@ int gs_combine(gs_handle dst, gs_handle src) {
   }
   DeviceGuard g(dst->device);
   if (int rc = join_lanes(dst)) return rc;
+  hot_drop(dst);
   GS_HIP(hipStreamWaitEvent(dst->stream, src->xs.ready, 0));
   gs_summary* rows = src;
   if (dst->device != src->device) {  // rows to dst's own scratch over xGMI
@@ -1467,6 +1586,7 @@ int gs_combine_exported_device(gs_handle h, const int64_t* v, const int64_t* lab
   if (n && h->kind == GS_KIND_SIGNED && !parity) return fail(GS_ERR_INVALID, "a signed summary needs parity");
   DeviceGuard g(h->device);
   if (int rc_ = join_lanes(h)) return rc_;
+  hot_drop(h);
   if (failed) {  // the verdict is the AND (BipartitenessCheck.combineFunction -> Candidates.merge :79-81)
     GS_HIP(hipMemsetAsync(h->ctr + gs::ctr_index(gs::CTR_FAIL), 1, 1, h->stream));
     return GS_OK;
@@ -1909,6 +2029,44 @@ int gs_set_pipelining(gs_handle h, int depth) {
   if (int rc_ = ensure_lanes(h, depth)) return rc_;
   h->pipe_depth = depth;
   h->lane_next = 0;
+  return GS_OK;
+}
+
+int gs_set_hot_index(gs_handle h, int log2_entries, uint64_t first_after_edges, uint32_t rebuild_every_folds) {
+  if (int rc = check_any(h)) return rc;
+  if (h->kind != GS_KIND_CC) return fail(GS_ERR_INVALID, "the hot index serves connected-components summaries only");
+  if (log2_entries > kHotMaxLog2) return fail(GS_ERR_INVALID, "hot index: at most 2^20 entries");
+  DeviceGuard g(h->device);
+  if (int rc = join_lanes(h)) return rc;
+  GS_HIP(hipStreamSynchronize(h->stream));  // nothing reads or builds a buffer any more
+  hot_drop(h);
+  if (h->hot_alloc_log2 != (log2_entries > 0 ? log2_entries : kHotLog2)) {
+    h->hot_alloc_log2 = 0;
+    for (auto& b : h->hot_buf) b.reset();
+    h->hot_scratch.reset();
+  }
+  h->hot_cfg = log2_entries < 0 ? -1 : log2_entries;
+  h->hot_first = first_after_edges;
+  h->hot_every = rebuild_every_folds;
+  return GS_OK;
+}
+
+int gs_hot_index_stats(gs_handle h, uint64_t* out4) {
+  if (int rc = check_any(h)) return rc;
+  if (!out4) return fail(GS_ERR_INVALID, "out is null");
+  DeviceGuard g(h->device);
+  if (int rc = join_lanes(h)) return rc;
+  GS_HIP(hipStreamSynchronize(h->stream));  // a queued build is done
+  if (int rc = hot_before_fold(h)) return rc;
+  out4[0] = h->hot_builds;
+  out4[1] = 0;
+  out4[2] = h->hot_live >= 0 ? (uint64_t)h->hot_alloc_log2 : 0;
+  out4[3] = h->hot_refreshes;
+  if (h->hot_live >= 0) {  // the entries the live index holds
+    std::vector<gs::HotEntry> e(1ull << h->hot_alloc_log2);
+    GS_HIP(hipMemcpy(e.data(), h->hot_buf[h->hot_live], e.size() * sizeof(gs::HotEntry), hipMemcpyDeviceToHost));
+    for (const gs::HotEntry& x : e) out4[1] += x.slot != gs::kNoSlot;
+  }
   return GS_OK;
 }
 

@@ -99,6 +99,8 @@ enum CounterBlock : int {
   CTR_DBG_FINDLD,                // parent loads of the finds (fold phase, before the hook)
   CTR_DBG_HOOKOK,                // hooks whose CAS joined two trees
   CTR_DBG_PROBES,                // extra linear-probe loads (beyond each endpoint's first)
+  CTR_DBG_HOTHIT,                // hot index: edges settled by index answers (no table access for a hit side)
+  CTR_DBG_HOTFALL,               // hot index: edges with a hit whose shortcut test failed (ordinary probes follow)
   CTR_DBG_LAST_,
   CTR_COUNT
 };
@@ -174,6 +176,33 @@ __device__ __forceinline__ void load_slot(const Slot* p, int64_t& key, uint32_t&
   const uint4 v = *reinterpret_cast<const uint4*>(p);
   key = (int64_t)(((uint64_t)v.y << 32) | v.x);
   link = v.z;
+}
+
+// Hot index (gs_hot_k.hip): a direct-mapped, L2-sized table of the stream's
+// most frequent ids, probed by the plain CC fold before the relabel table. An entry names its
+// key's slot and a slot that was an ancestor of it when the entry was built (its root then).
+// Within one life of the table a key's slot never changes and an ancestor stays an ancestor
+// (links only move to ancestors, hooks only give a root a parent), so two slots with a common
+// ancestor are in one component for good: an entry may settle an edge, and is used for nothing
+// else. An empty entry has slot == kNoSlot; kEmpty is never a key here (its vertex lives in r0).
+struct alignas(16) HotEntry {
+  int64_t key;
+  uint32_t slot;
+  uint32_t anc;
+};
+struct HotIndex {
+  const HotEntry* e = nullptr;  // null: no live index
+  int shift = 63;               // 64 - log2(entries)
+};
+__device__ __forceinline__ uint32_t hot_pos(int64_t key, int shift) {
+  return (uint32_t)(((uint64_t)key * 0xD6E8FEB86659FD93ull) >> shift);
+}
+// the entry at p as one 16-B load; true when it answers `key`
+__device__ __forceinline__ bool hot_load(const HotEntry* p, int64_t key, uint32_t& slot, uint32_t& anc) {
+  const uint4 v = *reinterpret_cast<const uint4*>(p);
+  slot = v.z;
+  anc = v.w;
+  return (int64_t)(((uint64_t)v.y << 32) | v.x) == key && v.z != kNoSlot && key != kEmpty;
 }
 
 __device__ __forceinline__ uint32_t load_link_fresh(const Slot* p) {

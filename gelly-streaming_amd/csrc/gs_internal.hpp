@@ -327,6 +327,25 @@ struct gs_summary : gsi::StreamOwner {
   int last_lane = -1;  // lane of the most recently queued fold (the label pass runs there)
   bool lanes_dirty = false;
   bool export_ctr_zero = false;  // CTR_EXPORT is zero behind the queued work (no fill before an export)
+  // hot index of the plain CC fold (gs_set_hot_index; gs_hot_k.hip): two
+  // buffers, one read by the folds while a build fills the other on the lane that folded the
+  // sampled batch. hot_drop ends an index with the life of the table it was built from.
+  int hot_cfg = 0;             // log2 entries asked for: < 0 off, 0 the default rule, > 0 forced
+  uint64_t hot_first = 0;      // first build after this many edges of the table's life
+  uint32_t hot_every = 0;      // then a build every this many folds
+  gsi::DevBuf<gs::HotEntry> hot_buf[2];  // (first use: the first build)
+  gsi::DevBuf<unsigned long long> hot_scratch;
+  int hot_alloc_log2 = 0;      // log2 entries the buffers hold (0: none)
+  int hot_live = -1;           // the buffer the folds read (-1: no index)
+  int hot_building = -1;       // the buffer a queued build writes, adopted once hot_built has passed
+  gsi::Event hot_built;
+  gsi::Event hot_read[2][kLanes + 1];  // behind every stream's last fold that read the buffer (lanes, handle)
+  bool hot_read_on[2] = {false, false};
+  uint64_t hot_edges = 0;      // edges of the index's folds in this life of the table
+  uint32_t hot_folds = 0;      // such folds since the last build was queued
+  uint32_t hot_folds_r = 0;    //   ... since the last build or refresh was
+  uint64_t hot_builds = 0;     // builds queued since create
+  uint64_t hot_refreshes = 0;  // refreshes queued since create
   // side stream (a multi-GPU group's apply stream): folds of remote rows run there,
   // overlapping this rank's own folds; every reader joins it (join_lanes), the
   // handle's own folds do not (union commutes). Views: the group owns both and takes them

@@ -153,6 +153,7 @@ struct FoldArgs {
   unsigned long long* rep_out = nullptr;
   unsigned long long rep_claim = 0;
   unsigned rep_epoch = 0;
+  HotIndex hot;  // HOT: the live hot index
 };
 
 // The capacity report (k_report below) by one wave: edges covered += n, then the
@@ -419,13 +420,14 @@ __device__ __forceinline__ bool take_tail(const Table& t, const FoldArgs& a, con
   return true;
 }
 
-template <bool SIGNED, bool TRACK, bool TAKE, bool ROWS = false>
+template <bool SIGNED, bool TRACK, bool TAKE, bool ROWS = false, bool HOT = false>
 __device__ __forceinline__ void fold_block(const Table& t, const Delta& D, const FoldArgs& a, uint32_t blk,
                                            bool failed, unsigned long long n_word, uint32_t* dbg);
 
 // ROWS: a group's gathered remote rows (exchange layout); they keep the insert re-read
 // (profiles/r04_rank_replay.txt section 8: 47 M rows fold in 2.86 ms with it, 3.94 without)
-template <bool SIGNED, bool TRACK, bool TAKE, bool ROWS = false>
+// HOT: the plain CC fold with a live hot index (fold_block)
+template <bool SIGNED, bool TRACK, bool TAKE, bool ROWS = false, bool HOT = false>
 __global__ __launch_bounds__(kFoldBS) void k_fold(Table t, Delta D, FoldArgs a) {
   __shared__ int64_t lrec[TAKE ? kFoldBS * 3 : 1];
   __shared__ uint32_t lcnt;
@@ -457,9 +459,9 @@ __global__ __launch_bounds__(kFoldBS) void k_fold(Table t, Delta D, FoldArgs a) 
   const bool failed = SIGNED && __builtin_amdgcn_readfirstlane(t.ctr[ctr_index(CTR_FAIL)]) != 0;
   if (failed && !TAKE) return;
 #ifdef GS_BLOCKLOG
-  fold_block<SIGNED, TRACK, TAKE, ROWS>(t, D, a, blockIdx.x, failed, n_word, SIGNED ? nullptr : dbg);
+  fold_block<SIGNED, TRACK, TAKE, ROWS, HOT>(t, D, a, blockIdx.x, failed, n_word, SIGNED ? nullptr : dbg);
 #else
-  fold_block<SIGNED, TRACK, TAKE, ROWS>(t, D, a, blockIdx.x, failed, n_word, nullptr);
+  fold_block<SIGNED, TRACK, TAKE, ROWS, HOT>(t, D, a, blockIdx.x, failed, n_word, nullptr);
 #endif
 #ifdef GS_BLOCKLOG
   if (!SIGNED) {
@@ -493,7 +495,7 @@ __global__ __launch_bounds__(kFoldBS) void k_fold(Table t, Delta D, FoldArgs a) 
 
 // The fold of one block's edges (edge i = blk * kFoldBS + threadIdx.x): relabel probes,
 // shortcut, finds, wave-combined hooks. Shared by k_fold and the resident window server.
-template <bool SIGNED, bool TRACK, bool TAKE, bool ROWS>
+template <bool SIGNED, bool TRACK, bool TAKE, bool ROWS, bool HOT>
 __device__ __forceinline__ void fold_block(const Table& t, const Delta& D, const FoldArgs& a, uint32_t blk,
                                            bool failed, unsigned long long n_word, uint32_t* dbg) {
   const int shard = (int)((blk + a.shard0) & (kShards - 1));
@@ -517,7 +519,39 @@ __device__ __forceinline__ void fold_block(const Table& t, const Delta& D, const
   const uint32_t hu = hash_slot(ks, t.shift), hv = hash_slot(kd, t.shift);
   int64_t k0u = 0, k0v = 0;
   uint32_t l0u = 0, l0v = 0;
-  if (valid) {
+  if (HOT) {
+    // Hot index: both index probes go out first, together; an endpoint's table probe only if its
+    // index probe missed. With a hit the edge is tested as the shortcut below tests it -- a hit
+    // side's slot and ancestor for its slot and parent, a missed side's first-probe slot and
+    // link -- and a common ancestor settles it: the vertices exist and are in one component, so
+    // the thread has nothing to insert, find, hook or store. A test that fails (or a missed side
+    // whose first probe is not its key) discards the index answers: the hit sides are probed in
+    // the table and the edge goes on as without an index.
+    static_assert(!HOT || (!SIGNED && !TRACK && !TAKE && !ROWS), "the hot index serves the plain CC fold only");
+    uint32_t xsu = 0, xau = 0, xsv = 0, xav = 0;
+    bool hitu = false, hitv = false;
+    if (valid) {
+      const HotEntry *eu = a.hot.e + hot_pos(ks, a.hot.shift), *ev = a.hot.e + hot_pos(kd, a.hot.shift);
+      hitu = hot_load(eu, ks, xsu, xau);
+      hitv = hot_load(ev, kd, xsv, xav);
+      if (!hitu) load_slot(t.tab + hu, k0u, l0u);
+      if (!hitv) load_slot(t.tab + hv, k0v, l0v);
+    }
+    if (hitu || hitv) {
+      const bool oku = hitu || (k0u == ks && ks != kEmpty), okv = hitv || (k0v == kd && kd != kEmpty);
+      const uint32_t s_u = hitu ? xsu : hu, p_u = hitu ? xau : l0u >> 1;
+      const uint32_t s_v = hitv ? xsv : hv, p_v = hitv ? xav : l0v >> 1;
+      if (oku && okv && (s_u == s_v || p_u == p_v || p_u == s_v || p_v == s_u)) {
+        GS_DBG(CTR_DBG_EDGES);
+        GS_DBG(CTR_DBG_HOTHIT);
+        valid = false;  // done: the rest of the block's work sees an idle lane
+      } else {
+        GS_DBG(CTR_DBG_HOTFALL);
+        if (hitu) load_slot(t.tab + hu, k0u, l0u);
+        if (hitv) load_slot(t.tab + hv, k0v, l0v);
+      }
+    }
+  } else if (valid) {
     load_slot(t.tab + hu, k0u, l0u);
     load_slot(t.tab + hv, k0v, l0v);
   }
@@ -1233,6 +1267,7 @@ void launch_fold(bool sign, bool track, const Table& t, const Delta& D, const Fo
   a.rep_out = f.rep_out;
   a.rep_claim = f.rep_claim;
   a.rep_epoch = f.rep_epoch;
+  a.hot = f.hot;
   const dim3 g((f.n + kFoldBS - 1) / kFoldBS), b(kFoldBS);
   if (f.take_out) {  // fused window take (always tracked)
     if (sign) hipLaunchKernelGGL((k_fold<true, true, true>), g, b, 0, st, t, D, a);
@@ -1242,6 +1277,10 @@ void launch_fold(bool sign, bool track, const Table& t, const Delta& D, const Fo
   if ((f.rows || f.stride == 3) && !track) {  // other replicas' rows (a group's exchange layout, or 24-B records)
     if (sign) hipLaunchKernelGGL((k_fold<true, false, false, true>), g, b, 0, st, t, D, a);
     else hipLaunchKernelGGL((k_fold<false, false, false, true>), g, b, 0, st, t, D, a);
+    return;
+  }
+  if (!sign && !track && f.hot.e) {
+    hipLaunchKernelGGL((k_fold<false, false, false, false, true>), g, b, 0, st, t, D, a);
     return;
   }
   if (!sign && !track) hipLaunchKernelGGL((k_fold<false, false, false>), g, b, 0, st, t, D, a);

@@ -33,6 +33,7 @@ struct FoldLaunch {
   unsigned long long* rep_out = nullptr;
   unsigned long long rep_claim = 0;
   unsigned rep_epoch = 0;
+  HotIndex hot;  // the live hot index of a plain CC fold (e null: none)
 };
 
 // Resident window server (latency path, gs_set_window_server): the host posts each
@@ -103,6 +104,14 @@ void launch_signal(unsigned long long* out, unsigned long long seq, const uint32
 void launch_find_one(const Table& t, int64_t key, int64_t* out, hipStream_t st);
 void launch_find_batch(const Table& t, const int64_t* v, uint64_t n, int64_t* label, uint8_t* found, uint8_t* parity,
                        hipStream_t st);
+
+// hot index build (gs_hot_k.hip): out[2^log2] from the first n edges of a micro-batch; scratch
+// holds hot_scratch_words(log2) words
+uint64_t hot_scratch_words(int log2_entries);
+void launch_hot_build(const Table& t, const int64_t* src, const int64_t* dst, uint32_t n, uint32_t stride,
+                      HotEntry* out, int log2_entries, unsigned long long* scratch, hipStream_t st);
+// out = the entries of `in` with their ancestors found again
+void launch_hot_refresh(const Table& t, const HotEntry* in, HotEntry* out, int log2_entries, hipStream_t st);
 
 // change emission (gs_changes_k.hip)
 void launch_iota(uint32_t* nxt, uint64_t n, hipStream_t st);

@@ -8,12 +8,17 @@
 //   B : hot probe first; main probe only on a hot miss
 //   C : B with non-temporal main-table loads (leave the L2 to hot lines)
 //   D : A with non-temporal main loads (reference for C)
+//   M : direct-mapped hot table (one 16-B probe, the highest-count key per slot)
+// Last, A against M1 with entries {key, slot, anc} under the pipelined fold's conditions: three
+// probe kernels in flight on three streams (profiles/hot_index_calib.txt).
 // Build: hipcc -O3 --offload-arch=gfx950 -Iinclude tools/calib_hot.hip
 //          -Lgelly-streaming_amd/lib -lgs_summary -Wl,-rpath,$PWD/gelly-streaming_amd/lib -o tools/bin/calib_hot
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <time.h>
+#include <algorithm>
 #include <vector>
 #include "gs_gen.h"
 
@@ -213,6 +218,53 @@ __global__ __launch_bounds__(256) void k_probe_k(const uint4* tab, uint32_t mask
   if (acc == 0x12345671u) sink[0] = acc;
 }
 
+// The fold's index entry {key (8), slot (4), anc (4)}: after k_dm_place, look every placed key up
+// in the main table and write its slot into z and w (the calibration table has no forest, so the
+// ancestor is the slot itself); a key the main table does not hold leaves the index.
+__global__ void k_dm_fill(uint4* hot, uint32_t H, const uint4* tab, uint32_t mask, int sh, unsigned long long* nfill) {
+  const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= H) return;
+  const int64_t key = key_of(hot[e]);
+  if (key == kEmpty) return;
+  uint32_t h = hmain(key, sh), slot = ~0u;
+  for (uint32_t p = 0; p <= mask; ++p) {
+    const int64_t k = key_of(tab[h]);
+    if (k == key) slot = h;
+    if (k == key || k == kEmpty) break;
+    h = (h + 1) & mask;
+  }
+  uint4 v = hot[e];
+  if (slot == ~0u) v.x = 0u, v.y = 0x80000000u;  // kEmpty
+  else atomicAdd(nfill, 1ull);
+  v.z = slot;
+  v.w = slot;
+  hot[e] = v;
+}
+
+// What the fold would do per edge: both index probes first, the main probe only for a side that
+// missed; a hit side brings {slot, anc} from the index, a missed side {slot, link} from the table.
+template <bool HOT>
+__global__ __launch_bounds__(256) void k_probe_ix(const uint4* tab, uint32_t mask, int sh, const uint4* hot, int hsh,
+                                                  const int64_t* src, const int64_t* dst, uint32_t n, uint32_t* sink) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int64_t ku = __builtin_nontemporal_load(src + i), kv = __builtin_nontemporal_load(dst + i);
+  uint32_t su = ~0u, sv = ~0u, pu = 0, pv = 0;
+  if (HOT) {
+    const uint4 a = hot[hhot(ku, hsh)], b = hot[hhot(kv, hsh)];
+    if (key_of(a) == ku) su = a.z, pu = a.w;
+    if (key_of(b) == kv) sv = b.z, pv = b.w;
+  }
+  const uint32_t hu = hmain(ku, sh), hv = hmain(kv, sh);
+  uint4 a{}, b{};
+  const bool mu = su == ~0u, mv = sv == ~0u;
+  if (mu) a = tab[hu];
+  if (mv) b = tab[hv];
+  if (mu) pu = probe_main<false>(tab, mask, sh, ku, hu, a), su = pu >> 1;  // (the table's link word is slot << 1)
+  if (mv) pv = probe_main<false>(tab, mask, sh, kv, hv, b), sv = pv >> 1;
+  if (((su ^ sv) + (pu ^ pv)) == 0x12345671u) sink[0] = su;
+}
+
 int main(int argc, char** argv) {
   setvbuf(stdout, nullptr, _IONBF, 0);
   const int logs = 27, scale = 26;
@@ -354,5 +406,70 @@ int main(int argc, char** argv) {
       if (run(34, logH, "M4 direct-mapped hot, 4 edges/thread")) return 1;
     }
   }
+  // Under the fold's real conditions: three probe kernels in flight on three streams over different
+  // batches, as the 3-deep pipelined step runs them. A = main only, M1 = direct-mapped index of
+  // {key, slot, anc} entries first. The variants alternate within every repetition; a repetition is
+  // kRounds passes over the NB batches, timed on the host from the first launch to a device synchronise.
+  constexpr int kStreams = 3, kReps = 7, kRounds = 8, kVar = 3;
+  hipStream_t st[kStreams];
+  for (int i = 0; i < kStreams; ++i) CK(hipStreamCreateWithFlags(&st[i], hipStreamNonBlocking));
+  uint4* hotv[kVar] = {nullptr, nullptr, nullptr};
+  const int logv[kVar] = {0, 15, 16};
+  const char* namev[kVar] = {"A  main only", "M1 index 2^15", "M1 index 2^16"};
+  printf("3 streams, %d x %u batches per repetition, %d repetitions, variants alternated\n", kRounds, NB, kReps);
+  for (int v = 1; v < kVar; ++v) {
+    const uint64_t H = 1ull << logv[v];
+    uint64_t T = 63, acc = 0;
+    for (int c = 63; c >= 2; --c) {
+      if (acc + hh[c] > H) break;
+      acc += hh[c];
+      T = c;
+    }
+    CK(hipMalloc(&hotv[v], H * 16));
+    CK(hipMemset(hotv[v], 0, H * 16));
+    CK(hipMemset2D(reinterpret_cast<char*>(hotv[v]) + 7, 16, 0x80, 1, H));
+    CK(hipMemset(best, 0, H * 8));
+    CK(hipMemset(nsel, 0, 8));
+    k_dm_max<<<2048, 256>>>(cnt, cslots, T, best, 64 - logv[v]);
+    k_dm_place<<<2048, 256>>>(cnt, cslots, T, best, hotv[v], 64 - logv[v], nsel);
+    CK(hipMemset(nsel, 0, 8));
+    k_dm_fill<<<(uint32_t)(H / 256), 256>>>(hotv[v], (uint32_t)H, tab, (uint32_t)(slots - 1), sh, nsel);
+    unsigned long long ns = 0;
+    CK(hipMemcpy(&ns, nsel, 8, hipMemcpyDeviceToHost));
+    printf("index 2^%d entries (%llu KiB): T=%llu, %llu entries filled\n", logv[v], (unsigned long long)(H * 16 >> 10),
+           (unsigned long long)T, ns);
+  }
+  double us[kVar][kReps];
+  for (int rep = -1; rep < kReps; ++rep) {  // repetition -1 warms up and is not kept
+    for (int v = 0; v < kVar; ++v) {
+      CK(hipDeviceSynchronize());
+      timespec t0, t1;
+      clock_gettime(CLOCK_MONOTONIC, &t0);
+      for (int r = 0; r < kRounds; ++r)
+        for (uint32_t b = 0; b < NB; ++b) {
+          const int64_t* s = src + (size_t)b * B;
+          const int64_t* d = dst + (size_t)b * B;
+          hipStream_t q = st[(r * NB + b) % kStreams];
+          if (v == 0) k_probe_ix<false><<<B / 256, 256, 0, q>>>(tab, (uint32_t)(slots - 1), sh, nullptr, 0, s, d, B, sink);
+          else k_probe_ix<true><<<B / 256, 256, 0, q>>>(tab, (uint32_t)(slots - 1), sh, hotv[v], 64 - logv[v], s, d, B, sink);
+        }
+      CK(hipDeviceSynchronize());
+      clock_gettime(CLOCK_MONOTONIC, &t1);
+      if (rep >= 0) us[v][rep] = ((t1.tv_sec - t0.tv_sec) * 1e9 + (t1.tv_nsec - t0.tv_nsec)) * 1e-3 / (kRounds * NB);
+    }
+  }
+  double med[kVar], spread[kVar];
+  for (int v = 0; v < kVar; ++v) {
+    std::vector<double> s(us[v], us[v] + kReps);
+    std::sort(s.begin(), s.end());
+    med[v] = s[kReps / 2];
+    spread[v] = s[kReps - 1] - s[0];
+    printf("  %-16s us/batch:", namev[v]);
+    for (int rep = 0; rep < kReps; ++rep) printf(" %6.2f", us[v][rep]);
+    printf("  median %6.2f  min %6.2f  max %6.2f  spread %5.2f\n", med[v], s[0], s[kReps - 1], spread[v]);
+  }
+  for (int v = 1; v < kVar; ++v)
+    printf("  %s vs A: %+.2f us/batch (%+.1f %%), 3 x A's spread = %.2f -> %s\n", namev[v], med[v] - med[0],
+           100.0 * (med[v] - med[0]) / med[0], 3 * spread[0], med[0] - med[v] > 3 * spread[0] ? "FASTER" : "not faster");
   return 0;
 }

@@ -133,8 +133,14 @@ TARGET = {"rmat-cc": ("k_fold<false, false, false>", "rmat26-cc-stream", "pmc_fo
 kname, wname, fname = TARGET
 if workload == "ingest" and "k_parse_fused" in out["kernels"]:  # the one-pass parse (round 4 default)
     kname = "k_parse_fused"
-if kname not in out["kernels"] and kname.endswith(">") and kname[:-1] + ", false>" in out["kernels"]:
-    kname = kname[:-1] + ", false>"  # k_fold<SIGNED, TRACK, TAKE, ROWS> (round 4: the ROWS instantiation)
+for _ in range(2):  # k_fold<SIGNED, TRACK, TAKE, ROWS, HOT> (round 4: the ROWS flag; then the hot index's)
+    if kname not in out["kernels"] and kname.endswith(">"):
+        kname = kname[:-1] + ", false>"
+if kname.endswith(", false>") and kname[:-len("false>")] + "true>" in out["kernels"]:
+    # the plain CC fold with a live hot index: most of a step's launches once the index is built
+    hot = kname[:-len("false>")] + "true>"
+    if out["kernels"][hot].get("calls", 0) > out["kernels"].get(kname, {}).get("calls", 0):
+        kname = hot
 r = out["kernels"].get(kname, {})
 if "derived" in r and r["derived"].get("read_requests"):
     import hashlib
