@@ -83,6 +83,10 @@ EXPORTED_SYMBOLS = (
     "gs_distinct_edges", "gs_distinct_rank_device", "gs_distinct_contains_device", "gs_distinct_sync",
     "gs_distinct_get_stream", "gs_distinct_wait_stream", "gs_testing_distinct_stats",
     "gs_testing_distinct_phases",
+    "gs_spanner_create", "gs_spanner_destroy", "gs_spanner_reset", "gs_spanner_fold", "gs_spanner_fold_device",
+    "gs_spanner_add", "gs_spanner_within", "gs_spanner_within_device", "gs_spanner_combine", "gs_spanner_count",
+    "gs_spanner_export_device", "gs_spanner_export", "gs_spanner_neighbors", "gs_spanner_sync",
+    "gs_spanner_get_stream", "gs_spanner_wait_stream", "gs_testing_spanner_stats",
 )
 
 # Pairs per workgroup of the component export's radix-sort kernels (csrc/gs_sort.hpp kSortTile):
@@ -133,6 +137,14 @@ SLICE_OPS = {"sum": 0, "min": 1, "max": 2, "count": 3}  # gs_slice_op
 # DISTINCT_TILE): the kept entries / edges of a fold are compacted tile by tile.
 DISTINCT_TILE = 2048
 DISTINCT_MODES = {"directed": 0, "undirected": 1}  # gs_distinct_mode
+
+# The k-spanner summary (csrc/gs_spanner_seq.hpp, csrc/gs_spanner.hpp): the range of k, the vertices
+# per side a wave's on-chip sets hold before a search takes the heavy path, the arenas of the
+# heavy path's pool and the rounds before the serial tail.
+SPANNER_MAX_K = 16
+SPANNER_LDS_SET = 256
+SPANNER_ARENAS = 32
+SPANNER_ROUND_CAP = 16
 
 FAIL_BIT = 1 << 62  # count words: a failed signed verdict (GS_FAIL_BIT)
 DIGEST_FAILED = (1 << 64) - 1  # gs_digest of a signed summary whose verdict failed (GS_DIGEST_FAILED)
@@ -313,6 +325,23 @@ def lib():
     L.gs_distinct_wait_stream.argtypes = [_vp, _vp]
     L.gs_testing_distinct_stats.argtypes = [_vp, ctypes.POINTER(_u64)]
     L.gs_testing_distinct_phases.argtypes = [_vp, ctypes.POINTER(_u64)]
+    L.gs_spanner_create.argtypes = [ctypes.POINTER(_vp), ctypes.c_int, ctypes.c_int, _u64]
+    L.gs_spanner_destroy.argtypes = [_vp]
+    L.gs_spanner_reset.argtypes = [_vp]
+    L.gs_spanner_fold.argtypes = [_vp, _vp, _vp, _sz, _vp]
+    L.gs_spanner_fold_device.argtypes = [_vp, _vp, _vp, _sz, _vp, _sz]
+    L.gs_spanner_add.argtypes = [_vp, _vp, _vp, _sz]
+    L.gs_spanner_within.argtypes = [_vp, _vp, _vp, _sz, ctypes.c_int, _vp]
+    L.gs_spanner_within_device.argtypes = [_vp, _vp, _vp, _sz, ctypes.c_int, _vp]
+    L.gs_spanner_combine.argtypes = [_vp, _vp]
+    L.gs_spanner_count.argtypes = [_vp, ctypes.POINTER(_u64), ctypes.POINTER(_u64)]
+    L.gs_spanner_export_device.argtypes = [_vp, _vp, _vp, _sz, ctypes.POINTER(_sz)]
+    L.gs_spanner_export.argtypes = [_vp, _vp, _vp, _sz, ctypes.POINTER(_sz)]
+    L.gs_spanner_neighbors.argtypes = [_vp, _vp, _vp, _vp, _sz, _sz, ctypes.POINTER(_sz), ctypes.POINTER(_sz)]
+    L.gs_spanner_sync.argtypes = [_vp]
+    L.gs_spanner_get_stream.argtypes = [_vp, ctypes.POINTER(_vp)]
+    L.gs_spanner_wait_stream.argtypes = [_vp, _vp]
+    L.gs_testing_spanner_stats.argtypes = [_vp, ctypes.POINTER(_u64)]
     L.gs_testing_set.argtypes = [ctypes.c_int, _i64]
     L.gs_testing_get.argtypes = [ctypes.c_int]
     L.gs_testing_get.restype = _i64
@@ -360,7 +389,8 @@ def digest_rows(v, label, parity=None):
 # include/gs_testing.h: private knobs the tests use (the product reads no environment)
 TESTING_KNOBS = {"server_idle_us": 0, "changes_walk_max": 1, "parse_lb_timeout_us": 2, "group_self_apply": 3,
                  "group_data_lag": 4, "degree_variant": 5, "triangle_variant": 6, "triangle_profile": 7,
-                 "slice_profile": 8, "distinct_profile": 9}
+                 "slice_profile": 8, "distinct_profile": 9, "spanner_round_cap": 10, "spanner_lds_set": 11,
+                 "spanner_arenas": 12}
 
 
 def testing_set(knob, value):
@@ -1454,6 +1484,150 @@ def _cap_of(cap, *arrays):
         if a is not None and not isinstance(a, int):
             return a.numel() if hasattr(a, "numel") else len(a)
     return 0
+
+
+# ---------------------------------------------------------------- k-spanner summary
+class Spanner:
+    """The streaming k-spanner of library/Spanner.java (the gs_spanner_* section of
+    include/gs_summary.h): an arriving edge is accepted into the graph iff its endpoints are more
+    than k edges apart in the graph the edges before it left, exactly in arrival order however
+    the stream is cut into folds. Owns a gs_spanner handle."""
+
+    def __init__(self, k=3, device=0, edge_hint=1 << 16):
+        self.device = device
+        self.k = int(k)
+        h = _vp()
+        _check(lib().gs_spanner_create(ctypes.byref(h), device, int(k), int(edge_hint)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().gs_spanner_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def stream(self):
+        s = _vp()
+        _check(lib().gs_spanner_get_stream(self._h, ctypes.byref(s)))
+        return s.value
+
+    def reset(self):
+        """The graph empty; capacity and k are kept."""
+        _check(lib().gs_spanner_reset(self._h))
+
+    def sync(self):
+        _check(lib().gs_spanner_sync(self._h))
+
+    def wait_stream(self, stream="torch"):
+        if isinstance(stream, str):
+            import torch
+            stream = torch.cuda.current_stream(self.device)
+        raw = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
+        _check(lib().gs_spanner_wait_stream(self._h, raw))
+
+    def fold(self, src, dst):
+        """Fold host edges (int64 arrays) in arrival order; returns the accepted mask (bool)."""
+        s = np.ascontiguousarray(np.asarray(src, dtype=np.int64))
+        d = np.ascontiguousarray(np.asarray(dst, dtype=np.int64))
+        assert s.shape == d.shape
+        acc = np.zeros(len(s), np.uint8)
+        _check(lib().gs_spanner_fold(self._h, s.ctypes.data, d.ctypes.data, len(s), acc.ctypes.data))
+        return acc.astype(bool)
+
+    def fold_device(self, src, dst, accepted=None, n=None, stride=1, after=None):
+        """Fold device-resident edges (torch tensors on this device or raw pointers); `accepted`
+        (optional): a DEVICE uint8 tensor of n bytes, written on the handle's stream; `after`: a
+        stream the edges were written on. The fold synchronises with the host."""
+        if n is None:
+            n = src.numel() // (stride if stride > 1 else 1)
+        if after is not None:
+            self.wait_stream(after)
+        _check(lib().gs_spanner_fold_device(self._h, _ptr(src), _ptr(dst), int(n), _ptr(accepted), int(stride)))
+
+    def add(self, src, dst):
+        """AdjacencyListGraph.addEdge for host edges: each joins the graph unless it is there."""
+        s = np.ascontiguousarray(np.asarray(src, dtype=np.int64))
+        d = np.ascontiguousarray(np.asarray(dst, dtype=np.int64))
+        assert s.shape == d.shape
+        _check(lib().gs_spanner_add(self._h, s.ctypes.data, d.ctypes.data, len(s)))
+
+    def within(self, src, dst, k=None):
+        """boundedBFS(src[i], dst[i], k) on the graph as it stands, host arrays; bool array."""
+        s = np.ascontiguousarray(np.atleast_1d(np.asarray(src, dtype=np.int64)))
+        d = np.ascontiguousarray(np.atleast_1d(np.asarray(dst, dtype=np.int64)))
+        assert s.shape == d.shape
+        out = np.zeros(len(s), np.uint8)
+        _check(lib().gs_spanner_within(self._h, s.ctypes.data, d.ctypes.data, len(s),
+                                       self.k if k is None else int(k), out.ctypes.data))
+        return out.astype(bool)
+
+    def within_device(self, src, dst, out, k=None, n=None):
+        """The same for DEVICE ids into the DEVICE uint8 tensor `out`, queued on self.stream."""
+        n = src.numel() if n is None else n
+        _check(lib().gs_spanner_within_device(self._h, _ptr(src), _ptr(dst), int(n),
+                                              self.k if k is None else int(k), _ptr(out)))
+
+    def combine(self, other):
+        """CombineSpanners: other's edges, ascending by (lo, hi), folded into this spanner with
+        this spanner's k; `other` is unchanged."""
+        _check(lib().gs_spanner_combine(self._h, other._h))
+
+    def count(self):
+        """(edges, vertices) of the graph. Synchronises."""
+        e, v = _u64(), _u64()
+        _check(lib().gs_spanner_count(self._h, ctypes.byref(e), ctypes.byref(v)))
+        return e.value, v.value
+
+    def edges(self):
+        """(lo, hi) numpy int64 arrays: the spanner's edges ascending by (lo, hi)."""
+        got = _sz()
+        n = max(self.count()[0], 1)
+        lo = np.empty(n, np.int64)
+        hi = np.empty(n, np.int64)
+        _check(lib().gs_spanner_export(self._h, lo.ctypes.data, hi.ctypes.data, n, ctypes.byref(got)))
+        return lo[: got.value].copy(), hi[: got.value].copy()
+
+    def edges_device(self, lo, hi):
+        """The same rows into DEVICE arrays (capacity lo.numel()); returns the edge count."""
+        got = _sz()
+        cap = lo.numel() if hasattr(lo, "numel") else len(lo)
+        _check(lib().gs_spanner_export_device(self._h, _ptr(lo), _ptr(hi), cap, ctypes.byref(got)))
+        return got.value
+
+    def neighbors(self):
+        """The adjacency as a CSR of numpy arrays (v, offset, neighbor): vertices ascending, the
+        neighbours of v[i] = neighbor[offset[i]:offset[i + 1]] ascending (getAdjacencyMap())."""
+        e, nv = self.count()
+        v = np.empty(max(nv, 1), np.int64)
+        off = np.zeros(max(nv, 1) + 1, np.uint64)
+        nb = np.empty(max(2 * e, 1), np.int64)
+        gv, ge = _sz(), _sz()
+        _check(lib().gs_spanner_neighbors(self._h, v.ctypes.data, off.ctypes.data, nb.ctypes.data, len(v), len(nb),
+                                          ctypes.byref(gv), ctypes.byref(ge)))
+        return v[: gv.value].copy(), off[: gv.value + 1].astype(np.int64), nb[: ge.value].copy()
+
+    def stats(self):
+        """gs_testing_spanner_stats: the last fold."""
+        out = (_u64 * 6)()
+        _check(lib().gs_testing_spanner_stats(self._h, out))
+        return {"filter_drops": out[0], "pending": out[1], "rounds": out[2], "tail": out[3], "heavy": out[4],
+                "longest_row": out[5]}
 
 
 # ---------------------------------------------------------------- native multi-GPU group

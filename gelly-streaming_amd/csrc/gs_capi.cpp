@@ -69,7 +69,9 @@ hipError_t dfree(void* p) {
 }
 
 // include/gs_testing.h: process-wide test knobs, -1 = unset (the product value)
-std::atomic<int64_t> g_testing[GS_TESTING_KNOBS] = {{-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}};
+std::atomic<int64_t> g_testing[GS_TESTING_KNOBS] = {{-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1},
+                                                  {-1}, {-1}, {-1}, {-1}, {-1}, {-1}};
+static_assert(GS_TESTING_KNOBS == 13, "one initialiser and one product value per knob");
 
 int64_t testing_value(int knob, int64_t product) {
   const int64_t v = g_testing[knob].load(std::memory_order_relaxed);
@@ -2104,7 +2106,7 @@ extern "C" int gs_testing_set(int knob, int64_t value) {
 
 extern "C" int64_t gs_testing_get(int knob) {
   if (knob < 0 || knob >= GS_TESTING_KNOBS) return -1;
-  static const int64_t product[GS_TESTING_KNOBS] = {2000, 1 << 16, 50000, 0, 2, 0, 0, 0, 0, 0};
+  static const int64_t product[GS_TESTING_KNOBS] = {2000, 1 << 16, 50000, 0, 2, 0, 0, 0, 0, 0, 16, 256, 32};
   return gsi::testing_value(knob, product[knob]);
 }
 

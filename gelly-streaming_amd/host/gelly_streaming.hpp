@@ -20,6 +20,8 @@
 //   Candidates                  summaries/Candidates.java:27-196   (GPU-resident signed forest)
 //   ConnectedComponents         library/ConnectedComponents.java:41-134
 //   BipartitenessCheck          library/BipartitenessCheck.java:37-133
+//   AdjacencyListGraph          summaries/AdjacencyListGraph.java:27-140 (GPU-resident adjacency)
+//   Spanner                     library/Spanner.java:40-118
 //
 // Summaries are held by std::shared_ptr (Java object references). A GPU-backed
 // summary buffers its per-edge callbacks (union / merge of a one-edge candidate)
@@ -1153,6 +1155,135 @@ class ExactTriangleCount {
 
  private:
   int device_;
+};
+
+// --------------------------------------------------------------------------
+// k-spanner (gs_summary.h, the gs_spanner_* section)
+// --------------------------------------------------------------------------
+// AdjacencyListGraph (summaries/AdjacencyListGraph.java:27-140) backed by a spanner handle.
+// addEdge and the spanner's per-edge update are buffered and reach the device as one batch on
+// any read, like DisjointSet's unions; a batch holds calls of one kind only, so their order is
+// kept. k is the handle's distance bound: what updateLocal and combine decide by.
+class AdjacencyListGraph {
+ public:
+  explicit AdjacencyListGraph(int k = 3, int device = 0, uint64_t edge_hint = 1 << 10)
+      : k_(k), device_(device), hint_(edge_hint) {}
+  ~AdjacencyListGraph() { gs_spanner_destroy(h_); }
+  AdjacencyListGraph(const AdjacencyListGraph&) = delete;
+  AdjacencyListGraph& operator=(const AdjacencyListGraph&) = delete;
+
+  // addEdge (:46-67): the edge joins the graph, whatever the distance of its endpoints
+  void addEdge(int64_t src, int64_t trg) { push(src, trg, false); }
+  // Spanner.UpdateLocal.foldEdges (Spanner.java:71-77): if (!boundedBFS(src, trg, k)) addEdge
+  void updateLocal(int64_t src, int64_t trg) { push(src, trg, true); }
+  // boundedBFS (:79-116)
+  bool boundedBFS(int64_t src, int64_t trg, int k) {
+    flush();
+    uint8_t out = 0;
+    gs_check(gs_spanner_within(handle(), &src, &trg, 1, k, &out));
+    return out != 0;
+  }
+  // getAdjacencyMap (:37-39): vertex -> its neighbours (a loop holds its own vertex once)
+  std::map<int64_t, std::set<int64_t>> getAdjacencyMap() {
+    flush();
+    uint64_t edges = 0, vertices = 0;
+    gs_check(gs_spanner_count(handle(), &edges, &vertices));
+    std::vector<int64_t> v(vertices + 1), nb(2 * edges + 1);
+    std::vector<uint64_t> off(vertices + 2);
+    size_t nv = 0, ne = 0;
+    gs_check(gs_spanner_neighbors(h_, v.data(), off.data(), nb.data(), v.size(), nb.size(), &nv, &ne));
+    std::map<int64_t, std::set<int64_t>> out;
+    for (size_t i = 0; i < nv; ++i) out[v[i]].insert(nb.begin() + (long)off[i], nb.begin() + (long)off[i + 1]);
+    return out;
+  }
+  // getAdjacencyMap().size(), what CombineSpanners compares
+  size_t size() {
+    flush();
+    uint64_t edges = 0, vertices = 0;
+    gs_check(gs_spanner_count(handle(), &edges, &vertices));
+    return (size_t)vertices;
+  }
+  // the edges (lo <= hi) ascending
+  std::vector<std::pair<int64_t, int64_t>> edges() {
+    flush();
+    uint64_t edges = 0, vertices = 0;
+    gs_check(gs_spanner_count(handle(), &edges, &vertices));
+    std::vector<int64_t> lo(edges + 1), hi(edges + 1);
+    size_t n = 0;
+    gs_check(gs_spanner_export(h_, lo.data(), hi.data(), lo.size(), &n));
+    std::vector<std::pair<int64_t, int64_t>> out(n);
+    for (size_t i = 0; i < n; ++i) out[i] = {lo[i], hi[i]};
+    return out;
+  }
+  // the edges of `other`, ascending by (lo, hi), through updateLocal; `other` is unchanged
+  void combine(AdjacencyListGraph& other) {
+    flush();
+    other.flush();
+    if (other.h_) gs_check(gs_spanner_combine(handle(), other.h_));
+  }
+  // reset (:118-120)
+  void reset() {
+    src_.clear();
+    dst_.clear();
+    if (h_) gs_check(gs_spanner_reset(h_));
+  }
+  int k() const { return k_; }
+  gs_spanner handle() {
+    if (!h_) gs_check(gs_spanner_create(&h_, device_, k_, hint_));
+    return h_;
+  }
+  void flush() {
+    if (src_.empty()) return;
+    if (conditional_) gs_check(gs_spanner_fold(handle(), src_.data(), dst_.data(), src_.size(), nullptr));
+    else gs_check(gs_spanner_add(handle(), src_.data(), dst_.data(), src_.size()));
+    src_.clear();
+    dst_.clear();
+  }
+
+ private:
+  void push(int64_t s, int64_t t, bool conditional) {
+    if (conditional != conditional_) flush();
+    conditional_ = conditional;
+    src_.push_back(s);
+    dst_.push_back(t);
+  }
+  int k_, device_;
+  uint64_t hint_;
+  gs_spanner h_ = nullptr;
+  std::vector<int64_t> src_, dst_;
+  bool conditional_ = false;
+};
+using AdjacencyListGraphRef = std::shared_ptr<AdjacencyListGraph>;
+
+// Spanner<K, EV> (library/Spanner.java:40-118)
+template <typename EV = NullValue>
+class Spanner : public SummaryBulkAggregation<int64_t, EV, AdjacencyListGraphRef, AdjacencyListGraphRef> {
+  using Base = SummaryBulkAggregation<int64_t, EV, AdjacencyListGraphRef, AdjacencyListGraphRef>;
+
+ public:
+  // UpdateLocal.foldEdges (:71-77)
+  struct UpdateLocal : EdgesFold<int64_t, EV, AdjacencyListGraphRef> {
+    AdjacencyListGraphRef foldEdges(AdjacencyListGraphRef g, int64_t src, int64_t trg, EV) override {
+      g->updateLocal(src, trg);
+      return g;
+    }
+  };
+  // CombineSpanners.reduce (:92-116): the spanner with strictly more vertices takes the other's
+  // edges; on a tie g2 takes g1's. The edges arrive ascending by (lo, hi) (gs_spanner_combine).
+  struct CombineSpanners : ReduceFunction<AdjacencyListGraphRef> {
+    AdjacencyListGraphRef reduce(AdjacencyListGraphRef g1, AdjacencyListGraphRef g2) override {
+      if (g1->size() > g2->size()) {
+        g1->combine(*g2);
+        return g1;
+      }
+      g2->combine(*g1);
+      return g2;
+    }
+  };
+  // Spanner(long mergeWindowTime, int k) (:50-53); device is the GPU knob
+  Spanner(int64_t mergeWindowTime, int k, int device = 0)
+      : Base(std::make_shared<UpdateLocal>(), std::make_shared<CombineSpanners>(),
+             [k, device] { return std::make_shared<AdjacencyListGraph>(k, device); }, mergeWindowTime, false) {}
 };
 
 }  // namespace gelly

@@ -654,6 +654,79 @@ int gs_distinct_sync(gs_distinct d);
 int gs_distinct_get_stream(gs_distinct d, void** stream);
 int gs_distinct_wait_stream(gs_distinct d, void* stream);
 
+/* ---- k-spanner summary ------------------------------------------------------------
+ * The streaming k-spanner of library/Spanner.java over summaries/AdjacencyListGraph.java: the
+ * third SummaryBulkAggregation of the reference's library (example/SpannerExample drives it).
+ *
+ * A spanner handle is its own opaque type with its own create call. It holds an undirected
+ * simple graph G over signed 64-bit ids, which may also hold self-loops {u, u}; every id is
+ * legal, INT64_MIN and INT64_MAX included.
+ *   within(s, t, k)  AdjacencyListGraph.boundedBFS: false when s is no vertex of G; otherwise
+ *                    true iff t is reached from s by 1..k edges of G without revisiting s: for
+ *                    s != t iff dist_G(s, t) <= k, for s == t iff the loop {s, s} is in G.
+ *                    1 <= k <= 16; any other k returns GS_ERR_INVALID, in gs_spanner_create and
+ *                    in gs_spanner_within* (the reference treats k <= 0 like k = 1).
+ *   fold             Spanner.UpdateLocal over the n edges in arrival order: edge i is accepted
+ *                    (added to G) iff within(src[i], dst[i], k) is false on the graph the edges
+ *                    0 .. i-1 left, otherwise dropped. So a repeated edge is dropped, a self-loop
+ *                    is kept the first time only, direction does not matter, and the accepted set
+ *                    is a function of the stream order alone, however the stream is cut into
+ *                    folds. The fold runs in parallel on the device and is exact to that
+ *                    sequential order. accepted[i] = 1 / 0 per arrival.
+ *   combine          Spanner.CombineSpanners: the edges of `from` folded into `into` with into's
+ *                    k, in ascending signed (lo, hi) order, each undirected edge once; `from` is
+ *                    unchanged. The reference iterates its hash maps, which is this order for
+ *                    small non-negative ids; its order elsewhere is an accident of HashMap
+ *                    capacity and is not reproduced. Both handles on one device.
+ * Not built: deletions, serialization, multi-GPU groups.
+ *
+ * Synchronisation: a fold synchronises with the host several times (the pending count, one or
+ * two words per round, the accepted count); its reads of DEVICE src / dst are queued on the
+ * handle's stream (gs_spanner_wait_stream orders them behind a producer). Adjacency entries
+ * (two per edge, one per loop) are 32-bit indices: a fold that could take them past 2^32 - 2
+ * fails with GS_ERR_CAPACITY before any work. Every device allocation of a handle is counted by
+ * gs_hbm_bytes and released by gs_spanner_destroy.
+ *
+ * gs_spanner_create: k as above; edge_hint sizes the first allocation only.
+ * gs_spanner_reset: G empty, capacity and k kept.
+ * gs_spanner_fold / _fold_device: n edges from HOST arrays (copied before the call returns) /
+ *   DEVICE arrays, element i = src[i*stride], dst[i*stride]; accepted (may be NULL): n bytes,
+ *   HOST / DEVICE (the device form queues the copy on the handle's stream).
+ * gs_spanner_add: AdjacencyListGraph.addEdge for n HOST edges in order: every edge joins G
+ *   unless G holds it already (the fold with k = 1, whatever the handle's k).
+ * gs_spanner_within / _within_device: out[i] = within(src[i], dst[i], k) on G as it stands, HOST /
+ *   DEVICE arrays; the device form leaves out[] queued on the handle's stream.
+ * gs_spanner_combine: as above (synchronises).
+ * gs_spanner_count: the edges (a loop counts as one) and the vertices of G (synchronises).
+ * gs_spanner_export_device / gs_spanner_export: the edges (lo <= hi) into DEVICE / HOST arrays of
+ *   capacity cap, ascending by (lo, hi) in signed order. *n on the host (synchronises);
+ *   GS_ERR_TRUNCATED with *n set and nothing written when cap < *n.
+ * gs_spanner_neighbors: the adjacency as a CSR in HOST arrays, what getAdjacencyMap() holds and
+ *   SpannerExample.FlattenSet reads: v[nv] ascending, offset[nv + 1], neighbor[ne] ascending
+ *   inside each row (a loop appears once in its row). GS_ERR_TRUNCATED with *nv, *ne set and
+ *   nothing written when cap_v < *nv or cap_e < *ne.
+ * gs_spanner_sync / _get_stream / _wait_stream: as gs_sync / gs_get_stream / gs_wait_stream.
+ * Null handles and pointers return GS_ERR_INVALID before any device call. */
+typedef struct gs_spanner_s* gs_spanner;
+int gs_spanner_create(gs_spanner* out, int device, int k, uint64_t edge_hint);
+int gs_spanner_destroy(gs_spanner s); /* NULL is GS_OK */
+int gs_spanner_reset(gs_spanner s);
+int gs_spanner_fold(gs_spanner s, const int64_t* src, const int64_t* dst, size_t n, uint8_t* accepted);
+int gs_spanner_fold_device(gs_spanner s, const int64_t* src, const int64_t* dst, size_t n, uint8_t* accepted,
+                           size_t stride);
+int gs_spanner_add(gs_spanner s, const int64_t* src, const int64_t* dst, size_t n);
+int gs_spanner_within(gs_spanner s, const int64_t* src, const int64_t* dst, size_t n, int k, uint8_t* out);
+int gs_spanner_within_device(gs_spanner s, const int64_t* src, const int64_t* dst, size_t n, int k, uint8_t* out);
+int gs_spanner_combine(gs_spanner into, gs_spanner from);
+int gs_spanner_count(gs_spanner s, uint64_t* edges, uint64_t* vertices);
+int gs_spanner_export_device(gs_spanner s, int64_t* lo, int64_t* hi, size_t cap, size_t* n);
+int gs_spanner_export(gs_spanner s, int64_t* lo, int64_t* hi, size_t cap, size_t* n);
+int gs_spanner_neighbors(gs_spanner s, int64_t* v, uint64_t* offset, int64_t* neighbor, size_t cap_v, size_t cap_e,
+                         size_t* nv, size_t* ne);
+int gs_spanner_sync(gs_spanner s);
+int gs_spanner_get_stream(gs_spanner s, void** stream);
+int gs_spanner_wait_stream(gs_spanner s, void* stream);
+
 /* ---- introspection -----------------------------------------------------------
  * The HIP stream (hipStream_t) the handle enqueues on, and per-kernel timing:
  * when profiling is on, every launch is bracketed by HIP events on the stream it

@@ -52,7 +52,16 @@ enum gs_testing_knob {
    * the occurrences that issue an atomic minimum (gs_testing_distinct_phases; needed by
    * tools/distinct_bench.py); product: 0 */
   GS_TESTING_DISTINCT_PROFILE = 9,
-  GS_TESTING_KNOBS = 10
+  /* spanner fold: rounds before the undecided pending edges go to the serial tail (product: 16,
+   * and a round that decides less than one in eight ends the rounds too; a set value fixes the
+   * number of rounds alone: 0 sends every pending edge to the tail, a huge one leaves no tail) */
+  GS_TESTING_SPANNER_ROUND_CAP = 10,
+  /* spanner searches: vertices per side of a wave's on-chip sets, 1..256 (product: 256); a search
+   * that needs more takes the heavy path */
+  GS_TESTING_SPANNER_LDS_SET = 11,
+  /* spanner heavy path: arenas of the pool, 1..64 (product: 32); 1 serialises the heavy searches */
+  GS_TESTING_SPANNER_ARENAS = 12,
+  GS_TESTING_KNOBS = 13
 };
 
 /* Set knob `knob` to `value` (< 0: the product value). Returns GS_OK or GS_ERR_INVALID. */
@@ -99,6 +108,13 @@ int gs_testing_distinct_stats(void* d, uint64_t* out);
  * out[5] = occurrences that issued an atomic minimum, out[6] = its occurrences (2 n entries + n
  * edges). Seven words. */
 int gs_testing_distinct_phases(void* d, uint64_t* out);
+
+/* The last fold of a spanner handle (`s` is a gs_spanner; no device call; zero after a reset):
+ * out[0] = arrivals the filter pass dropped (within k in the graph before the fold), out[1] = the
+ * pending edges it left, out[2] = rounds run, out[3] = pending edges the serial tail decided,
+ * out[4] = searches that overflowed their on-chip sets and took the heavy path (filter pass and
+ * rounds), out[5] = the longest row (adjacency plus pending entries) a search expanded. Six words. */
+int gs_testing_spanner_stats(void* s, uint64_t* out);
 
 #ifdef __cplusplus
 }
