@@ -87,6 +87,10 @@ EXPORTED_SYMBOLS = (
     "gs_spanner_add", "gs_spanner_within", "gs_spanner_within_device", "gs_spanner_combine", "gs_spanner_count",
     "gs_spanner_export_device", "gs_spanner_export", "gs_spanner_neighbors", "gs_spanner_sync",
     "gs_spanner_get_stream", "gs_spanner_wait_stream", "gs_testing_spanner_stats",
+    "gs_matching_create", "gs_matching_destroy", "gs_matching_reset", "gs_matching_fold", "gs_matching_fold_device",
+    "gs_matching_events", "gs_matching_events_device", "gs_matching_count", "gs_matching_export",
+    "gs_matching_export_device", "gs_matching_mate_device", "gs_matching_sync", "gs_matching_get_stream",
+    "gs_matching_wait_stream", "gs_testing_matching_stats", "gs_testing_matching_tune",
 )
 
 # Pairs per workgroup of the component export's radix-sort kernels (csrc/gs_sort.hpp kSortTile):
@@ -145,6 +149,17 @@ SPANNER_MAX_K = 16
 SPANNER_LDS_SET = 256
 SPANNER_ARENAS = 32
 SPANNER_ROUND_CAP = 16
+
+# The weighted matching summary (csrc/gs_matching_seq.hpp, csrc/gs_matching.hpp): the rounds of a
+# fold before the one-workgroup tail takes what is left, the pending count below which it takes
+# them at once, the fixpoint passes of a round before it falls back to plain reservations, the
+# bits of a weight-safe value, and the arrivals per workgroup of the event compaction.
+MATCHING_ROUND_CAP = 32
+MATCHING_TAIL_THRESHOLD = 4096
+MATCHING_ITER_CAP = 6
+MATCHING_SAFE_BITS = 61
+MATCHING_TILE = 1024
+MATCHING_EVENTS = {"add": 0, "remove": 1}  # gs_matching_event
 
 FAIL_BIT = 1 << 62  # count words: a failed signed verdict (GS_FAIL_BIT)
 DIGEST_FAILED = (1 << 64) - 1  # gs_digest of a signed summary whose verdict failed (GS_DIGEST_FAILED)
@@ -342,6 +357,22 @@ def lib():
     L.gs_spanner_get_stream.argtypes = [_vp, ctypes.POINTER(_vp)]
     L.gs_spanner_wait_stream.argtypes = [_vp, _vp]
     L.gs_testing_spanner_stats.argtypes = [_vp, ctypes.POINTER(_u64)]
+    L.gs_matching_create.argtypes = [ctypes.POINTER(_vp), ctypes.c_int, _u64]
+    L.gs_matching_destroy.argtypes = [_vp]
+    L.gs_matching_reset.argtypes = [_vp]
+    L.gs_matching_fold.argtypes = [_vp, _vp, _vp, _vp, _sz, _vp]
+    L.gs_matching_fold_device.argtypes = [_vp, _vp, _vp, _vp, _sz, _vp, _sz]
+    L.gs_matching_events.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _sz, ctypes.POINTER(_sz)]
+    L.gs_matching_events_device.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _sz, ctypes.POINTER(_sz)]
+    L.gs_matching_count.argtypes = [_vp, ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(ctypes.c_int64)]
+    L.gs_matching_export.argtypes = [_vp, _vp, _vp, _vp, _vp, _sz, ctypes.POINTER(_sz)]
+    L.gs_matching_export_device.argtypes = [_vp, _vp, _vp, _vp, _vp, _sz, ctypes.POINTER(_sz)]
+    L.gs_matching_mate_device.argtypes = [_vp, _vp, _sz, _vp, _vp, _vp]
+    L.gs_matching_sync.argtypes = [_vp]
+    L.gs_matching_get_stream.argtypes = [_vp, ctypes.POINTER(_vp)]
+    L.gs_matching_wait_stream.argtypes = [_vp, _vp]
+    L.gs_testing_matching_stats.argtypes = [_vp, ctypes.POINTER(_u64)]
+    L.gs_testing_matching_tune.argtypes = [_vp, ctypes.c_int, ctypes.c_int64]
     L.gs_testing_set.argtypes = [ctypes.c_int, _i64]
     L.gs_testing_get.argtypes = [ctypes.c_int]
     L.gs_testing_get.restype = _i64
@@ -1628,6 +1659,160 @@ class Spanner:
         _check(lib().gs_testing_spanner_stats(self._h, out))
         return {"filter_drops": out[0], "pending": out[1], "rounds": out[2], "tail": out[3], "heavy": out[4],
                 "longest_row": out[5]}
+
+
+# ---------------------------------------------------------------- weighted matching
+class Matching:
+    """The streaming greedy weighted matching of example/CentralizedWeightedMatching.java (the
+    gs_matching_* section of include/gs_summary.h): an arriving edge (u, v, w) joins the matching
+    M iff w > 2 * (the values of M's edges at u and v), in Java long arithmetic, and then removes
+    them; exactly in arrival order however the stream is cut into folds. Owns a gs_matching handle."""
+
+    def __init__(self, device=0, vertex_hint=1 << 16):
+        self.device = device
+        h = _vp()
+        _check(lib().gs_matching_create(ctypes.byref(h), device, int(vertex_hint)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().gs_matching_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def stream(self):
+        s = _vp()
+        _check(lib().gs_matching_get_stream(self._h, ctypes.byref(s)))
+        return s.value
+
+    def reset(self):
+        """M empty, no vertex seen, weight-safe again; capacity and tuning are kept."""
+        _check(lib().gs_matching_reset(self._h))
+
+    def sync(self):
+        _check(lib().gs_matching_sync(self._h))
+
+    def wait_stream(self, stream="torch"):
+        if isinstance(stream, str):
+            import torch
+            stream = torch.cuda.current_stream(self.device)
+        raw = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
+        _check(lib().gs_matching_wait_stream(self._h, raw))
+
+    def fold(self, src, dst, val):
+        """Fold host arrivals (int64 arrays) in order; returns the accepted mask (bool)."""
+        s = np.ascontiguousarray(np.asarray(src, dtype=np.int64))
+        d = np.ascontiguousarray(np.asarray(dst, dtype=np.int64))
+        w = np.ascontiguousarray(np.asarray(val, dtype=np.int64))
+        assert s.shape == d.shape == w.shape
+        acc = np.zeros(len(s), np.uint8)
+        _check(lib().gs_matching_fold(self._h, s.ctypes.data, d.ctypes.data, w.ctypes.data, len(s), acc.ctypes.data))
+        return acc.astype(bool)
+
+    def fold_device(self, src, dst, val, accepted=None, n=None, stride=1, after=None):
+        """Fold device-resident arrivals (torch tensors on this device or raw pointers), element i
+        at index i * stride; `accepted` (optional): a DEVICE uint8 tensor of n bytes, written on
+        the handle's stream; `after`: a stream the arrays were written on. The fold synchronises
+        with the host."""
+        if n is None:
+            n = (src.numel() + stride - 1) // stride
+        if after is not None:
+            self.wait_stream(after)
+        _check(lib().gs_matching_fold_device(self._h, _ptr(src), _ptr(dst), _ptr(val), int(n), _ptr(accepted),
+                                             int(stride)))
+
+    def events(self):
+        """The last fold's MatchingEvent rows as numpy arrays (arrival uint32, type uint8 --
+        MATCHING_EVENTS --, src, dst, val int64), ascending by arrival; an arrival's REMOVEs (the
+        edge at its source endpoint first) precede its ADD."""
+        got = _sz()
+        rc = lib().gs_matching_events(self._h, None, None, None, None, None, 0, ctypes.byref(got))
+        if rc != GS_ERR_TRUNCATED:  # (the row count of a fold with events)
+            _check(rc)
+        n = max(got.value, 1)
+        a = np.empty(n, np.uint32)
+        t = np.empty(n, np.uint8)
+        s, d, w = (np.empty(n, np.int64) for _ in range(3))
+        _check(lib().gs_matching_events(self._h, a.ctypes.data, t.ctypes.data, s.ctypes.data, d.ctypes.data,
+                                        w.ctypes.data, n, ctypes.byref(got)))
+        k = got.value
+        return a[:k].copy(), t[:k].copy(), s[:k].copy(), d[:k].copy(), w[:k].copy()
+
+    def events_device(self, arrival, type, src, dst, val):
+        """The same rows into DEVICE arrays (capacity src.numel(); any may be None); returns the
+        row count."""
+        got = _sz()
+        first = next(x for x in (src, dst, val, arrival, type) if x is not None)
+        cap = first.numel() if hasattr(first, "numel") else len(first)
+        _check(lib().gs_matching_events_device(self._h, _ptr(arrival), _ptr(type), _ptr(src), _ptr(dst), _ptr(val),
+                                               cap, ctypes.byref(got)))
+        return got.value
+
+    def count(self):
+        """(edges of M, distinct vertices seen, wrapping sum of M's values). No device call."""
+        e, v, w = _u64(), _u64(), ctypes.c_int64()
+        _check(lib().gs_matching_count(self._h, ctypes.byref(e), ctypes.byref(v), ctypes.byref(w)))
+        return e.value, v.value, w.value
+
+    def edges(self):
+        """(src, dst, val, first) numpy arrays: M ascending by the global arrival number `first`
+        at which each edge was accepted."""
+        got = _sz()
+        n = max(self.count()[0], 1)
+        s, d, w = (np.empty(n, np.int64) for _ in range(3))
+        f = np.empty(n, np.uint64)
+        _check(lib().gs_matching_export(self._h, s.ctypes.data, d.ctypes.data, w.ctypes.data, f.ctypes.data, n,
+                                        ctypes.byref(got)))
+        k = got.value
+        return s[:k].copy(), d[:k].copy(), w[:k].copy(), f[:k].copy()
+
+    def edges_device(self, src, dst, val, first=None):
+        """The same rows into DEVICE arrays (capacity src.numel()); returns the edge count."""
+        got = _sz()
+        cap = src.numel() if hasattr(src, "numel") else len(src)
+        _check(lib().gs_matching_export_device(self._h, _ptr(src), _ptr(dst), _ptr(val), _ptr(first), cap,
+                                               ctypes.byref(got)))
+        return got.value
+
+    def mate_device(self, v, mate, val, found, n=None):
+        """Per DEVICE id v[i]: found[i] (uint8) = it is matched, mate[i] / val[i] = its partner in M
+        and the edge's value (0 otherwise); queued on self.stream."""
+        n = v.numel() if n is None else n
+        _check(lib().gs_matching_mate_device(self._h, _ptr(v), int(n), _ptr(mate), _ptr(val), _ptr(found)))
+
+    def stats(self):
+        """gs_testing_matching_stats: the last fold."""
+        out = (_u64 * 6)()
+        _check(lib().gs_testing_matching_stats(self._h, out))
+        return {"rounds": out[0], "iterations": out[1], "tail": out[2], "accepted": out[3], "fallbacks": out[4],
+                "weight_safe": bool(out[5])}
+
+    def tune(self, round_cap=None, iter_cap=None, sharpen=None):
+        """gs_testing_matching_tune, per handle: round_cap (0: everything to the tail, huge: no
+        tail), iter_cap (fixpoint passes per round), sharpen (False: off). A negative value (or
+        sharpen=True) restores the product value; None leaves a control as it is."""
+        if round_cap is not None:
+            _check(lib().gs_testing_matching_tune(self._h, 0, int(round_cap)))
+        if iter_cap is not None:
+            _check(lib().gs_testing_matching_tune(self._h, 1, int(iter_cap)))
+        if sharpen is not None:
+            _check(lib().gs_testing_matching_tune(self._h, 2, -1 if sharpen else 1))
 
 
 # ---------------------------------------------------------------- native multi-GPU group

@@ -55,16 +55,8 @@ struct gs_distinct_s : StreamOwner {
   uint64_t phase_us[5] = {0, 0, 0, 0, 0};  // of the last profiled fold (gs_testing_distinct_phases)
   uint64_t last_atomics = 0;
 
-  gs::DistVTable vtable() const { return vtable_of(vtab, vcap); }
+  gs::DistVTable vtable() const { return gs::dist_vtable_of(vtab, vcap); }
   gs::DistETable etable() const { return etable_of(etab, ecap); }
-  static gs::DistVTable vtable_of(gs::DistVSlot* tab, uint64_t cap) {
-    gs::DistVTable t;
-    t.tab = tab;
-    t.cap = (uint32_t)cap;
-    t.mask = (uint32_t)(cap - 1);
-    t.shift = 64 - gs::dist_log2(cap);
-    return t;
-  }
   static gs::DistETable etable_of(gs::DistESlot* tab, uint64_t cap) {
     gs::DistETable t;
     t.tab = tab;
@@ -89,7 +81,7 @@ int grow_vertices(gs_distinct_s* d, uint64_t cap) {
   DevBuf<int64_t> vid;
   GS_HIP(tab.alloc(cap + 1));
   GS_HIP(vid.alloc(gs::dist_vid_cap(cap)));
-  const gs::DistVTable to = gs_distinct_s::vtable_of(tab, cap);
+  const gs::DistVTable to = gs::dist_vtable_of(tab, cap);
   gs::launch_dist_init(to, d->stream);
   GS_HIP(hipGetLastError());
   if (d->vtab) {

@@ -42,6 +42,15 @@ struct DistVTable {
   uint32_t mask;
   int shift;       // 64 - log2(cap)
 };
+// the view of a vertex table of `cap` hashed slots (a power of two) at tab[cap + 1]
+inline DistVTable dist_vtable_of(DistVSlot* tab, uint64_t cap) {
+  DistVTable t;
+  t.tab = tab;
+  t.cap = (uint32_t)cap;
+  t.mask = (uint32_t)(cap - 1);
+  t.shift = 64 - dist_log2(cap);
+  return t;
+}
 struct DistETable {
   DistESlot* tab;  // [cap]
   uint32_t cap;

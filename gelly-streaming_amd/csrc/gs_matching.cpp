@@ -1,0 +1,528 @@
+// gs_matching.cpp -- the weighted matching summary behind include/gs_summary.h's gs_matching_*
+// section: example/CentralizedWeightedMatching.java with util/MatchingEvent.java. State layout
+// and kernels are described in gs_matching.hpp / gs_matching_k.hip, the exactness argument of
+// the fold by rounds in DESIGN.md section 6g and, executable, in gs_matching_seq.hpp
+// (MatchingRounds).
+//
+// A fold of n arrivals: growth is decided first from host-known totals (worst case + 2 n
+// vertices), so nothing grows inside the fold; the distinct streams' vertex phase
+// (launch_dist_vertices) gives every new id its rank; the gather reads the ranks; rounds run
+// while the pending arrivals are many (the host reads two words per round: the pending count and
+// the error word); the tail finishes; the event rows are counted, the counts read (the fold's
+// last wait), the rows written.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <string>
+
+#include "gs_internal.hpp"
+#include "gs_matching.hpp"
+
+using namespace gsi;
+
+struct gs_matching_s : StreamOwner {
+  DevBuf<unsigned long long> ctl;   // gs::MtCtl words
+  DevBuf<unsigned long long> dctl;  // gs::DistCtl words of the vertex phase
+  // the vertex table, the vertices in rank order and the state record of every rank
+  DevBuf<gs::DistVSlot> vtab;  // [vcap + 1]
+  DevBuf<int64_t> vid;         // [dist_vid_cap(vcap)]
+  DevBuf<gs::MtVertex> st;     // [dist_vid_cap(vcap)]
+  uint64_t vcap = 0;
+  // fold scratch for n_cap arrivals
+  uint64_t n_cap = 0;
+  DevBuf<uint32_t> vslot;  // [2 n] slot of every entry
+  DevBuf<uint8_t> flags;   // whole tiles of 2 n positions (the vertex phase)
+  DevBuf<uint32_t> tbase;  // [tiles + 1]: the vertex phase's tile counts, then the event rows'
+  DevBuf<uint32_t> entry;  // [2 n] entries of the new vertices (the vertex phase writes them)
+  DevBuf<uint32_t> ru, rv;
+  DevBuf<int64_t> w;
+  DevBuf<uint8_t> mark, acc;
+  DevBuf<gs::MtRec> rec;
+  DevBuf<uint32_t> list[2];
+  // device staging of a host fold
+  uint64_t h_cap = 0;
+  DevBuf<int64_t> stage;  // [3][h_cap]
+  // the last fold's events
+  uint64_t ev_cap = 0, ev_rows = 0;
+  bool ev_kept = true;  // false after a fold the library cut into pieces
+  DevBuf<uint32_t> ev_arrival;
+  DevBuf<uint8_t> ev_type;
+  DevBuf<int64_t> ev_src, ev_dst, ev_val;
+  // export: compacted (stamp, rank) rows, the sort's scratch, staging of the host-array form
+  SortScratch sort;
+  uint64_t x_cap = 0;
+  DevBuf<int64_t> x_stamp;
+  DevBuf<uint32_t> x_rank;
+  uint64_t o_cap = 0;
+  DevBuf<int64_t> o_a, o_b, o_c;
+  DevBuf<unsigned long long> o_d;
+  // mate probe
+  uint64_t q_cap = 0;
+  DevBuf<int64_t> q_rank;
+  // host-known totals
+  uint64_t nv = 0, folded = 0, edges = 0;
+  int64_t weight = 0;
+  bool safe = true;
+  // gs_testing_matching_tune (< 0: product) and gs_testing_matching_stats
+  int64_t tune[3] = {-1, -1, -1};
+  uint64_t stats[5] = {0, 0, 0, 0, 0};
+
+  gs::DistVTable vtable() const { return gs::dist_vtable_of(vtab, vcap); }
+};
+
+namespace {
+
+int check_mt(gs_matching m) {
+  if (!m) return fail(GS_ERR_INVALID, "null matching handle");
+  return GS_OK;
+}
+
+int truncated(size_t cap, uint64_t need) {
+  return fail(GS_ERR_TRUNCATED, "output capacity " + std::to_string(cap) + " < " + std::to_string(need));
+}
+
+// A vertex table of `cap` slots, its vertex list and its state records in place of the current
+// ones, whose vertices move over (a rank is the same before and after); the first of a handle.
+int grow_vertices(gs_matching_s* m, uint64_t cap) {
+  DevBuf<gs::DistVSlot> tab;
+  DevBuf<int64_t> vid;
+  DevBuf<gs::MtVertex> st;
+  const uint64_t ranks = gs::dist_vid_cap(cap);
+  GS_HIP(tab.alloc(cap + 1));
+  GS_HIP(vid.alloc(ranks));
+  GS_HIP(st.alloc(ranks));
+  const gs::DistVTable to = gs::dist_vtable_of(tab, cap);
+  gs::launch_dist_init(to, m->stream);
+  GS_HIP(hipGetLastError());
+  gs::launch_mt_init(st, m->vtab ? m->nv : 0, ranks, m->stream);
+  GS_HIP(hipGetLastError());
+  if (m->vtab) {
+    gs::launch_dist_rebuild(m->vtable(), to, m->dctl, m->stream);
+    GS_HIP(hipGetLastError());
+    if (m->nv) {
+      GS_HIP(hipMemcpyAsync(vid, m->vid, m->nv * 8, hipMemcpyDeviceToDevice, m->stream));
+      GS_HIP(hipMemcpyAsync(st, m->st, m->nv * sizeof(gs::MtVertex), hipMemcpyDeviceToDevice, m->stream));
+    }
+    GS_HIP(hipStreamSynchronize(m->stream));  // before the old arrays are freed
+  }
+  m->vtab.swap(tab);
+  m->vid.swap(vid);
+  m->st.swap(st);
+  m->vcap = cap;
+  return GS_OK;
+}
+
+int ensure_scratch(gs_matching_s* m, uint64_t n) {
+  if (m->n_cap >= n) return GS_OK;
+  GS_HIP(hipStreamSynchronize(m->stream));
+  m->n_cap = 0;
+  const uint64_t c = std::min<uint64_t>(gs::kMtMaxFold, n + n / 4);
+  const uint64_t tiles = gs::dist_tiles(2 * c, gs::DISTINCT_TILE);
+  static_assert(2 * gs::MATCHING_TILE == gs::DISTINCT_TILE, "tbase serves both compactions: n / 1024 tiles");
+  GS_HIP(m->vslot.alloc(2 * c));
+  GS_HIP(m->flags.alloc(tiles * gs::DISTINCT_TILE));
+  GS_HIP(m->tbase.alloc(tiles + 1));
+  GS_HIP(m->entry.alloc(2 * c));
+  GS_HIP(m->ru.alloc(c));
+  GS_HIP(m->rv.alloc(c));
+  GS_HIP(m->w.alloc(c));
+  GS_HIP(m->mark.alloc(c));
+  GS_HIP(m->acc.alloc(c));
+  GS_HIP(m->rec.alloc(c));
+  GS_HIP(m->list[0].alloc(c));
+  GS_HIP(m->list[1].alloc(c));
+  m->n_cap = c;
+  return GS_OK;
+}
+
+int ensure_events(gs_matching_s* m, uint64_t rows) {
+  if (m->ev_cap >= rows) return GS_OK;
+  GS_HIP(hipStreamSynchronize(m->stream));
+  m->ev_cap = 0;
+  const uint64_t c = rows + rows / 4;
+  GS_HIP(m->ev_arrival.alloc(c));
+  GS_HIP(m->ev_type.alloc(c));
+  GS_HIP(m->ev_src.alloc(c));
+  GS_HIP(m->ev_dst.alloc(c));
+  GS_HIP(m->ev_val.alloc(c));
+  m->ev_cap = c;
+  return GS_OK;
+}
+
+int ensure_staging(gs_matching_s* m, uint64_t rows) {
+  if (m->o_cap >= rows) return GS_OK;
+  GS_HIP(hipStreamSynchronize(m->stream));
+  m->o_cap = 0;
+  const uint64_t c = rows + rows / 4;
+  GS_HIP(m->o_a.alloc(c));
+  GS_HIP(m->o_b.alloc(c));
+  GS_HIP(m->o_c.alloc(c));
+  GS_HIP(m->o_d.alloc(c));
+  m->o_cap = c;
+  return GS_OK;
+}
+
+int fold_guard(gs_matching_s* m, const void* src, const void* dst, const void* val, size_t n) {
+  if (n && (!src || !dst || !val)) return fail(GS_ERR_INVALID, "null edge arrays");
+  const uint64_t piece = std::min<uint64_t>(n, gs::kMtMaxFold);
+  const uint64_t need_v = m->nv + gs::dist_worst_vertices(n);
+  if (need_v > gs::kDistMaxVertices ||
+      (gs::dist_must_grow(m->nv, gs::dist_worst_vertices(piece), m->vcap) &&
+       gs::dist_slots_for(m->nv + gs::dist_worst_vertices(piece)) > gs::kDistMaxSlots))
+    return fail(GS_ERR_CAPACITY, "matching fold: the fold may pass 2^31 vertex table slots");
+  return GS_OK;
+}
+
+// 0 < n <= kMtMaxFold device arrivals on m->stream; on return m->acc[i] is the accepted byte of
+// arrival i and the event rows are queued
+int fold_piece(gs_matching_s* m, const int64_t* src, const int64_t* dst, const int64_t* val, uint64_t n,
+               uint64_t stride) {
+  hipStream_t st = m->stream;
+  if (gs::dist_must_grow(m->nv, gs::dist_worst_vertices(n), m->vcap))
+    if (int rc = grow_vertices(m, gs::dist_slots_for(m->nv + gs::dist_worst_vertices(n)))) return rc;
+  if (int rc = ensure_scratch(m, n)) return rc;
+  const gs::DistVTable vt = m->vtable();
+  const uint64_t ranks = gs::dist_vid_cap(m->vcap);
+  // ranks
+  GS_HIP(hipMemsetAsync(m->dctl, 0, gs::DIST_CTL_WORDS * 8, st));
+  gs::launch_dist_vertices(src, dst, n, stride, vt, m->vslot, m->flags, m->tbase, m->nv, m->vid, ranks, m->entry,
+                           m->dctl, st);
+  GS_HIP(hipGetLastError());
+  static_assert(gs::MT_UNSAFE == 2 && gs::kMtFoldWords == 10, "the fold's words lie around MT_UNSAFE");
+  GS_HIP(hipMemsetAsync(m->ctl, 0, gs::MT_UNSAFE * 8, st));
+  GS_HIP(hipMemsetAsync(m->ctl + gs::MT_UNSAFE + 1, 0, (gs::kMtFoldWords - gs::MT_UNSAFE - 1) * 8, st));
+  gs::launch_mt_gather(m->vslot, vt, ranks, val, stride, n, m->ru, m->rv, m->w, m->list[0], m->acc, m->ctl, st);
+  GS_HIP(hipGetLastError());
+  gs::MtFold F;
+  F.st = m->st;
+  F.ru = m->ru;
+  F.rv = m->rv;
+  F.w = m->w;
+  F.mark = m->mark;
+  F.accepted = m->acc;
+  F.rec = m->rec;
+  F.base = m->folded;
+  F.n = (uint32_t)n;
+  F.sharpen = 0;  // (the kernels set it from `sharpen` and ctl[MT_UNSAFE])
+  const int sharpen = m->tune[2] > 0 ? 0 : 1;
+  const uint32_t iter_cap = (uint32_t)std::min<int64_t>(
+      gs::kMatchingMaxIterCap, std::max<int64_t>(1, m->tune[1] < 0 ? (int64_t)gs::kMatchingIterCap : m->tune[1]));
+  // rounds: a set cap fixes their number alone; the product also hands a short list to the tail
+  const bool fixed = m->tune[0] >= 0;
+  const uint64_t round_cap = fixed ? (uint64_t)m->tune[0] : gs::kMatchingRoundCap;
+  uint64_t np = n, rounds = 0;
+  int side = 0;
+  while (np && rounds < round_cap && (fixed || np >= gs::kMatchingTailThreshold)) {
+    gs::launch_mt_round(F, m->list[side], np, m->list[side ^ 1], iter_cap, sharpen, m->ctl, st);
+    GS_HIP(hipGetLastError());
+    unsigned long long w2[2] = {0, 0};
+    GS_HIP(hipMemcpyAsync(w2, m->ctl + gs::MT_NEXT, sizeof(w2), hipMemcpyDeviceToHost, st));
+    GS_HIP(hipStreamSynchronize(st));
+    if (w2[1]) return fail(GS_ERR_HIP, "matching fold: a rank or list index out of range (the handle's state is undefined)");
+    if (w2[0] >= np) return fail(GS_ERR_HIP, "matching round: no arrival decided");
+    np = w2[0];
+    side ^= 1;
+    ++rounds;
+  }
+  const uint64_t tail = np;
+  if (np) {
+    gs::launch_mt_tail(F, m->list[side], m->list[side ^ 1], np, iter_cap, sharpen, m->ctl, st);
+    GS_HIP(hipGetLastError());
+  }
+  // events: rows per tile, their scan, the counts (the fold's last wait), the rows
+  const uint64_t nt = gs::mt_tiles(n);
+  gs::launch_mt_event_count(m->acc, m->rec, m->w, n, m->tbase, m->ctl, st);
+  GS_HIP(hipGetLastError());
+  gs::launch_tile_scan(m->tbase, nt, m->ctl + gs::MT_ROWS, st);
+  GS_HIP(hipGetLastError());
+  unsigned long long c[gs::kMtFoldWords], d[gs::DIST_CTL_WORDS];
+  GS_HIP(hipMemcpyAsync(c, m->ctl, sizeof(c), hipMemcpyDeviceToHost, st));
+  GS_HIP(hipMemcpyAsync(d, m->dctl, sizeof(d), hipMemcpyDeviceToHost, st));
+  GS_HIP(hipStreamSynchronize(st));
+  if (d[gs::DIST_OVERFLOW]) return fail(GS_ERR_HIP, "matching fold: the vertex table overflowed (the handle's state is undefined)");
+  if (c[gs::MT_ERR]) return fail(GS_ERR_HIP, "matching fold: a rank or list index out of range (the handle's state is undefined)");
+  if (d[gs::DIST_NEW_V] > 2 * n || c[gs::MT_ACC] > n || c[gs::MT_ROWS] > 3 * n)
+    return fail(GS_ERR_HIP, "matching fold: counts out of range");
+  m->nv += d[gs::DIST_NEW_V];
+  m->folded += n;
+  m->edges += c[gs::MT_EDGES];  // (wrapping: the change may be negative)
+  m->weight = gs::mt_wrap_add(m->weight, (int64_t)c[gs::MT_WEIGHT]);
+  m->safe = c[gs::MT_UNSAFE] == 0;
+  m->stats[0] = rounds + c[gs::MT_TAIL_ROUNDS];
+  m->stats[1] = c[gs::MT_ITERS];
+  m->stats[2] = tail;
+  m->stats[3] = c[gs::MT_ACC];
+  m->stats[4] = c[gs::MT_FALLBACKS];
+  m->ev_rows = c[gs::MT_ROWS];
+  if (m->ev_rows) {
+    if (int rc = ensure_events(m, m->ev_rows)) return rc;
+    gs::launch_mt_event_write(m->acc, m->rec, m->ru, m->rv, m->w, n, m->tbase, m->vid, m->nv, m->ev_arrival,
+                              m->ev_type, m->ev_src, m->ev_dst, m->ev_val, m->ev_cap, st);
+    GS_HIP(hipGetLastError());
+  }
+  return GS_OK;
+}
+
+void forget_last(gs_matching_s* m) {
+  std::fill(m->stats, m->stats + 5, 0);
+  m->ev_rows = 0;
+  m->ev_kept = true;
+}
+
+// the whole fold, cut into pieces of at most kMtMaxFold arrivals; host: the arrays are HOST arrays
+int fold_all(gs_matching_s* m, const int64_t* src, const int64_t* dst, const int64_t* val, size_t n,
+             uint8_t* accepted, uint64_t stride, bool host) {
+  forget_last(m);
+  if (n == 0) return GS_OK;
+  DeviceGuard g(m->device);
+  uint64_t sum[5] = {0, 0, 0, 0, 0};
+  for (uint64_t at = 0; at < n; at += gs::kMtMaxFold) {
+    const uint64_t len = std::min<uint64_t>(gs::kMtMaxFold, n - at);
+    const int64_t *ps = src + at * stride, *pd = dst + at * stride, *pv = val + at * stride;
+    if (host) {
+      if (m->h_cap < len) {
+        GS_HIP(hipStreamSynchronize(m->stream));
+        m->h_cap = 0;
+        const uint64_t c = std::min<uint64_t>(gs::kMtMaxFold, len + len / 4);
+        GS_HIP(m->stage.alloc(3 * c));
+        m->h_cap = c;
+      }
+      int64_t* s0 = m->stage;
+      GS_HIP(hipMemcpyAsync(s0, ps, len * 8, hipMemcpyHostToDevice, m->stream));
+      GS_HIP(hipMemcpyAsync(s0 + m->h_cap, pd, len * 8, hipMemcpyHostToDevice, m->stream));
+      GS_HIP(hipMemcpyAsync(s0 + 2 * m->h_cap, pv, len * 8, hipMemcpyHostToDevice, m->stream));
+      ps = s0;
+      pd = s0 + m->h_cap;
+      pv = s0 + 2 * m->h_cap;
+    }
+    if (int rc = fold_piece(m, ps, pd, pv, len, host ? 1 : stride)) return rc;
+    if (accepted)
+      GS_HIP(hipMemcpyAsync(accepted + at, m->acc, len, host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
+                            m->stream));
+    for (int i = 0; i < 5; ++i) sum[i] += m->stats[i];
+  }
+  if (n > gs::kMtMaxFold) {
+    std::copy(sum, sum + 5, m->stats);
+    m->ev_rows = 0;
+    m->ev_kept = false;
+  }
+  if (host) GS_HIP(hipStreamSynchronize(m->stream));
+  return GS_OK;
+}
+
+int events_impl(gs_matching_s* m, uint32_t* arrival, uint8_t* type, int64_t* src, int64_t* dst, int64_t* val,
+                size_t cap, size_t* n, bool to_host) {
+  if (!m->ev_kept) return fail(GS_ERR_INVALID, "matching events: the last fold was cut into pieces, its events were not kept");
+  const uint64_t rows = m->ev_rows;
+  *n = rows;
+  if (cap < rows) return truncated(cap, rows);
+  if (rows == 0) return GS_OK;
+  const hipMemcpyKind kind = to_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+  if (arrival) GS_HIP(hipMemcpyAsync(arrival, m->ev_arrival, rows * 4, kind, m->stream));
+  if (type) GS_HIP(hipMemcpyAsync(type, m->ev_type, rows, kind, m->stream));
+  if (src) GS_HIP(hipMemcpyAsync(src, m->ev_src, rows * 8, kind, m->stream));
+  if (dst) GS_HIP(hipMemcpyAsync(dst, m->ev_dst, rows * 8, kind, m->stream));
+  if (val) GS_HIP(hipMemcpyAsync(val, m->ev_val, rows * 8, kind, m->stream));
+  if (to_host) GS_HIP(hipStreamSynchronize(m->stream));
+  return GS_OK;
+}
+
+// scan the state, compact the source vertices of M's edges, sort by stamp, decode
+int export_impl(gs_matching_s* m, int64_t* src, int64_t* dst, int64_t* val, uint64_t* first, size_t cap, size_t* n,
+                bool to_host) {
+  const uint64_t ne = m->edges;
+  *n = ne;
+  if (cap < ne) return truncated(cap, ne);
+  if (ne == 0) return GS_OK;
+  if (m->x_cap < ne) {
+    GS_HIP(hipStreamSynchronize(m->stream));
+    m->x_cap = 0;
+    const uint64_t c = ne + ne / 4;
+    GS_HIP(m->x_stamp.alloc(c));
+    GS_HIP(m->x_rank.alloc(c));
+    m->x_cap = c;
+  }
+  if (int rc = sort_scratch_ensure(m->sort, ne, m->stream)) return rc;
+  int64_t *ds = src, *dd = dst, *dv = val;
+  unsigned long long* df = reinterpret_cast<unsigned long long*>(first);
+  if (to_host) {
+    if (int rc = ensure_staging(m, ne)) return rc;
+    ds = src ? m->o_a.get() : nullptr;
+    dd = dst ? m->o_b.get() : nullptr;
+    dv = val ? m->o_c.get() : nullptr;
+    df = first ? m->o_d.get() : nullptr;
+  }
+  GS_HIP(hipMemsetAsync(m->ctl + gs::MT_EXPORT, 0, 8, m->stream));
+  gs::launch_mt_export(m->st, m->nv, m->x_stamp, m->x_rank, ne, m->ctl, m->stream);
+  GS_HIP(hipGetLastError());
+  uint32_t* const sctl = m->sort.ctl;
+  GS_HIP(hipMemsetAsync(sctl, 0, gs::kSortCtlWords * 4, m->stream));
+  gs::launch_sort_digits_one(m->x_stamp, ne, sctl, m->stream);
+  GS_HIP(hipGetLastError());
+  // every stamp is below folded: the digits above its bits are equal in all keys
+  bool skip[gs::kSortPasses];
+  for (int p = 0; p < (int)gs::kSortPasses; ++p) skip[p] = p > 0 && (m->folded >> (8 * p)) == 0;
+  gs::SortSrc cur;  // (pay null: payload i of row i is i)
+  int side = 0;
+  if (int rc = sort_run(m->sort, m->x_stamp, ne, sctl, skip, &cur, &side, m->stream)) return rc;
+  if (!cur.key || !cur.pay) return fail(GS_ERR_HIP, "matching export: the sort ran no pass");
+  gs::launch_mt_decode(cur.key, cur.pay, m->x_rank, ne, m->st, m->vid, m->nv, ds, dd, dv, df, m->stream);
+  GS_HIP(hipGetLastError());
+  if (to_host) {
+    if (src) GS_HIP(hipMemcpyAsync(src, ds, ne * 8, hipMemcpyDeviceToHost, m->stream));
+    if (dst) GS_HIP(hipMemcpyAsync(dst, dd, ne * 8, hipMemcpyDeviceToHost, m->stream));
+    if (val) GS_HIP(hipMemcpyAsync(val, dv, ne * 8, hipMemcpyDeviceToHost, m->stream));
+    if (first) GS_HIP(hipMemcpyAsync(first, df, ne * 8, hipMemcpyDeviceToHost, m->stream));
+    GS_HIP(hipStreamSynchronize(m->stream));
+  }
+  return GS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gs_matching_destroy(gs_matching m) { return owner_destroy(m); }
+
+int gs_matching_create(gs_matching* out, int device, uint64_t vertex_hint) {
+  if (!out) return fail(GS_ERR_INVALID, "out is null");
+  *out = nullptr;
+  if (vertex_hint > gs::kDistMaxVertices || gs::dist_slots_for(vertex_hint) > gs::kDistMaxSlots)
+    return fail(GS_ERR_CAPACITY, "matching create: the hint passes 2^31 table slots");
+  if (int rc = check_device_index(device)) return rc;
+  return owner_create(out, device, [&](gs_matching_s* m) -> int {
+    GS_HIP(m->ctl.alloc(gs::MT_CTL_WORDS));
+    GS_HIP(hipMemsetAsync(m->ctl, 0, gs::MT_CTL_WORDS * 8, m->stream));
+    GS_HIP(m->dctl.alloc(gs::DIST_CTL_WORDS));
+    GS_HIP(hipMemsetAsync(m->dctl, 0, gs::DIST_CTL_WORDS * 8, m->stream));
+    return grow_vertices(m, gs::dist_slots_for(vertex_hint));
+  });
+}
+
+int gs_matching_reset(gs_matching m) {
+  if (int rc = check_mt(m)) return rc;
+  DeviceGuard g(m->device);
+  gs::launch_dist_init(m->vtable(), m->stream);
+  GS_HIP(hipGetLastError());
+  gs::launch_mt_init(m->st, 0, gs::dist_vid_cap(m->vcap), m->stream);
+  GS_HIP(hipGetLastError());
+  GS_HIP(hipMemsetAsync(m->ctl, 0, gs::MT_CTL_WORDS * 8, m->stream));
+  m->nv = m->folded = m->edges = 0;
+  m->weight = 0;
+  m->safe = true;
+  forget_last(m);
+  return GS_OK;
+}
+
+int gs_matching_fold_device(gs_matching m, const int64_t* src, const int64_t* dst, const int64_t* val, size_t n,
+                            uint8_t* accepted, size_t stride) {
+  if (int rc = check_mt(m)) return rc;
+  if (stride == 0 || stride > 0xFFFFFFFFull) return fail(GS_ERR_INVALID, "stride must be >= 1");
+  if (int rc = fold_guard(m, src, dst, val, n)) return rc;
+  return fold_all(m, src, dst, val, n, accepted, stride, false);
+}
+
+int gs_matching_fold(gs_matching m, const int64_t* src, const int64_t* dst, const int64_t* val, size_t n,
+                     uint8_t* accepted) {
+  if (int rc = check_mt(m)) return rc;
+  if (int rc = fold_guard(m, src, dst, val, n)) return rc;
+  return fold_all(m, src, dst, val, n, accepted, 1, true);
+}
+
+int gs_matching_events_device(gs_matching m, uint32_t* arrival, uint8_t* type, int64_t* src, int64_t* dst,
+                              int64_t* val, size_t cap, size_t* n) {
+  if (int rc = check_mt(m)) return rc;
+  if (!n) return fail(GS_ERR_INVALID, "n is null");
+  DeviceGuard g(m->device);
+  return events_impl(m, arrival, type, src, dst, val, cap, n, false);
+}
+
+int gs_matching_events(gs_matching m, uint32_t* arrival, uint8_t* type, int64_t* src, int64_t* dst, int64_t* val,
+                       size_t cap, size_t* n) {
+  if (int rc = check_mt(m)) return rc;
+  if (!n) return fail(GS_ERR_INVALID, "n is null");
+  DeviceGuard g(m->device);
+  return events_impl(m, arrival, type, src, dst, val, cap, n, true);
+}
+
+int gs_matching_count(gs_matching m, uint64_t* edges, uint64_t* vertices_seen, int64_t* weight) {
+  if (int rc = check_mt(m)) return rc;
+  if (!edges || !vertices_seen || !weight) return fail(GS_ERR_INVALID, "null count pointers");
+  *edges = m->edges;
+  *vertices_seen = m->nv;
+  *weight = m->weight;
+  return GS_OK;
+}
+
+int gs_matching_export_device(gs_matching m, int64_t* src, int64_t* dst, int64_t* val, uint64_t* first, size_t cap,
+                              size_t* n) {
+  if (int rc = check_mt(m)) return rc;
+  if (!n) return fail(GS_ERR_INVALID, "n is null");
+  DeviceGuard g(m->device);
+  return export_impl(m, src, dst, val, first, cap, n, false);
+}
+
+int gs_matching_export(gs_matching m, int64_t* src, int64_t* dst, int64_t* val, uint64_t* first, size_t cap,
+                       size_t* n) {
+  if (int rc = check_mt(m)) return rc;
+  if (!n) return fail(GS_ERR_INVALID, "n is null");
+  DeviceGuard g(m->device);
+  return export_impl(m, src, dst, val, first, cap, n, true);
+}
+
+int gs_matching_mate_device(gs_matching m, const int64_t* v, size_t n, int64_t* mate, int64_t* val, uint8_t* found) {
+  if (int rc = check_mt(m)) return rc;
+  if (n == 0) return GS_OK;
+  if (!v) return fail(GS_ERR_INVALID, "null arrays");
+  DeviceGuard g(m->device);
+  if (m->q_cap < n) {
+    GS_HIP(hipStreamSynchronize(m->stream));
+    m->q_cap = 0;
+    GS_HIP(m->q_rank.alloc(n + n / 4));
+    m->q_cap = n + n / 4;
+  }
+  gs::launch_dist_rank(m->vtable(), v, n, m->q_rank, nullptr, m->stream);
+  GS_HIP(hipGetLastError());
+  gs::launch_mt_mate(m->q_rank, n, m->st, m->vid, m->nv, mate, val, found, m->stream);
+  GS_HIP(hipGetLastError());
+  return GS_OK;
+}
+
+int gs_matching_sync(gs_matching m) {
+  if (int rc = check_mt(m)) return rc;
+  DeviceGuard g(m->device);
+  GS_HIP(hipStreamSynchronize(m->stream));
+  return GS_OK;
+}
+
+int gs_matching_get_stream(gs_matching m, void** stream) {
+  if (int rc = check_mt(m)) return rc;
+  if (!stream) return fail(GS_ERR_INVALID, "stream is null");
+  *stream = m->stream;
+  return GS_OK;
+}
+
+int gs_matching_wait_stream(gs_matching m, void* stream) {
+  if (int rc = check_mt(m)) return rc;
+  return m->wait_stream(stream);
+}
+
+// gs_testing.h: the last fold. No device call.
+int gs_testing_matching_stats(void* handle, uint64_t* out) {
+  gs_matching m = static_cast<gs_matching>(handle);
+  if (int rc = check_mt(m)) return rc;
+  if (!out) return fail(GS_ERR_INVALID, "out is null");
+  for (int i = 0; i < 5; ++i) out[i] = m->stats[i];
+  out[5] = m->safe ? 1 : 0;
+  return GS_OK;
+}
+
+int gs_testing_matching_tune(void* handle, int what, int64_t value) {
+  gs_matching m = static_cast<gs_matching>(handle);
+  if (int rc = check_mt(m)) return rc;
+  if (what < 0 || what > 2) return fail(GS_ERR_INVALID, "matching tune: unknown control");
+  m->tune[what] = value < 0 ? -1 : value;
+  return GS_OK;
+}
+
+}  // extern "C"

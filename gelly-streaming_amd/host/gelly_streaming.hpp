@@ -1286,4 +1286,90 @@ class Spanner : public SummaryBulkAggregation<int64_t, EV, AdjacencyListGraphRef
              [k, device] { return std::make_shared<AdjacencyListGraph>(k, device); }, mergeWindowTime, false) {}
 };
 
+// ---------------------------------------------------------------------------
+// weighted matching (gs_summary.h, the gs_matching_* section)
+// ---------------------------------------------------------------------------
+// MatchingEvent (util/MatchingEvent.java:25-44): a Tuple2 (f0 = type, f1 = edge)
+struct MatchingEvent {
+  enum class Type { ADD = GS_MATCH_ADD, REMOVE = GS_MATCH_REMOVE };  // :27
+  Type type;
+  Edge<int64_t, int64_t> edge;
+  Type geType() const { return type; }  // (:36, the reference's spelling)
+  Type getType() const { return type; }
+  const Edge<int64_t, int64_t>& getEdge() const { return edge; }
+  bool operator==(const MatchingEvent& o) const {
+    return type == o.type && edge.f0 == o.edge.f0 && edge.f1 == o.edge.f1 && edge.f2 == o.edge.f2;
+  }
+};
+
+// CentralizedWeightedMatching (example/CentralizedWeightedMatching.java:36-110): the
+// WeightedMatchingFlatMapper at parallelism 1 over the edge stream. The matching lives on the
+// device; `batch` arrivals are folded per call, with the same events whatever the batch size.
+// An arrival's REMOVE events come with the edge at its source endpoint first (the reference
+// iterates a HashSet there).
+class CentralizedWeightedMatching {
+ public:
+  explicit CentralizedWeightedMatching(int device = 0) { gs_check(gs_matching_create(&h_, device, 0)); }
+  ~CentralizedWeightedMatching() { gs_matching_destroy(h_); }
+  CentralizedWeightedMatching(const CentralizedWeightedMatching&) = delete;
+  CentralizedWeightedMatching& operator=(const CentralizedWeightedMatching&) = delete;
+
+  // flatMap (:79-106) over the whole stream, in order
+  std::vector<MatchingEvent> run(const EdgeStream<int64_t, int64_t>& stream, size_t batch = 1 << 16) {
+    std::vector<MatchingEvent> out;
+    if (batch == 0) batch = 1;
+    const size_t n = stream.edges.size();
+    std::vector<int64_t> s, d, w, es, ed, ew;
+    std::vector<uint8_t> type;
+    for (size_t at = 0; at < n; at += batch) {
+      const size_t len = std::min(batch, n - at);
+      s.resize(len);
+      d.resize(len);
+      w.resize(len);
+      for (size_t i = 0; i < len; ++i) {
+        s[i] = stream.edges[at + i].f0;
+        d[i] = stream.edges[at + i].f1;
+        w[i] = stream.edges[at + i].f2;
+      }
+      gs_check(gs_matching_fold(h_, s.data(), d.data(), w.data(), len, nullptr));
+      size_t rows = 0;
+      const int rc = gs_matching_events(h_, nullptr, nullptr, nullptr, nullptr, nullptr, 0, &rows);
+      if (rc != GS_ERR_TRUNCATED) gs_check(rc);
+      if (rows == 0) continue;
+      type.resize(rows);
+      es.resize(rows);
+      ed.resize(rows);
+      ew.resize(rows);
+      gs_check(gs_matching_events(h_, nullptr, type.data(), es.data(), ed.data(), ew.data(), rows, &rows));
+      for (size_t r = 0; r < rows; ++r)
+        out.push_back({type[r] == GS_MATCH_ADD ? MatchingEvent::Type::ADD : MatchingEvent::Type::REMOVE,
+                       {es[r], ed[r], ew[r]}});
+    }
+    return out;
+  }
+
+  // the matching as it stands, in order of acceptance
+  std::vector<Edge<int64_t, int64_t>> matching() const {
+    uint64_t edges = 0, vertices = 0;
+    int64_t weight = 0;
+    gs_check(gs_matching_count(h_, &edges, &vertices, &weight));
+    std::vector<int64_t> s(edges + 1), d(edges + 1), w(edges + 1);
+    size_t n = 0;
+    gs_check(gs_matching_export(h_, s.data(), d.data(), w.data(), nullptr, s.size(), &n));
+    std::vector<Edge<int64_t, int64_t>> out;
+    for (size_t i = 0; i < n; ++i) out.push_back({s[i], d[i], w[i]});
+    return out;
+  }
+  int64_t weight() const {
+    uint64_t edges = 0, vertices = 0;
+    int64_t weight = 0;
+    gs_check(gs_matching_count(h_, &edges, &vertices, &weight));
+    return weight;
+  }
+  gs_matching handle() const { return h_; }
+
+ private:
+  gs_matching h_ = nullptr;
+};
+
 }  // namespace gelly

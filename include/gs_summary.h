@@ -727,6 +727,81 @@ int gs_spanner_sync(gs_spanner s);
 int gs_spanner_get_stream(gs_spanner s, void** stream);
 int gs_spanner_wait_stream(gs_spanner s, void* stream);
 
+/* ---- weighted matching ---------------------------------------------------------------
+ * The streaming greedy weighted matching of example/CentralizedWeightedMatching.java with the
+ * event stream of util/MatchingEvent.java (the reference runs it at parallelism 1 and scans the
+ * whole matching for every edge).
+ *
+ * A matching handle is its own opaque type with its own create call. It holds a set M of edges
+ * (src, dst, value), signed 64-bit each; every id is legal, INT64_MIN and INT64_MAX included. M
+ * starts empty.
+ *   fold     Arrivals are taken in order. For arrival e = (u, v, w): collisions(e) is the set of
+ *            edges of M that have u or v as an endpoint -- at most two; one edge that touches both
+ *            endpoints counts once; for a self-loop e = (u, u) it is u's edge. sum is the sum of
+ *            their values in Java long arithmetic, wrapping. e is accepted iff w > 2 * sum,
+ *            wrapping again (CentralizedWeightedMatching.java:79-106). An accepted e removes its
+ *            collisions from M and joins M, its orientation kept. accepted[i] = 1 / 0.
+ *            M is therefore always a matching, and M is a function of the stream order alone,
+ *            however the stream is cut into folds: the fold runs in parallel (rounds of
+ *            reservations) and is exact to that order.
+ *   events   The MatchingEvent stream of the last fold: each accepted arrival gives its REMOVE
+ *            events and then one ADD; rows (arrival index in the fold, type, src, dst, value)
+ *            ascending by arrival. The reference emits the one or two REMOVEs of an arrival in
+ *            HashSet iteration order, an accident of hash codes; here the edge at the arrival's
+ *            source endpoint comes first, then the edge at its target endpoint.
+ * Consequences: a value <= 0 is never accepted while no sum has wrapped; a repeated edge is
+ * rejected (w > 2 w is false for w >= 0); direction does not matter for collisions but is kept in
+ * M and in events.
+ *
+ * Synchronisation: a fold waits for the handle's stream once per round it runs outside the tail
+ * (two words read back; RMAT streams take about ten rounds, a fold of fewer than 4096
+ * arrivals takes none) and once at its end (the counts); the tail
+ * (one workgroup, no host round trip) finishes what the rounds leave. Every allocation is
+ * counted by gs_hbm_bytes and released by gs_matching_destroy. Null handles and pointers return
+ * GS_ERR_INVALID before any device call.
+ *
+ * gs_matching_create: vertex_hint sizes the first allocation only (the handle grows).
+ * gs_matching_reset: M empty, no vertex seen, capacity kept.
+ * gs_matching_fold / _fold_device: n arrivals from HOST arrays (copied before the call returns) /
+ *   DEVICE arrays read on the handle's stream, element i at index i * stride; accepted (may be
+ *   NULL): n bytes, HOST / DEVICE. A fold of more than 2^30 arrivals is cut into pieces by the
+ *   library, with the same result; its events are then not kept (gs_matching_events returns
+ *   GS_ERR_INVALID until the next fold).
+ * gs_matching_events / _events_device: the last fold's event rows into HOST / DEVICE arrays of
+ *   capacity cap (any array may be NULL); *n = the rows. cap < rows: GS_ERR_TRUNCATED, *n set,
+ *   nothing written.
+ * gs_matching_count: |M|, the distinct vertex ids seen since reset, and the wrapping sum of M's
+ *   values. No device call.
+ * gs_matching_export / _export_device: M ascending by the global arrival number (since reset) at
+ *   which each edge was accepted, that number in first[] (any array may be NULL); cap and n as
+ *   for events.
+ * gs_matching_mate_device: per queried DEVICE id v[i]: found[i] = v[i] is matched, mate[i] = its
+ *   partner in M (itself for a loop), val[i] = the edge's value; 0, 0, 0 otherwise.
+ * gs_matching_sync / _get_stream / _wait_stream: as gs_sync / gs_get_stream / gs_wait_stream.
+ * Not built: combine, serialization, multi-GPU groups, deletions. */
+enum gs_matching_event { GS_MATCH_ADD = 0, GS_MATCH_REMOVE = 1 }; /* MatchingEvent.Type */
+typedef struct gs_matching_s* gs_matching;
+int gs_matching_create(gs_matching* out, int device, uint64_t vertex_hint);
+int gs_matching_destroy(gs_matching m); /* NULL is GS_OK */
+int gs_matching_reset(gs_matching m);
+int gs_matching_fold(gs_matching m, const int64_t* src, const int64_t* dst, const int64_t* val, size_t n,
+                     uint8_t* accepted);
+int gs_matching_fold_device(gs_matching m, const int64_t* src, const int64_t* dst, const int64_t* val, size_t n,
+                            uint8_t* accepted, size_t stride);
+int gs_matching_events(gs_matching m, uint32_t* arrival, uint8_t* type, int64_t* src, int64_t* dst, int64_t* val,
+                       size_t cap, size_t* n);
+int gs_matching_events_device(gs_matching m, uint32_t* arrival, uint8_t* type, int64_t* src, int64_t* dst,
+                              int64_t* val, size_t cap, size_t* n);
+int gs_matching_count(gs_matching m, uint64_t* edges, uint64_t* vertices_seen, int64_t* weight);
+int gs_matching_export(gs_matching m, int64_t* src, int64_t* dst, int64_t* val, uint64_t* first, size_t cap,
+                       size_t* n);
+int gs_matching_export_device(gs_matching m, int64_t* src, int64_t* dst, int64_t* val, uint64_t* first, size_t cap,
+                              size_t* n);
+int gs_matching_mate_device(gs_matching m, const int64_t* v, size_t n, int64_t* mate, int64_t* val, uint8_t* found);
+int gs_matching_sync(gs_matching m);
+int gs_matching_get_stream(gs_matching m, void** stream);
+int gs_matching_wait_stream(gs_matching m, void* stream);
+
 /* ---- introspection -----------------------------------------------------------
  * The HIP stream (hipStream_t) the handle enqueues on, and per-kernel timing:
  * when profiling is on, every launch is bracketed by HIP events on the stream it

@@ -116,6 +116,22 @@ int gs_testing_distinct_phases(void* d, uint64_t* out);
  * rounds), out[5] = the longest row (adjacency plus pending entries) a search expanded. Six words. */
 int gs_testing_spanner_stats(void* s, uint64_t* out);
 
+/* The last fold of a matching handle (`m` is a gs_matching; no device call; zero after a reset
+ * but the last word): out[0] = rounds run (the tail's included), out[1] = fixpoint passes in
+ * total, out[2] = arrivals still pending when the tail took over (the arrivals the tail
+ * decided), out[3] = arrivals accepted, out[4] = rounds that hit the pass cap before the
+ * fixpoint and fell back to plain reservations, out[5] = 1 while the handle is weight-safe
+ * (every value folded since the last reset lies in [0, 2^61): sharpening applies). Six words. */
+int gs_testing_matching_stats(void* m, uint64_t* out);
+
+/* Per-handle controls of a matching handle's folds (`m` is a gs_matching; not a knob of
+ * gs_testing_set): what = 0 the round cap (product: 32 rounds, and fewer than 4096 pending
+ * arrivals go to the tail at once; a set value fixes the rounds alone: 0 sends everything to the
+ * tail, a huge one leaves no tail), what = 1 the cap of fixpoint passes per round (product: 6;
+ * clamped to 1..64), what = 2 sharpening off (value != 0). A value < 0 restores the product
+ * value. Returns GS_OK or GS_ERR_INVALID. */
+int gs_testing_matching_tune(void* m, int what, int64_t value);
+
 #ifdef __cplusplus
 }
 #endif
