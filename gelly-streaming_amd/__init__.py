@@ -509,24 +509,32 @@ def _ptr(x):
     raise TypeError(type(x))
 
 
-class Summary:
-    """One GPU-resident summary (DisjointSet for kind 'cc', signed forest for
-    kind 'signed'). Thin owner of a gs_handle; see include/gs_summary.h."""
+def _int64s(x):
+    """x as a contiguous int64 numpy array (what the host entry points read)."""
+    return np.ascontiguousarray(np.asarray(x, dtype=np.int64))
 
-    def __init__(self, kind="cc", device=0, capacity_hint=1 << 20):
-        self.kind = {"cc": KIND_CC, "signed": KIND_SIGNED}[kind] if isinstance(kind, str) else int(kind)
-        self.device = device
-        h = _vp()
-        _check(lib().gs_create(ctypes.byref(h), device, self.kind, capacity_hint))
-        self._h = h
-        # A/B runs: GS_HOT_INDEX=0 turns the hot index's default off (set_hot_index still forces it)
-        if self.kind == KIND_CC and os.environ.get("GS_HOT_INDEX") == "0":
-            _check(lib().gs_set_hot_index(h, -1, 0, 0))
 
-    # --- lifecycle
+def _edges(src, dst):
+    """The two endpoint arrays of a host fold, of one shape."""
+    s, d = _int64s(src), _int64s(dst)
+    assert s.shape == d.shape
+    return s, d
+
+
+class _Handle:
+    """The owner of one C handle, and the entry points every handle type has. A subclass names
+    its C prefix (_PREFIX = "gs_triangle": gs_triangle_destroy, gs_triangle_sync,
+    gs_triangle_get_stream, gs_triangle_wait_stream), creates the handle into self._h and sets
+    self.device."""
+
+    _PREFIX = None
+
+    def _call(self, name, *args):
+        _check(getattr(lib(), "%s_%s" % (self._PREFIX, name))(self._h, *args))
+
     def close(self):
         if getattr(self, "_h", None):
-            lib().gs_destroy(self._h)
+            getattr(lib(), self._PREFIX + "_destroy")(self._h)
             self._h = None
 
     def __del__(self):
@@ -545,32 +553,67 @@ class Summary:
     def handle(self):
         return self._h
 
+    @property
+    def stream(self):
+        """The handle's stream (a raw hipStream_t): device entry points queue their work there."""
+        s = _vp()
+        self._call("get_stream", ctypes.byref(s))
+        return s.value
+
+    def sync(self):
+        self._call("sync")
+
+    def wait_stream(self, stream="torch"):
+        """Every later operation of the handle waits (on the device) for the work queued on
+        `stream` so far: a torch.cuda.Stream, a raw hipStream_t, or "torch" (torch's current
+        stream). <prefix>_wait_stream."""
+        if isinstance(stream, str):
+            import torch
+            stream = torch.cuda.current_stream(self.device)
+        self._call("wait_stream", stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream))
+
+
+class _ResetHandle(_Handle):
+    """A handle type with <prefix>_reset."""
+
     def reset(self):
-        _check(lib().gs_reset(self._h))
+        """Back to the empty state; capacity is kept (and what the class's docstring names)."""
+        self._call("reset")
+
+
+class Summary(_ResetHandle):
+    """One GPU-resident summary (DisjointSet for kind 'cc', signed forest for
+    kind 'signed'). Thin owner of a gs_handle; see include/gs_summary.h."""
+
+    _PREFIX = "gs"
+
+    def __init__(self, kind="cc", device=0, capacity_hint=1 << 20):
+        self.kind = {"cc": KIND_CC, "signed": KIND_SIGNED}[kind] if isinstance(kind, str) else int(kind)
+        self.device = device
+        h = _vp()
+        _check(lib().gs_create(ctypes.byref(h), device, self.kind, capacity_hint))
+        self._h = h
+        # A/B runs: GS_HOT_INDEX=0 turns the hot index's default off (set_hot_index still forces it)
+        if self.kind == KIND_CC and os.environ.get("GS_HOT_INDEX") == "0":
+            _check(lib().gs_set_hot_index(h, -1, 0, 0))
 
     def reset_config(self):
         """gs_reset_config: reset plus the default configuration (tracking off,
         pipelining 1, profiling off), as a handle pool's release does."""
         _check(lib().gs_reset_config(self._h))
 
-    def sync(self):
-        _check(lib().gs_sync(self._h))
-
     # --- fold / combine
     def fold(self, src, dst):
         """Fold host edges (int64 numpy arrays or sequences)."""
-        s = np.ascontiguousarray(np.asarray(src, dtype=np.int64))
-        d = np.ascontiguousarray(np.asarray(dst, dtype=np.int64))
-        assert s.shape == d.shape
+        s, d = _edges(src, dst)
         _check(lib().gs_fold(self._h, s.ctypes.data, d.ctypes.data, len(s)))
 
     def fold_parity(self, src, dst, w):
         """Fold host edges with a required parity each (gs_fold_parity; signed kind:
         w = 1 different sides, 0 same side)."""
-        s = np.ascontiguousarray(np.asarray(src, dtype=np.int64))
-        d = np.ascontiguousarray(np.asarray(dst, dtype=np.int64))
+        s, d = _edges(src, dst)
         ww = np.ascontiguousarray(np.asarray(w, dtype=np.uint8))
-        assert s.shape == d.shape == ww.shape
+        assert s.shape == ww.shape
         _check(lib().gs_fold_parity(self._h, s.ctypes.data, d.ctypes.data, ww.ctypes.data, len(s)))
 
     def fold_device(self, src, dst, n=None, stride=1, w=None, after=None):
@@ -585,16 +628,6 @@ class Summary:
         if after is not None:
             self.wait_stream(after)
         _check(lib().gs_fold_device(self._h, _ptr(src), _ptr(dst), _ptr(w), int(n), int(stride)))
-
-    def wait_stream(self, stream="torch"):
-        """Every later operation of the summary waits (on the device) for the work queued
-        on `stream` so far: a torch.cuda.Stream, a raw hipStream_t, or "torch" (torch's
-        current stream). gs_wait_stream."""
-        if isinstance(stream, str):
-            import torch
-            stream = torch.cuda.current_stream(self.device)
-        raw = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
-        _check(lib().gs_wait_stream(self._h, raw))
 
     def wait_event(self, event):
         """Every later operation waits for a recorded torch.cuda.Event (or raw hipEvent_t)."""
@@ -834,12 +867,6 @@ class Summary:
         _check(lib().gs_fold_records_counted_device(self._h, _ptr(rec), int(cap), _ptr(count), 1 if track else 0))
 
     # --- introspection
-    @property
-    def stream(self):
-        s = _vp()
-        _check(lib().gs_get_stream(self._h, ctypes.byref(s)))
-        return s.value
-
     def set_profiling(self, on=True):
         _check(lib().gs_set_profiling(self._h, 1 if on else 0))
 
@@ -908,11 +935,13 @@ class Summary:
 
 
 # ---------------------------------------------------------------- degree summary
-class Degrees:
+class Degrees(_ResetHandle):
     """Streaming vertex degrees and their distribution (GS_KIND_DEGREE; the gs_degree_*
     section of include/gs_summary.h): SimpleEdgeStream.getDegrees / getInDegrees /
     getOutDegrees for direction "all" / "in" / "out", with optional edge deletions
     (example/DegreeDistribution.java). Owns a gs_handle."""
+
+    _PREFIX = "gs"
 
     DIRECTIONS = {"all": DEGREE_ALL, "in": DEGREE_IN, "out": DEGREE_OUT}
 
@@ -922,39 +951,6 @@ class Degrees:
         h = _vp()
         _check(lib().gs_create(ctypes.byref(h), device, KIND_DEGREE, capacity_hint))
         self._h = h
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().gs_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    @property
-    def handle(self):
-        return self._h
-
-    @property
-    def stream(self):
-        s = _vp()
-        _check(lib().gs_get_stream(self._h, ctypes.byref(s)))
-        return s.value
-
-    def reset(self):
-        _check(lib().gs_reset(self._h))
-
-    def sync(self):
-        _check(lib().gs_sync(self._h))
 
     def num_vertices(self):
         """Table entries: every vertex ever collected, those whose net count is <= 0 included."""
@@ -967,19 +963,10 @@ class Degrees:
         _check(lib().gs_table_capacity(self._h, ctypes.byref(n)))
         return n.value
 
-    def wait_stream(self, stream="torch"):
-        if isinstance(stream, str):
-            import torch
-            stream = torch.cuda.current_stream(self.device)
-        raw = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
-        _check(lib().gs_wait_stream(self._h, raw))
-
     # --- fold / combine
     def fold(self, src, dst, deletions=None):
         """Fold host edges (int64 arrays); deletions: optional uint8 per edge, bit 0 = deletion."""
-        s = np.ascontiguousarray(np.asarray(src, dtype=np.int64))
-        d = np.ascontiguousarray(np.asarray(dst, dtype=np.int64))
-        assert s.shape == d.shape
+        s, d = _edges(src, dst)
         e = None
         if deletions is not None:
             e = np.ascontiguousarray(np.asarray(deletions, dtype=np.uint8))
@@ -1056,12 +1043,15 @@ class Degrees:
 
 
 # ---------------------------------------------------------------- triangle summary
-class Triangles:
+class Triangles(_ResetHandle):
     """Exact triangle counts of a streamed graph (the gs_triangle_* section of
     include/gs_summary.h): the count of each window's graph (example/WindowTriangles: `window`)
     or the running global and per-vertex counts of an insertion-only stream
     (example/ExactTriangleCount: `fold` after `fold`). Direction, repeated edges and self-loops
-    do not change the graph. Owns a gs_triangles handle."""
+    do not change the graph. `reset`: the graph empty and every counter zero; capacity is kept.
+    Owns a gs_triangles handle."""
+
+    _PREFIX = "gs_triangle"
 
     def __init__(self, device=0, edge_hint=1 << 20):
         self.device = device
@@ -1069,52 +1059,9 @@ class Triangles:
         _check(lib().gs_triangle_create(ctypes.byref(h), device, int(edge_hint)))
         self._h = h
 
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().gs_triangle_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    @property
-    def handle(self):
-        return self._h
-
-    @property
-    def stream(self):
-        s = _vp()
-        _check(lib().gs_triangle_get_stream(self._h, ctypes.byref(s)))
-        return s.value
-
-    def reset(self):
-        """The graph empty and every counter zero; capacity is kept."""
-        _check(lib().gs_triangle_reset(self._h))
-
-    def sync(self):
-        _check(lib().gs_triangle_sync(self._h))
-
-    def wait_stream(self, stream="torch"):
-        if isinstance(stream, str):
-            import torch
-            stream = torch.cuda.current_stream(self.device)
-        raw = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
-        _check(lib().gs_triangle_wait_stream(self._h, raw))
-
     def fold(self, src, dst):
         """Fold host edges (int64 arrays)."""
-        s = np.ascontiguousarray(np.asarray(src, dtype=np.int64))
-        d = np.ascontiguousarray(np.asarray(dst, dtype=np.int64))
-        assert s.shape == d.shape
+        s, d = _edges(src, dst)
         _check(lib().gs_triangle_fold(self._h, s.ctypes.data, d.ctypes.data, len(s)))
 
     def fold_device(self, src, dst, n=None, stride=1, after=None):
@@ -1184,12 +1131,14 @@ class Triangles:
 
 
 # ---------------------------------------------------------------- window slices
-class Slice:
+class Slice(_Handle):
     """The per-vertex neighbourhoods of one window of (src, dst, value) edges (the gs_slice_*
     section of include/gs_summary.h: SimpleEdgeStream.slice and its SnapshotStream): `window`
     replaces the handle's window, `reduce` gives one value per vertex (reduceOnEdges),
     `neighborhoods` the CSR that foldNeighbors / applyOnNeighbors iterate, entries in arrival
     order. Nothing is deduplicated. Owns a gs_slices handle."""
+
+    _PREFIX = "gs_slice"
 
     def __init__(self, device=0, edge_hint=0):
         self.device = device
@@ -1198,51 +1147,12 @@ class Slice:
         self._h = h
         self._has_val = True  # the current window carries values (an empty one reads none)
 
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().gs_slice_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    @property
-    def handle(self):
-        return self._h
-
-    @property
-    def stream(self):
-        s = _vp()
-        _check(lib().gs_slice_get_stream(self._h, ctypes.byref(s)))
-        return s.value
-
-    def sync(self):
-        _check(lib().gs_slice_sync(self._h))
-
-    def wait_stream(self, stream="torch"):
-        if isinstance(stream, str):
-            import torch
-            stream = torch.cuda.current_stream(self.device)
-        raw = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
-        _check(lib().gs_slice_wait_stream(self._h, raw))
-
     def window(self, src, dst, val=None, direction="out"):
         """One window of host edges (int64 arrays; val None: a stream without values)."""
-        s = np.ascontiguousarray(np.asarray(src, dtype=np.int64))
-        d = np.ascontiguousarray(np.asarray(dst, dtype=np.int64))
-        assert s.shape == d.shape
+        s, d = _edges(src, dst)
         w = None
         if val is not None:
-            w = np.ascontiguousarray(np.asarray(val, dtype=np.int64))
+            w = _int64s(val)
             assert w.shape == s.shape
         _check(lib().gs_slice_window(self._h, s.ctypes.data, d.ctypes.data, None if w is None else w.ctypes.data,
                                      len(s), _slice_dir(direction)))
@@ -1328,13 +1238,16 @@ def _slice_op(op):
 
 
 # ---------------------------------------------------------------- distinct streams
-class Distinct:
+class Distinct(_ResetHandle):
     """The first-seen edges and vertices of an edge stream (the gs_distinct_* section of
     include/gs_summary.h: SimpleEdgeStream.distinct and getVertices): `fold` answers which edges
     and endpoint entries of a batch are seen for the first time, always keeping the arrival-first
     occurrence; `vertices` lists every vertex in first-appearance (rank) order and `edges` every
     edge by first arrival. mode: "directed" keys an edge by (src, dst), "undirected" by the
-    unordered pair. Owns a gs_distinct handle."""
+    unordered pair. `reset`: both sets empty and folded = 0; capacity is kept. Owns a gs_distinct
+    handle."""
+
+    _PREFIX = "gs_distinct"
 
     def __init__(self, device=0, mode="directed", vertex_hint=0, edge_hint=0):
         self.device = device
@@ -1343,52 +1256,9 @@ class Distinct:
         _check(lib().gs_distinct_create(ctypes.byref(h), device, self.mode, int(vertex_hint), int(edge_hint)))
         self._h = h
 
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().gs_distinct_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    @property
-    def handle(self):
-        return self._h
-
-    @property
-    def stream(self):
-        s = _vp()
-        _check(lib().gs_distinct_get_stream(self._h, ctypes.byref(s)))
-        return s.value
-
-    def sync(self):
-        _check(lib().gs_distinct_sync(self._h))
-
-    def wait_stream(self, stream="torch"):
-        if isinstance(stream, str):
-            import torch
-            stream = torch.cuda.current_stream(self.device)
-        raw = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
-        _check(lib().gs_distinct_wait_stream(self._h, raw))
-
-    def reset(self):
-        """Both sets empty and folded = 0; capacity is kept."""
-        _check(lib().gs_distinct_reset(self._h))
-
     def fold(self, src, dst):
         """Fold host edges (int64 arrays); returns (new_vertices, new_edges) of this fold."""
-        s = np.ascontiguousarray(np.asarray(src, dtype=np.int64))
-        d = np.ascontiguousarray(np.asarray(dst, dtype=np.int64))
-        assert s.shape == d.shape
+        s, d = _edges(src, dst)
         _check(lib().gs_distinct_fold(self._h, s.ctypes.data, d.ctypes.data, len(s)))
         return self.size()[3:]
 
@@ -1518,11 +1388,14 @@ def _cap_of(cap, *arrays):
 
 
 # ---------------------------------------------------------------- k-spanner summary
-class Spanner:
+class Spanner(_ResetHandle):
     """The streaming k-spanner of library/Spanner.java (the gs_spanner_* section of
     include/gs_summary.h): an arriving edge is accepted into the graph iff its endpoints are more
     than k edges apart in the graph the edges before it left, exactly in arrival order however
-    the stream is cut into folds. Owns a gs_spanner handle."""
+    the stream is cut into folds. `reset`: the graph empty; capacity and k are kept. Owns a
+    gs_spanner handle."""
+
+    _PREFIX = "gs_spanner"
 
     def __init__(self, k=3, device=0, edge_hint=1 << 16):
         self.device = device
@@ -1531,52 +1404,9 @@ class Spanner:
         _check(lib().gs_spanner_create(ctypes.byref(h), device, int(k), int(edge_hint)))
         self._h = h
 
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().gs_spanner_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    @property
-    def handle(self):
-        return self._h
-
-    @property
-    def stream(self):
-        s = _vp()
-        _check(lib().gs_spanner_get_stream(self._h, ctypes.byref(s)))
-        return s.value
-
-    def reset(self):
-        """The graph empty; capacity and k are kept."""
-        _check(lib().gs_spanner_reset(self._h))
-
-    def sync(self):
-        _check(lib().gs_spanner_sync(self._h))
-
-    def wait_stream(self, stream="torch"):
-        if isinstance(stream, str):
-            import torch
-            stream = torch.cuda.current_stream(self.device)
-        raw = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
-        _check(lib().gs_spanner_wait_stream(self._h, raw))
-
     def fold(self, src, dst):
         """Fold host edges (int64 arrays) in arrival order; returns the accepted mask (bool)."""
-        s = np.ascontiguousarray(np.asarray(src, dtype=np.int64))
-        d = np.ascontiguousarray(np.asarray(dst, dtype=np.int64))
-        assert s.shape == d.shape
+        s, d = _edges(src, dst)
         acc = np.zeros(len(s), np.uint8)
         _check(lib().gs_spanner_fold(self._h, s.ctypes.data, d.ctypes.data, len(s), acc.ctypes.data))
         return acc.astype(bool)
@@ -1593,16 +1423,12 @@ class Spanner:
 
     def add(self, src, dst):
         """AdjacencyListGraph.addEdge for host edges: each joins the graph unless it is there."""
-        s = np.ascontiguousarray(np.asarray(src, dtype=np.int64))
-        d = np.ascontiguousarray(np.asarray(dst, dtype=np.int64))
-        assert s.shape == d.shape
+        s, d = _edges(src, dst)
         _check(lib().gs_spanner_add(self._h, s.ctypes.data, d.ctypes.data, len(s)))
 
     def within(self, src, dst, k=None):
         """boundedBFS(src[i], dst[i], k) on the graph as it stands, host arrays; bool array."""
-        s = np.ascontiguousarray(np.atleast_1d(np.asarray(src, dtype=np.int64)))
-        d = np.ascontiguousarray(np.atleast_1d(np.asarray(dst, dtype=np.int64)))
-        assert s.shape == d.shape
+        s, d = _edges(np.atleast_1d(src), np.atleast_1d(dst))
         out = np.zeros(len(s), np.uint8)
         _check(lib().gs_spanner_within(self._h, s.ctypes.data, d.ctypes.data, len(s),
                                        self.k if k is None else int(k), out.ctypes.data))
@@ -1662,11 +1488,14 @@ class Spanner:
 
 
 # ---------------------------------------------------------------- weighted matching
-class Matching:
+class Matching(_ResetHandle):
     """The streaming greedy weighted matching of example/CentralizedWeightedMatching.java (the
     gs_matching_* section of include/gs_summary.h): an arriving edge (u, v, w) joins the matching
     M iff w > 2 * (the values of M's edges at u and v), in Java long arithmetic, and then removes
-    them; exactly in arrival order however the stream is cut into folds. Owns a gs_matching handle."""
+    them; exactly in arrival order however the stream is cut into folds. `reset`: M empty, no vertex
+    seen, weight-safe again; capacity and tuning are kept. Owns a gs_matching handle."""
+
+    _PREFIX = "gs_matching"
 
     def __init__(self, device=0, vertex_hint=1 << 16):
         self.device = device
@@ -1674,53 +1503,11 @@ class Matching:
         _check(lib().gs_matching_create(ctypes.byref(h), device, int(vertex_hint)))
         self._h = h
 
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().gs_matching_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    @property
-    def handle(self):
-        return self._h
-
-    @property
-    def stream(self):
-        s = _vp()
-        _check(lib().gs_matching_get_stream(self._h, ctypes.byref(s)))
-        return s.value
-
-    def reset(self):
-        """M empty, no vertex seen, weight-safe again; capacity and tuning are kept."""
-        _check(lib().gs_matching_reset(self._h))
-
-    def sync(self):
-        _check(lib().gs_matching_sync(self._h))
-
-    def wait_stream(self, stream="torch"):
-        if isinstance(stream, str):
-            import torch
-            stream = torch.cuda.current_stream(self.device)
-        raw = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
-        _check(lib().gs_matching_wait_stream(self._h, raw))
-
     def fold(self, src, dst, val):
         """Fold host arrivals (int64 arrays) in order; returns the accepted mask (bool)."""
-        s = np.ascontiguousarray(np.asarray(src, dtype=np.int64))
-        d = np.ascontiguousarray(np.asarray(dst, dtype=np.int64))
-        w = np.ascontiguousarray(np.asarray(val, dtype=np.int64))
-        assert s.shape == d.shape == w.shape
+        s, d = _edges(src, dst)
+        w = _int64s(val)
+        assert s.shape == w.shape
         acc = np.zeros(len(s), np.uint8)
         _check(lib().gs_matching_fold(self._h, s.ctypes.data, d.ctypes.data, w.ctypes.data, len(s), acc.ctypes.data))
         return acc.astype(bool)

@@ -245,16 +245,15 @@ int hot_after_fold(gs_summary* h, const int64_t* src, const int64_t* dst, size_t
       if (i == gs_summary::kLanes || h->lane[i]) GS_HIP(hipStreamWaitEvent(st, h->hot_read[b][i], 0));
     h->hot_read_on[b] = false;
   }
-  if (build) {
-    gs::launch_hot_build(h->table(), src, dst, (uint32_t)std::min(c, kHotSampleEdges), (uint32_t)stride, h->hot_buf[b],
-                         hl, h->hot_scratch, st);
+  if (build) {  // (counted whether or not the launch is accepted)
     h->hot_folds = 0;
     h->hot_builds++;
+    GS_LAUNCH(gs::launch_hot_build(h->table(), src, dst, (uint32_t)std::min(c, kHotSampleEdges), (uint32_t)stride,
+                                   h->hot_buf[b], hl, h->hot_scratch, st));
   } else {
-    gs::launch_hot_refresh(h->table(), h->hot_buf[h->hot_live], h->hot_buf[b], hl, st);
     h->hot_refreshes++;
+    GS_LAUNCH(gs::launch_hot_refresh(h->table(), h->hot_buf[h->hot_live], h->hot_buf[b], hl, st));
   }
-  GS_HIP(hipGetLastError());
   GS_HIP(hipEventRecord(h->hot_built, st));
   h->hot_building = b;
   h->hot_folds_r = 0;
@@ -508,9 +507,8 @@ int server_start(gs_summary* h) {
   // (GS_TESTING_SERVER_IDLE_US, include/gs_testing.h).
   const int64_t idle_us = testing_value(GS_TESTING_SERVER_IDLE_US, 2000);
   const unsigned long long idle_ticks = (unsigned long long)std::max<int64_t>(idle_us, 1) * 100ull;
-  gs::launch_window_server(h->kind == GS_KIND_SIGNED, h->table(), h->delta(), h->srv.box, h->srv.bc, h->done_dev,
-                           h->srv_seq, idle_ticks, h->stream);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_window_server(h->kind == GS_KIND_SIGNED, h->table(), h->delta(), h->srv.box, h->srv.bc,
+                                     h->done_dev, h->srv_seq, idle_ticks, h->stream));
   h->srv_running = true;
   h->srv_launches++;
   return GS_OK;
@@ -547,8 +545,7 @@ int wait_stream(gs_summary* h, const uint32_t* vals, uint64_t* value, int nvals,
   if (!st) st = h->stream;
   if (!vals && !(st == h->stream && h->xwait) && stream_idle(h, st)) return GS_OK;  // already idle (no launch)
   const unsigned long long seq = ++h->done_seq;
-  gs::launch_signal(h->done_dev, seq, vals, nvals, stride, st, clear, flag);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_signal(h->done_dev, seq, vals, nvals, stride, st, clear, flag));
   if (int rc = wait_done(h, seq, st)) return rc;
   if (st == h->stream) h->xwait = false;
   if (value) return done_value_read(h, 1, seq, value);
@@ -645,9 +642,8 @@ hipStream_t report_stream_of(const gs_summary* h, int rs) {
 int launch_report_now(gs_summary* h, int rs, hipStream_t st) {
   const uint64_t claim = h->rep_pending[rs];
   if (!claim) return GS_OK;
-  gs::launch_report(h->ctr, claim, h->rep.dev() + (h->rep_seq++ % gs_summary::kRepRing), (unsigned)(h->rep_epoch & 7u),
-                    st);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_report(h->ctr, claim, h->rep.dev() + (h->rep_seq++ % gs_summary::kRepRing),
+                              (unsigned)(h->rep_epoch & 7u), st));
   h->rep_pending_edges -= claim;
   h->rep_pending[rs] = 0;
   return GS_OK;
@@ -764,8 +760,7 @@ int fold_device_impl(gs_summary* h, const int64_t* src, const int64_t* dst, cons
       }
       const uint64_t slots = 2 * next_pow2(c);  // load factor <= 1/2
       GS_HIP(hipMemsetAsync(h->dd_tab[set], 0xFF, slots * 16, st));
-      gs::launch_dedup(f.src, f.dst, c, h->dd_tab[set], (uint32_t)(slots - 1), h->dd_w[set], st);
-      GS_HIP(hipGetLastError());
+      GS_LAUNCH(gs::launch_dedup(f.src, f.dst, c, h->dd_tab[set], (uint32_t)(slots - 1), h->dd_w[set], st));
       f.w = h->dd_w[set];
       f.w_stride = 1;
     }
@@ -886,7 +881,7 @@ int export_device_impl(gs_summary* h, int64_t* v, int64_t* l, uint8_t* p, size_t
   // from it instead of 2 per edge of the chunks whose reports ride on launches not yet made
   if (nparts == 1) note_exact_count(h, cnt);
   *n = cnt;
-  if (cnt > cap) return fail(GS_ERR_TRUNCATED, "output capacity " + std::to_string(cap) + " < " + std::to_string(cnt));
+  if (cnt > cap) return truncated(cap, cnt);
   return GS_OK;
 }
 
@@ -1236,8 +1231,7 @@ int gs_find(gs_handle h, int64_t v, int64_t* label, int* found) {
   if (!label || !found) return fail(GS_ERR_INVALID, "null output");
   DeviceGuard g(h->device);
   if (int rc_ = join_lanes(h)) return rc_;
-  gs::launch_find_one(h->table(), v, h->d_scratch, h->stream);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_find_one(h->table(), v, h->d_scratch, h->stream));
   int64_t out[2];
   GS_HIP(hipMemcpyAsync(out, h->d_scratch, 16, hipMemcpyDeviceToHost, h->stream));
   GS_HIP(hipStreamSynchronize(h->stream));
@@ -1252,8 +1246,7 @@ int gs_find_labels_device(gs_handle h, const int64_t* v, size_t n, int64_t* labe
   DeviceGuard g(h->device);
   if (int rc_ = join_lanes(h)) return rc_;
   if (!n) return GS_OK;
-  gs::launch_find_batch(h->table(), v, n, label, found, nullptr, h->stream);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_find_batch(h->table(), v, n, label, found, nullptr, h->stream));
   return GS_OK;
 }
 
@@ -1265,8 +1258,7 @@ int gs_digest(gs_handle h, uint64_t* digest) {
   unsigned long long* d = reinterpret_cast<unsigned long long*>(h->d_scratch.get());
   uint32_t failed = 0;
   GS_HIP(hipMemsetAsync(d, 0, 8, h->stream));
-  gs::launch_digest(h->table(), d, std::min<uint64_t>(h->nv_ub, h->cap + 1), h->stream);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_digest(h->table(), d, std::min<uint64_t>(h->nv_ub, h->cap + 1), h->stream));
   unsigned long long out = 0;
   GS_HIP(hipMemcpyAsync(&out, d, 8, hipMemcpyDeviceToHost, h->stream));
   GS_HIP(hipMemcpyAsync(&failed, h->ctr + gs::ctr_index(gs::CTR_FAIL), 4, hipMemcpyDeviceToHost, h->stream));
@@ -1298,7 +1290,7 @@ static int export_host(gs_handle h, int64_t* v, int64_t* l, uint8_t* p, size_t c
   int rc = read_nv(h, &nv);
   if (rc) return rc;
   *n = nv;
-  if (cap < nv) return fail(GS_ERR_TRUNCATED, "output capacity " + std::to_string(cap) + " < " + std::to_string(nv));
+  if (cap < nv) return truncated(cap, nv);
   if (nv == 0) return GS_OK;
   if ((rc = ensure_x(h, nv + 1))) return rc;
   if ((rc = wait_x_consumer(h))) return rc;
@@ -1395,22 +1387,12 @@ static int gather_rows(gs_handle h, uint64_t* n) {
 
 // Device staging of the host-array form: nv members / signs, nc components.
 static int ensure_comp_staging(gs_handle h, uint64_t nv, uint64_t nc) {
-  if (h->co_vcap < nv) {
-    GS_HIP(hipStreamSynchronize(h->stream));
-    h->co_vcap = 0;
-    const uint64_t c = nv + nv / 4;
-    GS_HIP(h->co_member.alloc(c));
-    GS_HIP(h->co_sign.alloc(c));
-    h->co_vcap = c;
-  }
-  if (h->co_ccap < nc) {
-    GS_HIP(hipStreamSynchronize(h->stream));
-    h->co_ccap = 0;
-    const uint64_t c = nc + nc / 4;
-    GS_HIP(h->co_comp.alloc(c));
-    GS_HIP(h->co_off.alloc(c + 1));
-    h->co_ccap = c;
-  }
+  GS_HIP(grow_group(h->stream, h->co_vcap, nv, nv + nv / 4,
+                    [&](uint64_t c) { return alloc_each(c, h->co_member, h->co_sign); }));
+  GS_HIP(grow_group(h->stream, h->co_ccap, nc, nc + nc / 4, [&](uint64_t c) {
+    const hipError_t e = h->co_comp.alloc(c);
+    return e != hipSuccess ? e : h->co_off.alloc(c + 1);
+  }));
   return GS_OK;
 }
 
@@ -1431,8 +1413,7 @@ static int components_impl(gs_handle h, int64_t* comp, uint64_t* offset, int64_t
   if (int rc = sort_scratch_ensure(ss, n, h->stream)) return rc;
   std::vector<uint32_t> ctl(gs::kSortCtlWords);
   GS_HIP(hipMemsetAsync(ss.ctl, 0, gs::kSortCtlWords * 4, h->stream));
-  gs::launch_sort_digits(h->x_v, h->x_l, n, ss.ctl, h->stream);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_sort_digits(h->x_v, h->x_l, n, ss.ctl, h->stream));
   GS_HIP(hipMemcpyAsync(ctl.data(), ss.ctl, gs::kSortCtlWords * 4, hipMemcpyDeviceToHost, h->stream));
   GS_HIP(hipStreamSynchronize(h->stream));
   const uint64_t roots = ctl[gs::kSortCtlRoots];
@@ -1468,9 +1449,8 @@ static int components_impl(gs_handle h, int64_t* comp, uint64_t* offset, int64_t
       return rc;
   }
   if (!cur.key) cur.ids = h->x_l;
-  gs::launch_comp_csr(cur, n, h->x_v, h->x_p, h->kind == GS_KIND_SIGNED, ss.table, d_comp, d_off, d_member, d_sign,
-                      d_cap_c, h->stream);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_comp_csr(cur, n, h->x_v, h->x_p, h->kind == GS_KIND_SIGNED, ss.table, d_comp, d_off, d_member,
+                                d_sign, d_cap_c, h->stream));
   if (to_host) {
     GS_HIP(hipMemcpyAsync(comp, d_comp, roots * 8, hipMemcpyDeviceToHost, h->stream));
     GS_HIP(hipMemcpyAsync(offset, d_off, (roots + 1) * 8, hipMemcpyDeviceToHost, h->stream));
@@ -1492,8 +1472,7 @@ int gs_num_components(gs_handle h, uint64_t* n) {
   unsigned long long* d = reinterpret_cast<unsigned long long*>(h->d_scratch.get());
   unsigned long long out = 0;
   GS_HIP(hipMemsetAsync(d, 0, 8, h->stream));
-  gs::launch_comp_roots(h->x_v, h->x_l, rows, d, h->stream);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_comp_roots(h->x_v, h->x_l, rows, d, h->stream));
   GS_HIP(hipMemcpyAsync(&out, d, 8, hipMemcpyDeviceToHost, h->stream));
   GS_HIP(hipStreamSynchronize(h->stream));
   *n = out;

@@ -74,8 +74,7 @@ int change_tracking_reset(gs_summary* h, int mode) {
   if (!h->changes) return GS_OK;
   if (int rc = ensure_nxt(h)) return rc;
   if (int rc = ensure_scratch(h)) return rc;
-  if (mode >= 1) gs::launch_iota(h->nxt, h->cap + 1, h->stream);
-  GS_HIP(hipGetLastError());
+  if (mode >= 1) GS_LAUNCH(gs::launch_iota(h->nxt, h->cap + 1, h->stream));
   GS_HIP(hipMemsetAsync(scratch(h).vmark, 0, gs::kShards * 4, h->stream));
   h->chg_scan_all = mode == 2;
   return GS_OK;
@@ -111,8 +110,7 @@ int gs_set_change_tracking(gs_handle h, int on) {
   h->changes = true;
   if (int rc = change_tracking_reset(h, 1)) return rc;
   if (nv) {  // existing vertices: lists of the current forest, first emission = everything
-    gs::launch_relist(h->table(), h->nxt, h->stream);
-    GS_HIP(hipGetLastError());
+    GS_LAUNCH(gs::launch_relist(h->table(), h->nxt, h->stream));
     h->chg_scan_all = true;
   }
   return GS_OK;
@@ -141,23 +139,22 @@ int gs_take_changes_device(gs_handle h, int64_t* v, int64_t* label, uint8_t* par
     gs::launch_emit_scan(t, v, label, parity, cap, true, h->stream);
     gs::launch_iota(h->nxt, h->cap + 1, h->stream);
     gs::launch_relist(t, h->nxt, h->stream);
-    gs::launch_emit_new(t, c.vmark, v, label, parity, cap, h->vlist_ok ? nv : 0, false, h->stream);  // marks
-    GS_HIP(hipGetLastError());
+    GS_LAUNCH(gs::launch_emit_new(t, c.vmark, v, label, parity, cap, h->vlist_ok ? nv : 0, false, h->stream));  // marks
     h->chg_scan_all = false;
   } else {
     uint64_t nrec = 0;  // (< 2^32: at most the delta capacity)
     if (int rc = wait_stream(h, reinterpret_cast<const uint32_t*>(c.nrec), &nrec)) return rc;
     // phase 0 flags roots too large to walk, phase 1 walks the rest and splices
-    if (nrec) gs::launch_emit_records(t, h->nxt, c.rec, c.nrec, nrec, walk_max(), v, label, parity, cap, c.big, h->stream);
-    GS_HIP(hipGetLastError());
+    if (nrec)
+      GS_LAUNCH(gs::launch_emit_records(t, h->nxt, c.rec, c.nrec, nrec, walk_max(), v, label, parity, cap, c.big,
+                                        h->stream));
     uint64_t nbig = 0;
     if (int rc = wait_stream(h, h->ctr + gs::ctr_index(gs::CTR_BIG), &nbig)) return rc;
     if (nbig) {  // before k_emit_new clears the new bits the scan tests
       gs::launch_emit_scan(t, v, label, parity, cap, false, h->stream);
       gs::launch_clear_big(t, c.big, nbig, h->stream);
     }
-    gs::launch_emit_new(t, c.vmark, v, label, parity, cap, nv, true, h->stream);
-    GS_HIP(hipGetLastError());
+    GS_LAUNCH(gs::launch_emit_new(t, c.vmark, v, label, parity, cap, nv, true, h->stream));
   }
   uint64_t emitted = 0;  // (low word of the u64 counter: rows < 2^32)
   if (int rc = wait_stream(h, h->ctr + gs::ctr_index(gs::CTR_EMIT), &emitted)) return rc;
@@ -187,9 +184,7 @@ int gs_take_changes(gs_handle h, int64_t* v, int64_t* label, uint8_t* parity, si
   if (h->chg_ocap < nv + 1) {
     h->chg_ocap = 0;
     const uint64_t rows = std::max<uint64_t>(nv + 1, 1024) * 5 / 4;  // headroom: fewer reallocations
-    GS_HIP(h->chg_ov.alloc(rows));
-    GS_HIP(h->chg_ol.alloc(rows));
-    GS_HIP(h->chg_op.alloc(rows));
+    GS_HIP(alloc_each(rows, h->chg_ov, h->chg_ol, h->chg_op));
     h->chg_ocap = rows;
   }
   uint64_t k = 0;

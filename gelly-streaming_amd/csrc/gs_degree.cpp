@@ -84,8 +84,7 @@ int launch_chunks(gs_summary* h, gs::DegreeLaunch f, uint64_t n, bool check_cap)
     f.n = (uint32_t)c;
     f.shard0 = h->shard0;
     h->shard0 = (h->shard0 + gs::degree_blocks(f.n, variant)) & (gs::kShards - 1);
-    gs::launch_degree_fold(h->table(), f, variant, h->stream);
-    GS_HIP(hipGetLastError());
+    GS_LAUNCH(gs::launch_degree_fold(h->table(), f, variant, h->stream));
   }
   return GS_OK;
 }
@@ -131,8 +130,7 @@ int gather_rows(gs_summary* h, bool all, uint64_t* n) {
   unsigned long long* cnt = reinterpret_cast<unsigned long long*>(h->d_scratch.get());
   unsigned long long got = 0;
   GS_HIP(hipMemsetAsync(cnt, 0, 8, h->stream));
-  gs::launch_degree_export(h->table(), h->x_v, h->x_l, h->x_cap, cnt, all, h->stream);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_degree_export(h->table(), h->x_v, h->x_l, h->x_cap, cnt, all, h->stream));
   GS_HIP(hipMemcpyAsync(&got, cnt, 8, hipMemcpyDeviceToHost, h->stream));
   GS_HIP(hipStreamSynchronize(h->stream));
   if (got > h->x_cap) return fail(GS_ERR_HIP, "degree export found more rows than the table's vertex count");
@@ -148,8 +146,7 @@ int sort_rows(gs_summary* h, const int64_t* ids, uint64_t n, gs::SortSrc* cur, i
   if (int rc = sort_scratch_ensure(ss, n, h->stream)) return rc;
   std::vector<uint32_t> ctl(gs::kSortCtlWords);
   GS_HIP(hipMemsetAsync(ss.ctl, 0, gs::kSortCtlWords * 4, h->stream));
-  gs::launch_sort_digits(ids, ids, n, ss.ctl, h->stream);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_sort_digits(ids, ids, n, ss.ctl, h->stream));
   GS_HIP(hipMemcpyAsync(ctl.data(), ss.ctl, gs::kSortCtlWords * 4, hipMemcpyDeviceToHost, h->stream));
   GS_HIP(hipStreamSynchronize(h->stream));
   bool skip[gs::kSortPasses];
@@ -165,8 +162,7 @@ int export_impl(gs_summary* h, int64_t* v, int64_t* degree, size_t cap, size_t* 
   uint64_t rows = 0;
   if (int rc = gather_rows(h, false, &rows)) return rc;
   *n = rows;
-  if (cap < rows)
-    return fail(GS_ERR_TRUNCATED, "output capacity " + std::to_string(cap) + " < " + std::to_string(rows));
+  if (cap < rows) return truncated(cap, rows);
   if (rows == 0) return GS_OK;
   if (!v || !degree) return fail(GS_ERR_INVALID, "null arrays");
   const int64_t *rv = h->x_v, *rd = h->x_l;
@@ -177,14 +173,13 @@ int export_impl(gs_summary* h, int64_t* v, int64_t* degree, size_t cap, size_t* 
     if (int rc = sort_rows(h, h->x_v, rows, &cur, &side)) return rc;
     if (to_host) {
       if (int rc = comp_staging(h, rows, rows)) return rc;
-      gs::launch_degree_gather(cur.pay, h->x_v, h->x_l, rows, h->co_member, h->co_comp, h->stream);
+      GS_LAUNCH(gs::launch_degree_gather(cur.pay, h->x_v, h->x_l, rows, h->co_member, h->co_comp, h->stream));
       rv = h->co_member;
       rd = h->co_comp;
     } else {
-      gs::launch_degree_gather(cur.pay, h->x_v, h->x_l, rows, v, degree, h->stream);
+      GS_LAUNCH(gs::launch_degree_gather(cur.pay, h->x_v, h->x_l, rows, v, degree, h->stream));
       rv = rd = nullptr;
     }
-    GS_HIP(hipGetLastError());
   }
   if (rv) {
     GS_HIP(hipMemcpyAsync(v, rv, rows * 8, kind, h->stream));
@@ -208,30 +203,26 @@ int distribution_impl(gs_summary* h, int64_t* degree, int64_t* count, size_t cap
   if (cur.key) {
     unsigned long long* heads = reinterpret_cast<unsigned long long*>(h->d_scratch.get()) + 1;
     GS_HIP(hipMemsetAsync(heads, 0, 8, h->stream));
-    gs::launch_degree_heads(cur.key, rows, heads, h->stream);
-    GS_HIP(hipGetLastError());
+    GS_LAUNCH(gs::launch_degree_heads(cur.key, rows, heads, h->stream));
     GS_HIP(hipMemcpyAsync(&nd, heads, 8, hipMemcpyDeviceToHost, h->stream));
     GS_HIP(hipStreamSynchronize(h->stream));
   }
   *n = nd;
-  if (cap < nd) return fail(GS_ERR_TRUNCATED, "output capacity " + std::to_string(cap) + " < " + std::to_string(nd));
+  if (cap < nd) return truncated(cap, nd);
   if (!degree || !count) return fail(GS_ERR_INVALID, "null arrays");
   if (int rc = comp_staging(h, rows, rows)) return rc;
   if (!cur.key) cur.ids = h->x_l;
-  gs::launch_comp_csr(cur, rows, h->x_l, nullptr, false, h->sort.table, h->co_comp, h->co_off, h->co_member, nullptr,
-                      h->co_ccap, h->stream);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_comp_csr(cur, rows, h->x_l, nullptr, false, h->sort.table, h->co_comp, h->co_off, h->co_member,
+                                nullptr, h->co_ccap, h->stream));
   if (to_host) {
     // (the CSR's member column and the sort's free ping-pong buffer are dead by now)
     int64_t* sd = h->co_member;
     int64_t* sc = reinterpret_cast<int64_t*>(h->sort.key[side].get());
-    gs::launch_degree_runs(h->co_comp, h->co_off, nd, sd, sc, h->stream);
-    GS_HIP(hipGetLastError());
+    GS_LAUNCH(gs::launch_degree_runs(h->co_comp, h->co_off, nd, sd, sc, h->stream));
     GS_HIP(hipMemcpyAsync(degree, sd, nd * 8, hipMemcpyDeviceToHost, h->stream));
     GS_HIP(hipMemcpyAsync(count, sc, nd * 8, hipMemcpyDeviceToHost, h->stream));
   } else {
-    gs::launch_degree_runs(h->co_comp, h->co_off, nd, degree, count, h->stream);
-    GS_HIP(hipGetLastError());
+    GS_LAUNCH(gs::launch_degree_runs(h->co_comp, h->co_off, nd, degree, count, h->stream));
   }
   GS_HIP(hipStreamSynchronize(h->stream));
   return GS_OK;
@@ -382,8 +373,7 @@ int gs_degree_find_device(gs_handle h, const int64_t* v, size_t n, int64_t* degr
   if (n && (!v || !degree)) return fail(GS_ERR_INVALID, "null arrays");
   DeviceGuard g(h->device);
   if (int rc = join_lanes(h)) return rc;
-  gs::launch_degree_find(h->table(), v, n, degree, found, h->stream);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_degree_find(h->table(), v, n, degree, found, h->stream));
   return GS_OK;
 }
 

@@ -15,17 +15,15 @@
 
 #include "gs_distinct.hpp"
 #include "gs_internal.hpp"
+#include "gs_vtable.hpp"
 
 using namespace gsi;
 
-struct gs_distinct_s : StreamOwner {
+struct gs_distinct_s : StreamOwner, VertexTable {  // (the vertex table and the vertex list: vtab, vid, vcap)
   int mode = GS_DISTINCT_DIRECTED;
   DevBuf<unsigned long long> ctl;  // gs::DistCtl words
-  // the two tables and the vertex list
-  DevBuf<gs::DistVSlot> vtab;  // [vcap + 1]
-  DevBuf<gs::DistESlot> etab;  // [ecap]
-  DevBuf<int64_t> vid;         // [dist_vid_cap(vcap)] vertices in rank order
-  uint64_t vcap = 0, ecap = 0;
+  DevBuf<gs::DistESlot> etab;      // [ecap] the edge table
+  uint64_t ecap = 0;
   // the last fold's scratch and emissions, sized for n_cap edges
   uint64_t n_cap = 0;
   DevBuf<uint32_t> vslot;       // [2 n] slot of every entry
@@ -55,7 +53,6 @@ struct gs_distinct_s : StreamOwner {
   uint64_t phase_us[5] = {0, 0, 0, 0, 0};  // of the last profiled fold (gs_testing_distinct_phases)
   uint64_t last_atomics = 0;
 
-  gs::DistVTable vtable() const { return gs::dist_vtable_of(vtab, vcap); }
   gs::DistETable etable() const { return etable_of(etab, ecap); }
   static gs::DistETable etable_of(gs::DistESlot* tab, uint64_t cap) {
     gs::DistETable t;
@@ -69,31 +66,12 @@ struct gs_distinct_s : StreamOwner {
 
 namespace {
 
-int check_distinct(gs_distinct d) {
-  if (!d) return fail(GS_ERR_INVALID, "null distinct handle");
-  return GS_OK;
-}
+constexpr const char* kWhat = "distinct";  // check_handle: "null distinct handle"
 
-// A vertex table of `cap` slots (and its vertex list) in place of the current one, whose
-// vertices move over; the first table of a handle when there is none.
 int grow_vertices(gs_distinct_s* d, uint64_t cap) {
-  DevBuf<gs::DistVSlot> tab;
-  DevBuf<int64_t> vid;
-  GS_HIP(tab.alloc(cap + 1));
-  GS_HIP(vid.alloc(gs::dist_vid_cap(cap)));
-  const gs::DistVTable to = gs::dist_vtable_of(tab, cap);
-  gs::launch_dist_init(to, d->stream);
-  GS_HIP(hipGetLastError());
-  if (d->vtab) {
-    gs::launch_dist_rebuild(d->vtable(), to, d->ctl, d->stream);
-    GS_HIP(hipGetLastError());
-    if (d->nv) GS_HIP(hipMemcpyAsync(vid, d->vid, d->nv * 8, hipMemcpyDeviceToDevice, d->stream));
-    GS_HIP(hipStreamSynchronize(d->stream));  // before the old arrays are freed
-    ++d->v_rebuilds;
-  }
-  d->vtab.swap(tab);
-  d->vid.swap(vid);
-  d->vcap = cap;
+  const bool rebuild = d->vtab;
+  if (int rc = d->grow(cap, d->nv, d->ctl, d->stream, [](bool) { return GS_OK; })) return rc;
+  if (rebuild) ++d->v_rebuilds;
   return GS_OK;
 }
 
@@ -101,11 +79,9 @@ int grow_edges(gs_distinct_s* d, uint64_t cap) {
   DevBuf<gs::DistESlot> tab;
   GS_HIP(tab.alloc(cap));
   const gs::DistETable to = gs_distinct_s::etable_of(tab, cap);
-  gs::launch_dist_init(to, d->stream);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_dist_init(to, d->stream));
   if (d->etab) {
-    gs::launch_dist_rebuild(d->etable(), to, d->ctl, d->stream);
-    GS_HIP(hipGetLastError());
+    GS_LAUNCH(gs::launch_dist_rebuild(d->etable(), to, d->ctl, d->stream));
     GS_HIP(hipStreamSynchronize(d->stream));
     ++d->e_rebuilds;
   }
@@ -115,30 +91,21 @@ int grow_edges(gs_distinct_s* d, uint64_t cap) {
 }
 
 int ensure_scratch(gs_distinct_s* d, uint64_t n) {
-  if (d->n_cap >= n) return GS_OK;
-  GS_HIP(hipStreamSynchronize(d->stream));
-  d->n_cap = 0;
-  const uint64_t c = std::min<uint64_t>(gs::kDistMaxFold, n + n / 4);
-  const uint64_t tiles = gs::dist_tiles(2 * c, gs::DISTINCT_TILE);
-  GS_HIP(d->vslot.alloc(2 * c));
-  GS_HIP(d->eslot.alloc(c));
-  GS_HIP(d->flags.alloc(tiles * gs::DISTINCT_TILE));
-  GS_HIP(d->tbase.alloc(tiles + 1));
-  GS_HIP(d->newv_entry.alloc(2 * c));
-  GS_HIP(d->newe_index.alloc(c));
-  d->n_cap = c;
+  const auto alloc_scratch = [&](uint64_t c) {
+    const uint64_t tiles = gs::dist_tiles(2 * c, gs::DISTINCT_TILE);
+    hipError_t e = alloc_each(2 * c, d->vslot, d->newv_entry);
+    if (e == hipSuccess) e = alloc_each(c, d->eslot, d->newe_index);
+    if (e == hipSuccess) e = d->flags.alloc(tiles * gs::DISTINCT_TILE);
+    if (e == hipSuccess) e = d->tbase.alloc(tiles + 1);
+    return e;
+  };
+  GS_HIP(grow_group(d->stream, d->n_cap, n, std::min<uint64_t>(gs::kDistMaxFold, n + n / 4), alloc_scratch));
   return GS_OK;
 }
 
 int ensure_staging(gs_distinct_s* d, uint64_t rows) {
-  if (d->o_cap >= rows) return GS_OK;
-  GS_HIP(hipStreamSynchronize(d->stream));
-  d->o_cap = 0;
-  const uint64_t c = rows + rows / 4;
-  GS_HIP(d->o_a.alloc(c));
-  GS_HIP(d->o_b.alloc(c));
-  GS_HIP(d->o_c.alloc(c));
-  d->o_cap = c;
+  GS_HIP(grow_group(d->stream, d->o_cap, rows, rows + rows / 4,
+                    [&](uint64_t c) { return alloc_each(c, d->o_a, d->o_b, d->o_c); }));
   return GS_OK;
 }
 
@@ -148,7 +115,7 @@ void forget_last(gs_distinct_s* d) {
 }
 
 int fold_guard(gs_distinct d, const void* src, const void* dst, size_t n) {
-  if (int rc = check_distinct(d)) return rc;
+  if (int rc = check_handle(d, kWhat)) return rc;
   if (n && (!src || !dst)) return fail(GS_ERR_INVALID, "null edge arrays");
   if ((uint64_t)n > gs::kDistMaxFold)
     return fail(GS_ERR_CAPACITY, "distinct fold: " + std::to_string(n) + " edges pass 2^31 - 2 per fold");
@@ -176,13 +143,11 @@ int fold_impl(gs_distinct_s* d, const int64_t* src, const int64_t* dst, uint64_t
   const gs::DistETable et = d->etable();
   PhaseTimer timer(d->stream, testing_value(GS_TESTING_DISTINCT_PROFILE, 0) == 1, d->phase_us, 5);
   timer.mark(0);
-  gs::launch_dist_vertices(src, dst, n, stride, vt, d->vslot, d->flags, d->tbase, d->nv, d->vid,
-                           gs::dist_vid_cap(d->vcap), d->newv_entry, d->ctl, d->stream, timer.event(1));
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_dist_vertices(src, dst, n, stride, vt, d->vslot, d->flags, d->tbase, d->nv, d->vid,
+                                     gs::dist_vid_cap(d->vcap), d->newv_entry, d->ctl, d->stream, timer.event(1)));
   timer.mark(2);
-  gs::launch_dist_edges(n, d->folded, d->mode, vt, d->vslot, et, d->eslot, d->flags, d->tbase, d->newe_index, d->ctl,
-                        d->stream, timer.event(3));
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_dist_edges(n, d->folded, d->mode, vt, d->vslot, et, d->eslot, d->flags, d->tbase, d->newe_index,
+                                  d->ctl, d->stream, timer.event(3)));
   timer.mark(4);
   // the fold's one host synchronisation: new vertices, new edges, overflow, longest probe
   unsigned long long w[6] = {0, 0, 0, 0, 0, 0};
@@ -204,11 +169,10 @@ int fold_impl(gs_distinct_s* d, const int64_t* src, const int64_t* dst, uint64_t
   return GS_OK;
 }
 
-int truncated(size_t cap, uint64_t need) {
-  return fail(GS_ERR_TRUNCATED, "output capacity " + std::to_string(cap) + " < " + std::to_string(need));
-}
-
 int new_edges_impl(gs_distinct_s* d, uint32_t* index, int64_t* src, int64_t* dst, size_t cap, size_t* n, bool to_host) {
+  if (int rc = check_handle(d, kWhat)) return rc;
+  if (!n) return fail(GS_ERR_INVALID, "n is null");
+  DeviceGuard g(d->device);
   const uint64_t ne = d->last_ne;
   *n = ne;
   if (cap < ne) return truncated(cap, ne);
@@ -221,8 +185,8 @@ int new_edges_impl(gs_distinct_s* d, uint32_t* index, int64_t* src, int64_t* dst
     dd = dst ? d->o_b.get() : nullptr;
   }
   if (ds || dd) {
-    gs::launch_dist_new_edges(d->newe_index, ne, d->eslot, d->last_n, d->etable(), d->vid, d->nv, ds, dd, d->stream);
-    GS_HIP(hipGetLastError());
+    GS_LAUNCH(gs::launch_dist_new_edges(d->newe_index, ne, d->eslot, d->last_n, d->etable(), d->vid, d->nv, ds, dd,
+                                        d->stream));
   }
   if (index) GS_HIP(hipMemcpyAsync(index, d->newe_index, ne * 4, kind, d->stream));
   if (to_host) {
@@ -234,6 +198,9 @@ int new_edges_impl(gs_distinct_s* d, uint32_t* index, int64_t* src, int64_t* dst
 }
 
 int new_vertices_impl(gs_distinct_s* d, int64_t* v, uint32_t* entry, size_t cap, size_t* n, bool to_host) {
+  if (int rc = check_handle(d, kWhat)) return rc;
+  if (!n) return fail(GS_ERR_INVALID, "n is null");
+  DeviceGuard g(d->device);
   const uint64_t k = d->last_nv;
   *n = k;
   if (cap < k) return truncated(cap, k);
@@ -247,6 +214,9 @@ int new_vertices_impl(gs_distinct_s* d, int64_t* v, uint32_t* entry, size_t cap,
 }
 
 int vertices_impl(gs_distinct_s* d, int64_t* v, size_t cap, size_t* n, bool to_host) {
+  if (int rc = check_handle(d, kWhat)) return rc;
+  if (!n) return fail(GS_ERR_INVALID, "n is null");
+  DeviceGuard g(d->device);
   *n = d->nv;
   if (cap < d->nv) return truncated(cap, d->nv);
   if (d->nv == 0) return GS_OK;
@@ -257,18 +227,15 @@ int vertices_impl(gs_distinct_s* d, int64_t* v, size_t cap, size_t* n, bool to_h
 }
 
 int edges_impl(gs_distinct_s* d, int64_t* src, int64_t* dst, uint64_t* first, size_t cap, size_t* n, bool to_host) {
+  if (int rc = check_handle(d, kWhat)) return rc;
+  if (!n) return fail(GS_ERR_INVALID, "n is null");
+  DeviceGuard g(d->device);
   const uint64_t ne = d->ne;
   *n = ne;
   if (cap < ne) return truncated(cap, ne);
   if (ne == 0) return GS_OK;
-  if (d->x_cap < ne) {
-    GS_HIP(hipStreamSynchronize(d->stream));
-    d->x_cap = 0;
-    const uint64_t c = ne + ne / 4;
-    GS_HIP(d->x_stamp.alloc(c));
-    GS_HIP(d->x_key.alloc(c));
-    d->x_cap = c;
-  }
+  GS_HIP(grow_group(d->stream, d->x_cap, ne, ne + ne / 4,
+                    [&](uint64_t c) { return alloc_each(c, d->x_stamp, d->x_key); }));
   if (int rc = sort_scratch_ensure(d->sort, ne, d->stream)) return rc;
   int64_t *ds = src, *dd = dst;
   unsigned long long* df = reinterpret_cast<unsigned long long*>(first);
@@ -280,12 +247,11 @@ int edges_impl(gs_distinct_s* d, int64_t* src, int64_t* dst, uint64_t* first, si
   }
   // scan the table, compact, sort by stamp, decode through the vertex list
   GS_HIP(hipMemsetAsync(d->ctl + gs::DIST_EXPORT, 0, 8, d->stream));
-  gs::launch_dist_export(d->etable(), d->x_stamp, d->x_key, ne, d->ctl, d->stream);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_dist_export(d->etable(), d->x_stamp, d->x_key, ne, d->ctl, d->stream));
   uint32_t* const sctl = d->sort.ctl;
   GS_HIP(hipMemsetAsync(sctl, 0, gs::kSortCtlWords * 4, d->stream));
-  gs::launch_sort_digits_one(d->x_stamp, ne, sctl, d->stream);  // rows 0..7: the digit histograms of one key column
-  GS_HIP(hipGetLastError());
+  // rows 0..7: the digit histograms of one key column
+  GS_LAUNCH(gs::launch_sort_digits_one(d->x_stamp, ne, sctl, d->stream));
   // every stamp is below 2 * folded: the digits above its bits are equal in all keys
   bool skip[gs::kSortPasses];
   for (int p = 0; p < (int)gs::kSortPasses; ++p) skip[p] = p > 0 && 8 * p < 64 && ((2 * d->folded) >> (8 * p)) == 0;
@@ -293,8 +259,7 @@ int edges_impl(gs_distinct_s* d, int64_t* src, int64_t* dst, uint64_t* first, si
   int side = 0;
   if (int rc = sort_run(d->sort, d->x_stamp, ne, sctl, skip, &cur, &side, d->stream)) return rc;
   if (!cur.key || !cur.pay) return fail(GS_ERR_HIP, "distinct edges: the sort ran no pass");
-  gs::launch_dist_decode(cur.key, cur.pay, d->x_key, ne, d->vid, d->nv, ds, dd, df, d->stream);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_dist_decode(cur.key, cur.pay, d->x_key, ne, d->vid, d->nv, ds, dd, df, d->stream));
   if (to_host) {
     if (src) GS_HIP(hipMemcpyAsync(src, ds, ne * 8, hipMemcpyDeviceToHost, d->stream));
     if (dst) GS_HIP(hipMemcpyAsync(dst, dd, ne * 8, hipMemcpyDeviceToHost, d->stream));
@@ -328,12 +293,10 @@ int gs_distinct_create(gs_distinct* out, int device, int mode, uint64_t vertex_h
 }
 
 int gs_distinct_reset(gs_distinct d) {
-  if (int rc = check_distinct(d)) return rc;
+  if (int rc = check_handle(d, kWhat)) return rc;
   DeviceGuard g(d->device);
-  gs::launch_dist_init(d->vtable(), d->stream);
-  GS_HIP(hipGetLastError());
-  gs::launch_dist_init(d->etable(), d->stream);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_dist_init(d->vtable(), d->stream));
+  GS_LAUNCH(gs::launch_dist_init(d->etable(), d->stream));
   d->nv = d->ne = d->folded = 0;
   forget_last(d);
   return GS_OK;
@@ -357,14 +320,7 @@ int gs_distinct_fold(gs_distinct d, const int64_t* src, const int64_t* dst, size
     return GS_OK;
   }
   DeviceGuard g(d->device);
-  if (d->h_cap < n) {
-    GS_HIP(hipStreamSynchronize(d->stream));
-    d->h_cap = 0;
-    const uint64_t c = n + n / 4;
-    GS_HIP(d->hsrc.alloc(c));
-    GS_HIP(d->hdst.alloc(c));
-    d->h_cap = c;
-  }
+  GS_HIP(grow_group(d->stream, d->h_cap, n, n + n / 4, [&](uint64_t c) { return alloc_each(c, d->hsrc, d->hdst); }));
   GS_HIP(hipMemcpyAsync(d->hsrc, src, n * 8, hipMemcpyHostToDevice, d->stream));
   GS_HIP(hipMemcpyAsync(d->hdst, dst, n * 8, hipMemcpyHostToDevice, d->stream));
   // (fold_impl waits for the stream before it returns: the host arrays are free then)
@@ -373,7 +329,7 @@ int gs_distinct_fold(gs_distinct d, const int64_t* src, const int64_t* dst, size
 
 int gs_distinct_size(gs_distinct d, uint64_t* vertices, uint64_t* edges, uint64_t* folded, uint64_t* new_vertices,
                      uint64_t* new_edges) {
-  if (int rc = check_distinct(d)) return rc;
+  if (int rc = check_handle(d, kWhat)) return rc;
   if (!vertices || !edges || !folded || !new_vertices || !new_edges)
     return fail(GS_ERR_INVALID, "null count pointers");
   *vertices = d->nv;
@@ -385,104 +341,63 @@ int gs_distinct_size(gs_distinct d, uint64_t* vertices, uint64_t* edges, uint64_
 }
 
 int gs_distinct_new_edges_device(gs_distinct d, uint32_t* index, int64_t* src, int64_t* dst, size_t cap, size_t* n) {
-  if (int rc = check_distinct(d)) return rc;
-  if (!n) return fail(GS_ERR_INVALID, "n is null");
-  DeviceGuard g(d->device);
   return new_edges_impl(d, index, src, dst, cap, n, false);
 }
 
 int gs_distinct_new_edges(gs_distinct d, uint32_t* index, int64_t* src, int64_t* dst, size_t cap, size_t* n) {
-  if (int rc = check_distinct(d)) return rc;
-  if (!n) return fail(GS_ERR_INVALID, "n is null");
-  DeviceGuard g(d->device);
   return new_edges_impl(d, index, src, dst, cap, n, true);
 }
 
 int gs_distinct_new_vertices_device(gs_distinct d, int64_t* v, uint32_t* entry, size_t cap, size_t* n) {
-  if (int rc = check_distinct(d)) return rc;
-  if (!n) return fail(GS_ERR_INVALID, "n is null");
-  DeviceGuard g(d->device);
   return new_vertices_impl(d, v, entry, cap, n, false);
 }
 
 int gs_distinct_new_vertices(gs_distinct d, int64_t* v, uint32_t* entry, size_t cap, size_t* n) {
-  if (int rc = check_distinct(d)) return rc;
-  if (!n) return fail(GS_ERR_INVALID, "n is null");
-  DeviceGuard g(d->device);
   return new_vertices_impl(d, v, entry, cap, n, true);
 }
 
 int gs_distinct_vertices_device(gs_distinct d, int64_t* v, size_t cap, size_t* n) {
-  if (int rc = check_distinct(d)) return rc;
-  if (!n) return fail(GS_ERR_INVALID, "n is null");
-  DeviceGuard g(d->device);
   return vertices_impl(d, v, cap, n, false);
 }
 
 int gs_distinct_vertices(gs_distinct d, int64_t* v, size_t cap, size_t* n) {
-  if (int rc = check_distinct(d)) return rc;
-  if (!n) return fail(GS_ERR_INVALID, "n is null");
-  DeviceGuard g(d->device);
   return vertices_impl(d, v, cap, n, true);
 }
 
 int gs_distinct_edges_device(gs_distinct d, int64_t* src, int64_t* dst, uint64_t* first, size_t cap, size_t* n) {
-  if (int rc = check_distinct(d)) return rc;
-  if (!n) return fail(GS_ERR_INVALID, "n is null");
-  DeviceGuard g(d->device);
   return edges_impl(d, src, dst, first, cap, n, false);
 }
 
 int gs_distinct_edges(gs_distinct d, int64_t* src, int64_t* dst, uint64_t* first, size_t cap, size_t* n) {
-  if (int rc = check_distinct(d)) return rc;
-  if (!n) return fail(GS_ERR_INVALID, "n is null");
-  DeviceGuard g(d->device);
   return edges_impl(d, src, dst, first, cap, n, true);
 }
 
 int gs_distinct_rank_device(gs_distinct d, const int64_t* v, size_t n, int64_t* rank, uint8_t* found) {
-  if (int rc = check_distinct(d)) return rc;
+  if (int rc = check_handle(d, kWhat)) return rc;
   if (n == 0) return GS_OK;
   if (!v || !rank) return fail(GS_ERR_INVALID, "null arrays");
   DeviceGuard g(d->device);
-  gs::launch_dist_rank(d->vtable(), v, n, rank, found, d->stream);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_dist_rank(d->vtable(), v, n, rank, found, d->stream));
   return GS_OK;
 }
 
 int gs_distinct_contains_device(gs_distinct d, const int64_t* src, const int64_t* dst, size_t n, uint8_t* found) {
-  if (int rc = check_distinct(d)) return rc;
+  if (int rc = check_handle(d, kWhat)) return rc;
   if (n == 0) return GS_OK;
   if (!src || !dst || !found) return fail(GS_ERR_INVALID, "null arrays");
   DeviceGuard g(d->device);
-  gs::launch_dist_contains(d->vtable(), d->etable(), d->mode, src, dst, n, found, d->stream);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_dist_contains(d->vtable(), d->etable(), d->mode, src, dst, n, found, d->stream));
   return GS_OK;
 }
 
-int gs_distinct_sync(gs_distinct d) {
-  if (int rc = check_distinct(d)) return rc;
-  DeviceGuard g(d->device);
-  GS_HIP(hipStreamSynchronize(d->stream));
-  return GS_OK;
-}
-
-int gs_distinct_get_stream(gs_distinct d, void** stream) {
-  if (int rc = check_distinct(d)) return rc;
-  if (!stream) return fail(GS_ERR_INVALID, "stream is null");
-  *stream = d->stream;
-  return GS_OK;
-}
-
-int gs_distinct_wait_stream(gs_distinct d, void* stream) {
-  if (int rc = check_distinct(d)) return rc;
-  return d->wait_stream(stream);
-}
+int gs_distinct_sync(gs_distinct d) { return owner_sync(d, kWhat); }
+int gs_distinct_get_stream(gs_distinct d, void** stream) { return owner_get_stream(d, kWhat, stream); }
+int gs_distinct_wait_stream(gs_distinct d, void* stream) { return owner_wait_stream(d, kWhat, stream); }
 
 // gs_testing.h: six words, all host-known (no device call)
 int gs_testing_distinct_stats(void* handle, uint64_t* out) {
   gs_distinct d = static_cast<gs_distinct>(handle);
-  if (int rc = check_distinct(d)) return rc;
+  if (int rc = check_handle(d, kWhat)) return rc;
   if (!out) return fail(GS_ERR_INVALID, "out is null");
   out[0] = d->vcap;
   out[1] = d->ecap;
@@ -496,7 +411,7 @@ int gs_testing_distinct_stats(void* handle, uint64_t* out) {
 // gs_testing.h: seven words of the last profiled fold, all host-known
 int gs_testing_distinct_phases(void* handle, uint64_t* out) {
   gs_distinct d = static_cast<gs_distinct>(handle);
-  if (int rc = check_distinct(d)) return rc;
+  if (int rc = check_handle(d, kWhat)) return rc;
   if (!out) return fail(GS_ERR_INVALID, "out is null");
   for (int i = 0; i < 5; ++i) out[i] = d->phase_us[i];
   out[5] = d->last_atomics;

@@ -523,8 +523,8 @@ int gs_group_fold_device(gs_group_t g, const int64_t* src, const int64_t* dst, s
   GS_HIP(hipEventRecord(g->staged[d], g->xc));
   const int r = g->api.all_gather(g->cnt_send(k), g->cnt_recv(k), 1, kNcclInt64, g->comm_c, g->xc);
   if (r != 0) return rccl_fail(&g->api, "ncclAllGather(counts)", r);
-  gs::launch_headers(g->cnt_recv(k), g->nranks, g->hdr_host.dev() + (size_t)k * (g->nranks + 1), (long long)b, g->xc);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_headers(g->cnt_recv(k), g->nranks, g->hdr_host.dev() + (size_t)k * (g->nranks + 1), (long long)b,
+                               g->xc));
   ph_end(g, 2, pc, g->xc);
   GS_HIP(hipEventRecord(g->counted[k], g->xc));
   ht.lap(nullptr);
@@ -807,8 +807,7 @@ int part_read(gs_group* g, size_t first, size_t n) {
 
 int part_init_tables(gs_group* g) {
   hipStream_t st = g->h->stream;
-  gs::launch_part_init(g->ot.tab, (uint64_t)g->ot.cap + 1, st);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_part_init(g->ot.tab, (uint64_t)g->ot.cap + 1, st));
   GS_HIP(hipMemsetAsync(g->mark, 0, gs::kShards * 4, st));
   GS_HIP(hipMemsetAsync(g->pflags, 0, 16, st));
   g->win_edges = 0;
@@ -911,8 +910,8 @@ int gs_group_part_combine(gs_group_t g) {
   unsigned long long* words = allcnt + (size_t)N * N;
   // 1. what is new since the previous combine
   hipEvent_t p0 = ph_begin(g, st);
-  gs::launch_part_snap(h->table(), g->mark, g->snap, full ? 1 : 0, D.dctr, h->drec ? D.shard_cap : 0u, g->pdev, st);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_part_snap(h->table(), g->mark, g->snap, full ? 1 : 0, D.dctr, h->drec ? D.shard_cap : 0u,
+                                 g->pdev, st));
   if (int rc = part_read(g, 0, 3)) return rc;
   if (g->phost[2]) return fail(GS_ERR_CAPACITY, "vertex list overflow: the partitioned combine needs the list");
   const uint64_t total = g->phost[0], nrec = (g->window && h->track) ? g->phost[1] : 0;
@@ -922,11 +921,10 @@ int gs_group_part_combine(gs_group_t g) {
   if (int rc = ensure_buf(g->pairs, (nrec + 1) * W, st)) return rc;
   GS_HIP(hipMemsetAsync(g->pdev + 3, 0, 8, st));
   // 2. export the new vertices (marks their roots), then the marked roots hooked away
-  gs::launch_part_export(sign, h->table(), g->mark, g->snap, full ? 1 : 0, total, g->stage, W, g->bcnt, N, st);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_part_export(sign, h->table(), g->mark, g->snap, full ? 1 : 0, total, g->stage, W, g->bcnt, N,
+                                   st));
   if (nrec) {
-    gs::launch_part_records(sign, h->table(), D, g->pairs, W, g->pdev + 3, g->pairs.size() / W, st);
-    GS_HIP(hipGetLastError());
+    GS_LAUNCH(gs::launch_part_records(sign, h->table(), D, g->pairs, W, g->pdev + 3, g->pairs.size() / W, st));
   }
   if (h->track) {  // the window's records are consumed
     GS_HIP(hipMemsetAsync(h->ctr + gs::ctr_index(gs::CTR_DELTA), 0, (size_t)gs::kShards * gs::kCtrStride * 4, st));
@@ -941,8 +939,7 @@ int gs_group_part_combine(gs_group_t g) {
     GS_HIP(hipMemsetAsync(sendcnt, 0, (size_t)N * 8, st));
   }
   if (int rc = ensure_buf(g->sendbuf, std::max<uint64_t>(total, 1) * W, st)) return rc;
-  gs::launch_part_scatter(g->stage, total, W, g->bcnt, nblocks, sendcnt, N, g->sendbuf, st);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_part_scatter(g->stage, total, W, g->bcnt, nblocks, sendcnt, N, g->sendbuf, st));
   GS_HIP(hipMemcpyAsync(g->mark, g->snap, gs::kShards * 4, hipMemcpyDeviceToDevice, st));
   g->cap_seen = h->cap;
   ph_end(g, 2, p1, st);
@@ -981,12 +978,10 @@ int gs_group_part_combine(gs_group_t g) {
     ps.tab = g->pset;
     ps.mask = (uint32_t)(slots - 1);
   }
-  gs::launch_part_owner(sign, g->ot, ps, g->recvbuf, total_recv, W, g->pairs, g->pdev + 3, g->pairs.size() / W,
-                        g->pflags + 1, st);
-  GS_HIP(hipGetLastError());
-  gs::launch_part_count_word(g->pdev + 3, sign ? h->ctr + gs::ctr_index(gs::CTR_FAIL) : nullptr,
-                             sign ? g->pflags + 1 : nullptr, g->pdev + 4, st);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_part_owner(sign, g->ot, ps, g->recvbuf, total_recv, W, g->pairs, g->pdev + 3,
+                                  g->pairs.size() / W, g->pflags + 1, st));
+  GS_LAUNCH(gs::launch_part_count_word(g->pdev + 3, sign ? h->ctr + gs::ctr_index(gs::CTR_FAIL) : nullptr,
+                                       sign ? g->pflags + 1 : nullptr, g->pdev + 4, st));
   // 6. every rank's pairs into every rank's label forest
   ph_end(g, 4, p3, st);
   hipEvent_t p4 = ph_begin(g, st);
@@ -1048,8 +1043,7 @@ int gs_group_part_labels_device(gs_group_t g, int64_t* v, int64_t* label, uint8_
   GS_HIP(hipStreamWaitEvent(st, g->pev, 0));
   h->xwait = true;
   GS_HIP(hipMemsetAsync(g->pdev + 5, 0, 8, st));
-  gs::launch_part_labels(g->ot, g->G->table(), v, label, parity, cap, g->pdev + 5, st);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_part_labels(g->ot, g->G->table(), v, label, parity, cap, g->pdev + 5, st));
   if (int rc = part_read(g, 5, 1)) return rc;
   *n = (size_t)g->phost[5];
   if (*n > cap) return fail(GS_ERR_TRUNCATED, "output too small for the owned vertices");

@@ -1,10 +1,13 @@
 // gs_internal.hpp -- the summary handle and the internal entry points shared by
 // gs_capi.cpp (include/gs_summary.h), gs_group.cpp (include/gs_group.h),
-// gs_changes.cpp (per-window change emission), gs_degree.cpp, gs_triangle.cpp and gs_sort.cpp;
-// the phase timer and the stream owner every handle derives from (the summary here, and
-// gs_slice.cpp, gs_triangle.cpp, gs_distinct.cpp).
+// gs_changes.cpp (per-window change emission), gs_degree.cpp and gs_sort.cpp; and what every
+// handle type is made from -- the summary here, and the stand-alone summaries of gs_slice.cpp,
+// gs_triangle.cpp, gs_distinct.cpp, gs_spanner.cpp and gs_matching.cpp: the error macros
+// (GS_HIP, GS_LAUNCH), the phase timer, the stream owner each handle derives from with the entry
+// points all of them have (sync, get_stream, wait_stream, the null check, the truncation error).
 // Every device array a handle owns is a DevBuf (gs_devbuf.hpp), every event, stream and pinned
-// host block an Event, Stream or HostBuf (gs_own.hpp): deleting the handle releases them.
+// host block an Event, Stream or HostBuf (gs_own.hpp): deleting the handle releases them. Groups
+// of DevBufs that share a capacity grow through grow_group (gs_grow.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -12,6 +15,7 @@
 #include <vector>
 
 #include "gs_devbuf.hpp"
+#include "gs_grow.hpp"
 #include "gs_ingest.hpp"
 #include "gs_kernels.hpp"
 #include "gs_own.hpp"
@@ -35,6 +39,23 @@ uint64_t create_bytes(uint64_t cap);
     if (e_ != hipSuccess)                                                                             \
       return ::gsi::fail(GS_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_));              \
   } while (0)
+
+// A kernel launch (a gs::launch_* call) and the check of its launch error: a launch without the
+// check would hand its error to some later, unrelated call.
+#define GS_LAUNCH(...)            \
+  do {                            \
+    __VA_ARGS__;                  \
+    GS_HIP(hipGetLastError());    \
+  } while (0)
+
+// The two errors every handle type reports in the same words: a null handle ("null matching
+// handle") and an output array too small for its rows.
+inline int check_handle(const void* h, const char* what) {
+  return h ? GS_OK : fail(GS_ERR_INVALID, std::string("null ") + what + " handle");
+}
+inline int truncated(size_t cap, uint64_t need) {
+  return fail(GS_ERR_TRUNCATED, "output capacity " + std::to_string(cap) + " < " + std::to_string(need));
+}
 
 constexpr uint32_t kMaxChunk = 1u << 22;     // edges per k_fold launch
 constexpr uint32_t kStageChunk = 1u << 20;   // edges per pinned staging buffer
@@ -154,7 +175,32 @@ struct StreamOwner {
     GS_HIP(hipStreamWaitEvent(stream, ext_ev, 0));
     return GS_OK;
   }
+  int sync() {
+    DeviceGuard g(device);
+    GS_HIP(hipStreamSynchronize(stream));
+    return GS_OK;
+  }
+  int get_stream(void** out) {
+    if (!out) return fail(GS_ERR_INVALID, "stream is null");
+    *out = stream;
+    return GS_OK;
+  }
 };
+
+// The bodies of a handle type's *_sync, *_get_stream and *_wait_stream (h may be null; `what`
+// names the type in the message).
+inline int owner_sync(StreamOwner* h, const char* what) {
+  if (int rc = check_handle(h, what)) return rc;
+  return h->sync();
+}
+inline int owner_get_stream(StreamOwner* h, const char* what, void** out) {
+  if (int rc = check_handle(h, what)) return rc;
+  return h->get_stream(out);
+}
+inline int owner_wait_stream(StreamOwner* h, const char* what, void* producer) {
+  if (int rc = check_handle(h, what)) return rc;
+  return h->wait_stream(producer);
+}
 
 inline int check_device_index(int device) {
   int count = 0;

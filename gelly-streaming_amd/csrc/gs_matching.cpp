@@ -17,17 +17,14 @@
 
 #include "gs_internal.hpp"
 #include "gs_matching.hpp"
+#include "gs_vtable.hpp"
 
 using namespace gsi;
 
-struct gs_matching_s : StreamOwner {
+struct gs_matching_s : StreamOwner, VertexTable {  // (the vertex table and the vertices in rank order)
   DevBuf<unsigned long long> ctl;   // gs::MtCtl words
   DevBuf<unsigned long long> dctl;  // gs::DistCtl words of the vertex phase
-  // the vertex table, the vertices in rank order and the state record of every rank
-  DevBuf<gs::DistVSlot> vtab;  // [vcap + 1]
-  DevBuf<int64_t> vid;         // [dist_vid_cap(vcap)]
-  DevBuf<gs::MtVertex> st;     // [dist_vid_cap(vcap)]
-  uint64_t vcap = 0;
+  DevBuf<gs::MtVertex> st;          // [dist_vid_cap(vcap)] the state record of every rank
   // fold scratch for n_cap arrivals
   uint64_t n_cap = 0;
   DevBuf<uint32_t> vslot;  // [2 n] slot of every entry
@@ -66,99 +63,52 @@ struct gs_matching_s : StreamOwner {
   // gs_testing_matching_tune (< 0: product) and gs_testing_matching_stats
   int64_t tune[3] = {-1, -1, -1};
   uint64_t stats[5] = {0, 0, 0, 0, 0};
-
-  gs::DistVTable vtable() const { return gs::dist_vtable_of(vtab, vcap); }
 };
 
 namespace {
 
-int check_mt(gs_matching m) {
-  if (!m) return fail(GS_ERR_INVALID, "null matching handle");
-  return GS_OK;
-}
+constexpr const char* kWhat = "matching";  // check_handle: "null matching handle"
 
-int truncated(size_t cap, uint64_t need) {
-  return fail(GS_ERR_TRUNCATED, "output capacity " + std::to_string(cap) + " < " + std::to_string(need));
-}
-
-// A vertex table of `cap` slots, its vertex list and its state records in place of the current
-// ones, whose vertices move over (a rank is the same before and after); the first of a handle.
+// The vertex table grows (VertexTable::grow) and the state records with it, inside the same wait.
 int grow_vertices(gs_matching_s* m, uint64_t cap) {
-  DevBuf<gs::DistVSlot> tab;
-  DevBuf<int64_t> vid;
   DevBuf<gs::MtVertex> st;
   const uint64_t ranks = gs::dist_vid_cap(cap);
-  GS_HIP(tab.alloc(cap + 1));
-  GS_HIP(vid.alloc(ranks));
-  GS_HIP(st.alloc(ranks));
-  const gs::DistVTable to = gs::dist_vtable_of(tab, cap);
-  gs::launch_dist_init(to, m->stream);
-  GS_HIP(hipGetLastError());
-  gs::launch_mt_init(st, m->vtab ? m->nv : 0, ranks, m->stream);
-  GS_HIP(hipGetLastError());
-  if (m->vtab) {
-    gs::launch_dist_rebuild(m->vtable(), to, m->dctl, m->stream);
-    GS_HIP(hipGetLastError());
-    if (m->nv) {
-      GS_HIP(hipMemcpyAsync(vid, m->vid, m->nv * 8, hipMemcpyDeviceToDevice, m->stream));
+  const int rc = m->grow(cap, m->nv, m->dctl, m->stream, [&](bool rebuild) -> int {
+    GS_HIP(st.alloc(ranks));
+    GS_LAUNCH(gs::launch_mt_init(st, rebuild ? m->nv : 0, ranks, m->stream));
+    if (rebuild && m->nv)
       GS_HIP(hipMemcpyAsync(st, m->st, m->nv * sizeof(gs::MtVertex), hipMemcpyDeviceToDevice, m->stream));
-    }
-    GS_HIP(hipStreamSynchronize(m->stream));  // before the old arrays are freed
-  }
-  m->vtab.swap(tab);
-  m->vid.swap(vid);
+    return GS_OK;
+  });
+  if (rc) return rc;
   m->st.swap(st);
-  m->vcap = cap;
   return GS_OK;
 }
 
 int ensure_scratch(gs_matching_s* m, uint64_t n) {
-  if (m->n_cap >= n) return GS_OK;
-  GS_HIP(hipStreamSynchronize(m->stream));
-  m->n_cap = 0;
-  const uint64_t c = std::min<uint64_t>(gs::kMtMaxFold, n + n / 4);
-  const uint64_t tiles = gs::dist_tiles(2 * c, gs::DISTINCT_TILE);
   static_assert(2 * gs::MATCHING_TILE == gs::DISTINCT_TILE, "tbase serves both compactions: n / 1024 tiles");
-  GS_HIP(m->vslot.alloc(2 * c));
-  GS_HIP(m->flags.alloc(tiles * gs::DISTINCT_TILE));
-  GS_HIP(m->tbase.alloc(tiles + 1));
-  GS_HIP(m->entry.alloc(2 * c));
-  GS_HIP(m->ru.alloc(c));
-  GS_HIP(m->rv.alloc(c));
-  GS_HIP(m->w.alloc(c));
-  GS_HIP(m->mark.alloc(c));
-  GS_HIP(m->acc.alloc(c));
-  GS_HIP(m->rec.alloc(c));
-  GS_HIP(m->list[0].alloc(c));
-  GS_HIP(m->list[1].alloc(c));
-  m->n_cap = c;
+  const auto alloc_scratch = [&](uint64_t c) {
+    const uint64_t tiles = gs::dist_tiles(2 * c, gs::DISTINCT_TILE);
+    hipError_t e = alloc_each(2 * c, m->vslot, m->entry);
+    if (e == hipSuccess) e = m->flags.alloc(tiles * gs::DISTINCT_TILE);
+    if (e == hipSuccess) e = m->tbase.alloc(tiles + 1);
+    if (e == hipSuccess) e = alloc_each(c, m->ru, m->rv, m->w, m->mark, m->acc, m->rec, m->list[0], m->list[1]);
+    return e;
+  };
+  GS_HIP(grow_group(m->stream, m->n_cap, n, std::min<uint64_t>(gs::kMtMaxFold, n + n / 4), alloc_scratch));
   return GS_OK;
 }
 
 int ensure_events(gs_matching_s* m, uint64_t rows) {
-  if (m->ev_cap >= rows) return GS_OK;
-  GS_HIP(hipStreamSynchronize(m->stream));
-  m->ev_cap = 0;
-  const uint64_t c = rows + rows / 4;
-  GS_HIP(m->ev_arrival.alloc(c));
-  GS_HIP(m->ev_type.alloc(c));
-  GS_HIP(m->ev_src.alloc(c));
-  GS_HIP(m->ev_dst.alloc(c));
-  GS_HIP(m->ev_val.alloc(c));
-  m->ev_cap = c;
+  GS_HIP(grow_group(m->stream, m->ev_cap, rows, rows + rows / 4, [&](uint64_t c) {
+    return alloc_each(c, m->ev_arrival, m->ev_type, m->ev_src, m->ev_dst, m->ev_val);
+  }));
   return GS_OK;
 }
 
 int ensure_staging(gs_matching_s* m, uint64_t rows) {
-  if (m->o_cap >= rows) return GS_OK;
-  GS_HIP(hipStreamSynchronize(m->stream));
-  m->o_cap = 0;
-  const uint64_t c = rows + rows / 4;
-  GS_HIP(m->o_a.alloc(c));
-  GS_HIP(m->o_b.alloc(c));
-  GS_HIP(m->o_c.alloc(c));
-  GS_HIP(m->o_d.alloc(c));
-  m->o_cap = c;
+  GS_HIP(grow_group(m->stream, m->o_cap, rows, rows + rows / 4,
+                    [&](uint64_t c) { return alloc_each(c, m->o_a, m->o_b, m->o_c, m->o_d); }));
   return GS_OK;
 }
 
@@ -185,14 +135,13 @@ int fold_piece(gs_matching_s* m, const int64_t* src, const int64_t* dst, const i
   const uint64_t ranks = gs::dist_vid_cap(m->vcap);
   // ranks
   GS_HIP(hipMemsetAsync(m->dctl, 0, gs::DIST_CTL_WORDS * 8, st));
-  gs::launch_dist_vertices(src, dst, n, stride, vt, m->vslot, m->flags, m->tbase, m->nv, m->vid, ranks, m->entry,
-                           m->dctl, st);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_dist_vertices(src, dst, n, stride, vt, m->vslot, m->flags, m->tbase, m->nv, m->vid, ranks,
+                                     m->entry, m->dctl, st));
   static_assert(gs::MT_UNSAFE == 2 && gs::kMtFoldWords == 10, "the fold's words lie around MT_UNSAFE");
   GS_HIP(hipMemsetAsync(m->ctl, 0, gs::MT_UNSAFE * 8, st));
   GS_HIP(hipMemsetAsync(m->ctl + gs::MT_UNSAFE + 1, 0, (gs::kMtFoldWords - gs::MT_UNSAFE - 1) * 8, st));
-  gs::launch_mt_gather(m->vslot, vt, ranks, val, stride, n, m->ru, m->rv, m->w, m->list[0], m->acc, m->ctl, st);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_mt_gather(m->vslot, vt, ranks, val, stride, n, m->ru, m->rv, m->w, m->list[0], m->acc, m->ctl,
+                                 st));
   gs::MtFold F;
   F.st = m->st;
   F.ru = m->ru;
@@ -213,8 +162,7 @@ int fold_piece(gs_matching_s* m, const int64_t* src, const int64_t* dst, const i
   uint64_t np = n, rounds = 0;
   int side = 0;
   while (np && rounds < round_cap && (fixed || np >= gs::kMatchingTailThreshold)) {
-    gs::launch_mt_round(F, m->list[side], np, m->list[side ^ 1], iter_cap, sharpen, m->ctl, st);
-    GS_HIP(hipGetLastError());
+    GS_LAUNCH(gs::launch_mt_round(F, m->list[side], np, m->list[side ^ 1], iter_cap, sharpen, m->ctl, st));
     unsigned long long w2[2] = {0, 0};
     GS_HIP(hipMemcpyAsync(w2, m->ctl + gs::MT_NEXT, sizeof(w2), hipMemcpyDeviceToHost, st));
     GS_HIP(hipStreamSynchronize(st));
@@ -226,15 +174,12 @@ int fold_piece(gs_matching_s* m, const int64_t* src, const int64_t* dst, const i
   }
   const uint64_t tail = np;
   if (np) {
-    gs::launch_mt_tail(F, m->list[side], m->list[side ^ 1], np, iter_cap, sharpen, m->ctl, st);
-    GS_HIP(hipGetLastError());
+    GS_LAUNCH(gs::launch_mt_tail(F, m->list[side], m->list[side ^ 1], np, iter_cap, sharpen, m->ctl, st));
   }
   // events: rows per tile, their scan, the counts (the fold's last wait), the rows
   const uint64_t nt = gs::mt_tiles(n);
-  gs::launch_mt_event_count(m->acc, m->rec, m->w, n, m->tbase, m->ctl, st);
-  GS_HIP(hipGetLastError());
-  gs::launch_tile_scan(m->tbase, nt, m->ctl + gs::MT_ROWS, st);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_mt_event_count(m->acc, m->rec, m->w, n, m->tbase, m->ctl, st));
+  GS_LAUNCH(gs::launch_tile_scan(m->tbase, nt, m->ctl + gs::MT_ROWS, st));
   unsigned long long c[gs::kMtFoldWords], d[gs::DIST_CTL_WORDS];
   GS_HIP(hipMemcpyAsync(c, m->ctl, sizeof(c), hipMemcpyDeviceToHost, st));
   GS_HIP(hipMemcpyAsync(d, m->dctl, sizeof(d), hipMemcpyDeviceToHost, st));
@@ -256,9 +201,8 @@ int fold_piece(gs_matching_s* m, const int64_t* src, const int64_t* dst, const i
   m->ev_rows = c[gs::MT_ROWS];
   if (m->ev_rows) {
     if (int rc = ensure_events(m, m->ev_rows)) return rc;
-    gs::launch_mt_event_write(m->acc, m->rec, m->ru, m->rv, m->w, n, m->tbase, m->vid, m->nv, m->ev_arrival,
-                              m->ev_type, m->ev_src, m->ev_dst, m->ev_val, m->ev_cap, st);
-    GS_HIP(hipGetLastError());
+    GS_LAUNCH(gs::launch_mt_event_write(m->acc, m->rec, m->ru, m->rv, m->w, n, m->tbase, m->vid, m->nv, m->ev_arrival,
+                                        m->ev_type, m->ev_src, m->ev_dst, m->ev_val, m->ev_cap, st));
   }
   return GS_OK;
 }
@@ -280,13 +224,8 @@ int fold_all(gs_matching_s* m, const int64_t* src, const int64_t* dst, const int
     const uint64_t len = std::min<uint64_t>(gs::kMtMaxFold, n - at);
     const int64_t *ps = src + at * stride, *pd = dst + at * stride, *pv = val + at * stride;
     if (host) {
-      if (m->h_cap < len) {
-        GS_HIP(hipStreamSynchronize(m->stream));
-        m->h_cap = 0;
-        const uint64_t c = std::min<uint64_t>(gs::kMtMaxFold, len + len / 4);
-        GS_HIP(m->stage.alloc(3 * c));
-        m->h_cap = c;
-      }
+      GS_HIP(grow_group(m->stream, m->h_cap, len, std::min<uint64_t>(gs::kMtMaxFold, len + len / 4),
+                        [&](uint64_t c) { return m->stage.alloc(3 * c); }));
       int64_t* s0 = m->stage;
       GS_HIP(hipMemcpyAsync(s0, ps, len * 8, hipMemcpyHostToDevice, m->stream));
       GS_HIP(hipMemcpyAsync(s0 + m->h_cap, pd, len * 8, hipMemcpyHostToDevice, m->stream));
@@ -312,6 +251,9 @@ int fold_all(gs_matching_s* m, const int64_t* src, const int64_t* dst, const int
 
 int events_impl(gs_matching_s* m, uint32_t* arrival, uint8_t* type, int64_t* src, int64_t* dst, int64_t* val,
                 size_t cap, size_t* n, bool to_host) {
+  if (int rc = check_handle(m, kWhat)) return rc;
+  if (!n) return fail(GS_ERR_INVALID, "n is null");
+  DeviceGuard g(m->device);
   if (!m->ev_kept) return fail(GS_ERR_INVALID, "matching events: the last fold was cut into pieces, its events were not kept");
   const uint64_t rows = m->ev_rows;
   *n = rows;
@@ -330,18 +272,15 @@ int events_impl(gs_matching_s* m, uint32_t* arrival, uint8_t* type, int64_t* src
 // scan the state, compact the source vertices of M's edges, sort by stamp, decode
 int export_impl(gs_matching_s* m, int64_t* src, int64_t* dst, int64_t* val, uint64_t* first, size_t cap, size_t* n,
                 bool to_host) {
+  if (int rc = check_handle(m, kWhat)) return rc;
+  if (!n) return fail(GS_ERR_INVALID, "n is null");
+  DeviceGuard g(m->device);
   const uint64_t ne = m->edges;
   *n = ne;
   if (cap < ne) return truncated(cap, ne);
   if (ne == 0) return GS_OK;
-  if (m->x_cap < ne) {
-    GS_HIP(hipStreamSynchronize(m->stream));
-    m->x_cap = 0;
-    const uint64_t c = ne + ne / 4;
-    GS_HIP(m->x_stamp.alloc(c));
-    GS_HIP(m->x_rank.alloc(c));
-    m->x_cap = c;
-  }
+  GS_HIP(grow_group(m->stream, m->x_cap, ne, ne + ne / 4,
+                    [&](uint64_t c) { return alloc_each(c, m->x_stamp, m->x_rank); }));
   if (int rc = sort_scratch_ensure(m->sort, ne, m->stream)) return rc;
   int64_t *ds = src, *dd = dst, *dv = val;
   unsigned long long* df = reinterpret_cast<unsigned long long*>(first);
@@ -353,12 +292,10 @@ int export_impl(gs_matching_s* m, int64_t* src, int64_t* dst, int64_t* val, uint
     df = first ? m->o_d.get() : nullptr;
   }
   GS_HIP(hipMemsetAsync(m->ctl + gs::MT_EXPORT, 0, 8, m->stream));
-  gs::launch_mt_export(m->st, m->nv, m->x_stamp, m->x_rank, ne, m->ctl, m->stream);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_mt_export(m->st, m->nv, m->x_stamp, m->x_rank, ne, m->ctl, m->stream));
   uint32_t* const sctl = m->sort.ctl;
   GS_HIP(hipMemsetAsync(sctl, 0, gs::kSortCtlWords * 4, m->stream));
-  gs::launch_sort_digits_one(m->x_stamp, ne, sctl, m->stream);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_sort_digits_one(m->x_stamp, ne, sctl, m->stream));
   // every stamp is below folded: the digits above its bits are equal in all keys
   bool skip[gs::kSortPasses];
   for (int p = 0; p < (int)gs::kSortPasses; ++p) skip[p] = p > 0 && (m->folded >> (8 * p)) == 0;
@@ -366,8 +303,7 @@ int export_impl(gs_matching_s* m, int64_t* src, int64_t* dst, int64_t* val, uint
   int side = 0;
   if (int rc = sort_run(m->sort, m->x_stamp, ne, sctl, skip, &cur, &side, m->stream)) return rc;
   if (!cur.key || !cur.pay) return fail(GS_ERR_HIP, "matching export: the sort ran no pass");
-  gs::launch_mt_decode(cur.key, cur.pay, m->x_rank, ne, m->st, m->vid, m->nv, ds, dd, dv, df, m->stream);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_mt_decode(cur.key, cur.pay, m->x_rank, ne, m->st, m->vid, m->nv, ds, dd, dv, df, m->stream));
   if (to_host) {
     if (src) GS_HIP(hipMemcpyAsync(src, ds, ne * 8, hipMemcpyDeviceToHost, m->stream));
     if (dst) GS_HIP(hipMemcpyAsync(dst, dd, ne * 8, hipMemcpyDeviceToHost, m->stream));
@@ -400,12 +336,10 @@ int gs_matching_create(gs_matching* out, int device, uint64_t vertex_hint) {
 }
 
 int gs_matching_reset(gs_matching m) {
-  if (int rc = check_mt(m)) return rc;
+  if (int rc = check_handle(m, kWhat)) return rc;
   DeviceGuard g(m->device);
-  gs::launch_dist_init(m->vtable(), m->stream);
-  GS_HIP(hipGetLastError());
-  gs::launch_mt_init(m->st, 0, gs::dist_vid_cap(m->vcap), m->stream);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_dist_init(m->vtable(), m->stream));
+  GS_LAUNCH(gs::launch_mt_init(m->st, 0, gs::dist_vid_cap(m->vcap), m->stream));
   GS_HIP(hipMemsetAsync(m->ctl, 0, gs::MT_CTL_WORDS * 8, m->stream));
   m->nv = m->folded = m->edges = 0;
   m->weight = 0;
@@ -416,7 +350,7 @@ int gs_matching_reset(gs_matching m) {
 
 int gs_matching_fold_device(gs_matching m, const int64_t* src, const int64_t* dst, const int64_t* val, size_t n,
                             uint8_t* accepted, size_t stride) {
-  if (int rc = check_mt(m)) return rc;
+  if (int rc = check_handle(m, kWhat)) return rc;
   if (stride == 0 || stride > 0xFFFFFFFFull) return fail(GS_ERR_INVALID, "stride must be >= 1");
   if (int rc = fold_guard(m, src, dst, val, n)) return rc;
   return fold_all(m, src, dst, val, n, accepted, stride, false);
@@ -424,29 +358,23 @@ int gs_matching_fold_device(gs_matching m, const int64_t* src, const int64_t* ds
 
 int gs_matching_fold(gs_matching m, const int64_t* src, const int64_t* dst, const int64_t* val, size_t n,
                      uint8_t* accepted) {
-  if (int rc = check_mt(m)) return rc;
+  if (int rc = check_handle(m, kWhat)) return rc;
   if (int rc = fold_guard(m, src, dst, val, n)) return rc;
   return fold_all(m, src, dst, val, n, accepted, 1, true);
 }
 
 int gs_matching_events_device(gs_matching m, uint32_t* arrival, uint8_t* type, int64_t* src, int64_t* dst,
                               int64_t* val, size_t cap, size_t* n) {
-  if (int rc = check_mt(m)) return rc;
-  if (!n) return fail(GS_ERR_INVALID, "n is null");
-  DeviceGuard g(m->device);
   return events_impl(m, arrival, type, src, dst, val, cap, n, false);
 }
 
 int gs_matching_events(gs_matching m, uint32_t* arrival, uint8_t* type, int64_t* src, int64_t* dst, int64_t* val,
                        size_t cap, size_t* n) {
-  if (int rc = check_mt(m)) return rc;
-  if (!n) return fail(GS_ERR_INVALID, "n is null");
-  DeviceGuard g(m->device);
   return events_impl(m, arrival, type, src, dst, val, cap, n, true);
 }
 
 int gs_matching_count(gs_matching m, uint64_t* edges, uint64_t* vertices_seen, int64_t* weight) {
-  if (int rc = check_mt(m)) return rc;
+  if (int rc = check_handle(m, kWhat)) return rc;
   if (!edges || !vertices_seen || !weight) return fail(GS_ERR_INVALID, "null count pointers");
   *edges = m->edges;
   *vertices_seen = m->nv;
@@ -456,61 +384,33 @@ int gs_matching_count(gs_matching m, uint64_t* edges, uint64_t* vertices_seen, i
 
 int gs_matching_export_device(gs_matching m, int64_t* src, int64_t* dst, int64_t* val, uint64_t* first, size_t cap,
                               size_t* n) {
-  if (int rc = check_mt(m)) return rc;
-  if (!n) return fail(GS_ERR_INVALID, "n is null");
-  DeviceGuard g(m->device);
   return export_impl(m, src, dst, val, first, cap, n, false);
 }
 
 int gs_matching_export(gs_matching m, int64_t* src, int64_t* dst, int64_t* val, uint64_t* first, size_t cap,
                        size_t* n) {
-  if (int rc = check_mt(m)) return rc;
-  if (!n) return fail(GS_ERR_INVALID, "n is null");
-  DeviceGuard g(m->device);
   return export_impl(m, src, dst, val, first, cap, n, true);
 }
 
 int gs_matching_mate_device(gs_matching m, const int64_t* v, size_t n, int64_t* mate, int64_t* val, uint8_t* found) {
-  if (int rc = check_mt(m)) return rc;
+  if (int rc = check_handle(m, kWhat)) return rc;
   if (n == 0) return GS_OK;
   if (!v) return fail(GS_ERR_INVALID, "null arrays");
   DeviceGuard g(m->device);
-  if (m->q_cap < n) {
-    GS_HIP(hipStreamSynchronize(m->stream));
-    m->q_cap = 0;
-    GS_HIP(m->q_rank.alloc(n + n / 4));
-    m->q_cap = n + n / 4;
-  }
-  gs::launch_dist_rank(m->vtable(), v, n, m->q_rank, nullptr, m->stream);
-  GS_HIP(hipGetLastError());
-  gs::launch_mt_mate(m->q_rank, n, m->st, m->vid, m->nv, mate, val, found, m->stream);
-  GS_HIP(hipGetLastError());
+  GS_HIP(grow_group(m->stream, m->q_cap, n, n + n / 4, [&](uint64_t c) { return m->q_rank.alloc(c); }));
+  GS_LAUNCH(gs::launch_dist_rank(m->vtable(), v, n, m->q_rank, nullptr, m->stream));
+  GS_LAUNCH(gs::launch_mt_mate(m->q_rank, n, m->st, m->vid, m->nv, mate, val, found, m->stream));
   return GS_OK;
 }
 
-int gs_matching_sync(gs_matching m) {
-  if (int rc = check_mt(m)) return rc;
-  DeviceGuard g(m->device);
-  GS_HIP(hipStreamSynchronize(m->stream));
-  return GS_OK;
-}
-
-int gs_matching_get_stream(gs_matching m, void** stream) {
-  if (int rc = check_mt(m)) return rc;
-  if (!stream) return fail(GS_ERR_INVALID, "stream is null");
-  *stream = m->stream;
-  return GS_OK;
-}
-
-int gs_matching_wait_stream(gs_matching m, void* stream) {
-  if (int rc = check_mt(m)) return rc;
-  return m->wait_stream(stream);
-}
+int gs_matching_sync(gs_matching m) { return owner_sync(m, kWhat); }
+int gs_matching_get_stream(gs_matching m, void** stream) { return owner_get_stream(m, kWhat, stream); }
+int gs_matching_wait_stream(gs_matching m, void* stream) { return owner_wait_stream(m, kWhat, stream); }
 
 // gs_testing.h: the last fold. No device call.
 int gs_testing_matching_stats(void* handle, uint64_t* out) {
   gs_matching m = static_cast<gs_matching>(handle);
-  if (int rc = check_mt(m)) return rc;
+  if (int rc = check_handle(m, kWhat)) return rc;
   if (!out) return fail(GS_ERR_INVALID, "out is null");
   for (int i = 0; i < 5; ++i) out[i] = m->stats[i];
   out[5] = m->safe ? 1 : 0;
@@ -519,7 +419,7 @@ int gs_testing_matching_stats(void* handle, uint64_t* out) {
 
 int gs_testing_matching_tune(void* handle, int what, int64_t value) {
   gs_matching m = static_cast<gs_matching>(handle);
-  if (int rc = check_mt(m)) return rc;
+  if (int rc = check_handle(m, kWhat)) return rc;
   if (what < 0 || what > 2) return fail(GS_ERR_INVALID, "matching tune: unknown control");
   m->tune[what] = value < 0 ? -1 : value;
   return GS_OK;

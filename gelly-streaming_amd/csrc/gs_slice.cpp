@@ -57,47 +57,28 @@ namespace {
 constexpr uint64_t kSliceMaxEntries = 0xFFFFFFFFull;
 enum { PH_EXPAND = 0, PH_SORT = 1, PH_HEADS = 2, PH_REDUCE = 3, PH_GATHER = 4 };
 
-int check_slice(gs_slices s) {
-  if (!s) return fail(GS_ERR_INVALID, "null slice handle");
-  return GS_OK;
-}
+constexpr const char* kWhat = "slice";  // check_handle: "null slice handle"
 
 int ensure_window(gs_slices_s* s, uint64_t n, uint64_t entries) {
-  if (s->n_cap < n) {
-    GS_HIP(hipStreamSynchronize(s->stream));
-    s->n_cap = 0;
-    const uint64_t c = n + n / 4;
-    GS_HIP(s->esrc.alloc(c));
-    GS_HIP(s->edst.alloc(c));
-    GS_HIP(s->eval.alloc(c));
-    s->n_cap = c;
-  }
-  if (s->e_cap < entries) {
-    GS_HIP(hipStreamSynchronize(s->stream));
-    s->e_cap = 0;
-    const uint64_t c = std::min<uint64_t>(kSliceMaxEntries, entries + entries / 4);
+  GS_HIP(grow_group(s->stream, s->n_cap, n, n + n / 4,
+                    [&](uint64_t c) { return alloc_each(c, s->esrc, s->edst, s->eval); }));
+  const auto alloc_entries = [&](uint64_t c) {
     const uint64_t tiles = gs::slice_tiles(c, gs::SLICE_TILE);
-    GS_HIP(s->kid.alloc(c));
-    GS_HIP(s->vtx.alloc(c));
-    GS_HIP(s->off.alloc(c + 1));
-    GS_HIP(s->flags.alloc(tiles * gs::SLICE_TILE));
-    GS_HIP(s->tbase.alloc(tiles + 1));
-    GS_HIP(s->lead.alloc(tiles));
-    GS_HIP(s->trail.alloc(tiles));
-    GS_HIP(s->carry.alloc(tiles));
-    s->e_cap = c;
-  }
+    hipError_t e = alloc_each(c, s->kid, s->vtx);
+    if (e == hipSuccess) e = s->off.alloc(c + 1);
+    if (e == hipSuccess) e = s->flags.alloc(tiles * gs::SLICE_TILE);
+    if (e == hipSuccess) e = s->tbase.alloc(tiles + 1);
+    if (e == hipSuccess) e = alloc_each(tiles, s->lead, s->trail, s->carry);
+    return e;
+  };
+  GS_HIP(grow_group(s->stream, s->e_cap, entries, std::min<uint64_t>(kSliceMaxEntries, entries + entries / 4),
+                    alloc_entries));
   return sort_scratch_ensure(s->sort, entries, s->stream);
 }
 
 int ensure_staging(gs_slices_s* s, uint64_t rows) {
-  if (s->o_cap >= rows) return GS_OK;
-  GS_HIP(hipStreamSynchronize(s->stream));
-  s->o_cap = 0;
-  const uint64_t c = rows + rows / 4;
-  GS_HIP(s->o_a.alloc(c));
-  GS_HIP(s->o_b.alloc(c));
-  s->o_cap = c;
+  GS_HIP(grow_group(s->stream, s->o_cap, rows, rows + rows / 4,
+                    [&](uint64_t c) { return alloc_each(c, s->o_a, s->o_b); }));
   return GS_OK;
 }
 
@@ -115,7 +96,7 @@ void set_empty(gs_slices_s* s, int dir) {
 }
 
 int window_guard(gs_slices s, const void* src, const void* dst, size_t n, int dir) {
-  if (int rc = check_slice(s)) return rc;
+  if (int rc = check_handle(s, kWhat)) return rc;
   if (dir < 0 || dir >= gs::kSliceDirs) return fail(GS_ERR_INVALID, "unknown slice direction");
   if (n && (!src || !dst)) return fail(GS_ERR_INVALID, "null edge arrays");
   if ((uint64_t)n > kSliceMaxEntries || gs::slice_entries(n, dir) > kSliceMaxEntries)
@@ -131,20 +112,17 @@ int window_impl(gs_slices_s* s, const int64_t* src, const int64_t* dst, const in
   set_empty(s, dir);  // (a failure below leaves an empty window)
   PhaseTimer timer = phase_timer(s, PH_EXPAND, 3);
   timer.mark(PH_EXPAND);
-  gs::launch_slice_expand(src, dst, val, n, stride, dir, s->esrc, s->edst, s->eval, s->kid, s->stream);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_slice_expand(src, dst, val, n, stride, dir, s->esrc, s->edst, s->eval, s->kid, s->stream));
   timer.mark(PH_SORT);
   uint32_t* const sctl = s->sort.ctl;
   GS_HIP(hipMemsetAsync(sctl, 0, gs::kSortCtlWords * 4, s->stream));
-  gs::launch_sort_digits_one(s->kid, entries, sctl, s->stream);  // rows 0..7: the keys
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_sort_digits_one(s->kid, entries, sctl, s->stream));  // rows 0..7: the keys
   gs::SortSrc cur;  // (pay null: payload i of entry i is i)
   int side = 0;
   if (int rc = sort_run(s->sort, s->kid, entries, sctl, nullptr, &cur, &side, s->stream)) return rc;
   if (!cur.key || !cur.pay) return fail(GS_ERR_HIP, "slice window: the sort ran no pass");
   timer.mark(PH_HEADS);
-  gs::launch_slice_heads(cur.key, entries, s->flags, s->tbase, s->ctl, s->vtx, s->off, s->e_cap, s->stream);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_slice_heads(cur.key, entries, s->flags, s->tbase, s->ctl, s->vtx, s->off, s->e_cap, s->stream));
   // the window's one host synchronisation: the vertex count
   unsigned long long nv = 0;
   GS_HIP(hipMemcpyAsync(&nv, s->ctl + gs::SLICE_NV, 8, hipMemcpyDeviceToHost, s->stream));
@@ -162,11 +140,14 @@ int window_impl(gs_slices_s* s, const int64_t* src, const int64_t* dst, const in
 }
 
 int reduce_impl(gs_slices_s* s, int op, int64_t* v, int64_t* out, size_t cap, size_t* n, bool to_host) {
+  if (int rc = check_handle(s, kWhat)) return rc;
+  if (!n) return fail(GS_ERR_INVALID, "n is null");
+  if (op < 0 || op >= gs::kSliceOps) return fail(GS_ERR_INVALID, "unknown slice op");
+  DeviceGuard g(s->device);
   *n = s->nv;
   if (op != GS_SLICE_COUNT && !s->has_val)
     return fail(GS_ERR_INVALID, "the window has no values: only the count op applies");
-  if (cap < s->nv)
-    return fail(GS_ERR_TRUNCATED, "output capacity " + std::to_string(cap) + " < " + std::to_string(s->nv));
+  if (cap < s->nv) return truncated(cap, s->nv);
   if (s->nv == 0) return GS_OK;
   if (!v || !out) return fail(GS_ERR_INVALID, "null arrays");
   int64_t* dout = out;
@@ -177,13 +158,12 @@ int reduce_impl(gs_slices_s* s, int op, int64_t* v, int64_t* out, size_t cap, si
   PhaseTimer timer = phase_timer(s, PH_REDUCE, 1);
   timer.mark(0);
   if (op == GS_SLICE_COUNT) {
-    gs::launch_slice_count(s->off, s->nv, dout, s->stream);
+    GS_LAUNCH(gs::launch_slice_count(s->off, s->nv, dout, s->stream));
   } else {
-    gs::launch_slice_reduce(op, s->flags, s->spay, s->eval, s->entries, s->n, s->dir, s->tbase, dout, s->nv, s->lead,
-                            s->trail, s->carry, s->stream);
     s->reduce_tiles = gs::slice_tiles(s->entries, gs::SLICE_TILE);
+    GS_LAUNCH(gs::launch_slice_reduce(op, s->flags, s->spay, s->eval, s->entries, s->n, s->dir, s->tbase, dout, s->nv,
+                                      s->lead, s->trail, s->carry, s->stream));
   }
-  GS_HIP(hipGetLastError());
   timer.mark(1);
   timer.finish();
   GS_HIP(hipMemcpyAsync(v, s->vtx, s->nv * 8, to_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, s->stream));
@@ -196,6 +176,9 @@ int reduce_impl(gs_slices_s* s, int op, int64_t* v, int64_t* out, size_t cap, si
 
 int neighborhoods_impl(gs_slices_s* s, int64_t* v, uint64_t* offset, int64_t* neighbor, int64_t* val, size_t cap_v,
                        size_t cap_e, size_t* nv, size_t* ne, bool to_host) {
+  if (int rc = check_handle(s, kWhat)) return rc;
+  if (!nv || !ne) return fail(GS_ERR_INVALID, "null count pointers");
+  DeviceGuard g(s->device);
   *nv = s->nv;
   *ne = s->entries;
   if (val && !s->has_val) return fail(GS_ERR_INVALID, "the window has no values: pass a null val array");
@@ -217,9 +200,8 @@ int neighborhoods_impl(gs_slices_s* s, int64_t* v, uint64_t* offset, int64_t* ne
   }
   PhaseTimer timer = phase_timer(s, PH_GATHER, 1);
   timer.mark(0);
-  gs::launch_slice_gather(s->spay, s->entries, s->n, s->dir, s->esrc, s->edst, s->eval, dn, dv, s->entries,
-                          s->stream);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_slice_gather(s->spay, s->entries, s->n, s->dir, s->esrc, s->edst, s->eval, dn, dv, s->entries,
+                                    s->stream));
   timer.mark(1);
   timer.finish();
   const hipMemcpyKind kind = to_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
@@ -280,7 +262,7 @@ int gs_slice_window(gs_slices s, const int64_t* src, const int64_t* dst, const i
 }
 
 int gs_slice_size(gs_slices s, uint64_t* vertices, uint64_t* entries) {
-  if (int rc = check_slice(s)) return rc;
+  if (int rc = check_handle(s, kWhat)) return rc;
   if (!vertices || !entries) return fail(GS_ERR_INVALID, "null count pointers");
   *vertices = s->nv;
   *entries = s->entries;
@@ -288,55 +270,26 @@ int gs_slice_size(gs_slices s, uint64_t* vertices, uint64_t* entries) {
 }
 
 int gs_slice_reduce_device(gs_slices s, int op, int64_t* v, int64_t* out, size_t cap, size_t* n) {
-  if (int rc = check_slice(s)) return rc;
-  if (!n) return fail(GS_ERR_INVALID, "n is null");
-  if (op < 0 || op >= gs::kSliceOps) return fail(GS_ERR_INVALID, "unknown slice op");
-  DeviceGuard g(s->device);
   return reduce_impl(s, op, v, out, cap, n, false);
 }
 
 int gs_slice_reduce(gs_slices s, int op, int64_t* v, int64_t* out, size_t cap, size_t* n) {
-  if (int rc = check_slice(s)) return rc;
-  if (!n) return fail(GS_ERR_INVALID, "n is null");
-  if (op < 0 || op >= gs::kSliceOps) return fail(GS_ERR_INVALID, "unknown slice op");
-  DeviceGuard g(s->device);
   return reduce_impl(s, op, v, out, cap, n, true);
 }
 
 int gs_slice_neighborhoods_device(gs_slices s, int64_t* v, uint64_t* offset, int64_t* neighbor, int64_t* val,
                                   size_t cap_v, size_t cap_e, size_t* nv, size_t* ne) {
-  if (int rc = check_slice(s)) return rc;
-  if (!nv || !ne) return fail(GS_ERR_INVALID, "null count pointers");
-  DeviceGuard g(s->device);
   return neighborhoods_impl(s, v, offset, neighbor, val, cap_v, cap_e, nv, ne, false);
 }
 
 int gs_slice_neighborhoods(gs_slices s, int64_t* v, uint64_t* offset, int64_t* neighbor, int64_t* val, size_t cap_v,
                            size_t cap_e, size_t* nv, size_t* ne) {
-  if (int rc = check_slice(s)) return rc;
-  if (!nv || !ne) return fail(GS_ERR_INVALID, "null count pointers");
-  DeviceGuard g(s->device);
   return neighborhoods_impl(s, v, offset, neighbor, val, cap_v, cap_e, nv, ne, true);
 }
 
-int gs_slice_sync(gs_slices s) {
-  if (int rc = check_slice(s)) return rc;
-  DeviceGuard g(s->device);
-  GS_HIP(hipStreamSynchronize(s->stream));
-  return GS_OK;
-}
-
-int gs_slice_get_stream(gs_slices s, void** stream) {
-  if (int rc = check_slice(s)) return rc;
-  if (!stream) return fail(GS_ERR_INVALID, "stream is null");
-  *stream = s->stream;
-  return GS_OK;
-}
-
-int gs_slice_wait_stream(gs_slices s, void* stream) {
-  if (int rc = check_slice(s)) return rc;
-  return s->wait_stream(stream);
-}
+int gs_slice_sync(gs_slices s) { return owner_sync(s, kWhat); }
+int gs_slice_get_stream(gs_slices s, void** stream) { return owner_get_stream(s, kWhat, stream); }
+int gs_slice_wait_stream(gs_slices s, void* stream) { return owner_wait_stream(s, kWhat, stream); }
 
 // gs_testing.h: out[0] = tiles of the last reduce (0: none, or only the count op), out[1] = tiles
 // of the current window without a head (carry records that pass a run on), out[2] = its longest
@@ -344,15 +297,15 @@ int gs_slice_wait_stream(gs_slices s, void* stream) {
 // phases. Synchronises.
 int gs_testing_slice_stats(void* handle, uint64_t* out) {
   gs_slices s = static_cast<gs_slices>(handle);
-  if (int rc = check_slice(s)) return rc;
+  if (int rc = check_handle(s, kWhat)) return rc;
   if (!out) return fail(GS_ERR_INVALID, "out is null");
   DeviceGuard g(s->device);
   unsigned long long w[2] = {0, 0};
   if (s->nv) {
     static_assert(gs::SLICE_NOHEAD == gs::SLICE_LONGEST + 1, "the two diagnostic words are adjacent");
     GS_HIP(hipMemsetAsync(s->ctl + gs::SLICE_LONGEST, 0, 16, s->stream));
-    gs::launch_slice_stats(s->off, s->nv, s->tbase, gs::slice_tiles(s->entries, gs::SLICE_TILE), s->ctl, s->stream);
-    GS_HIP(hipGetLastError());
+    GS_LAUNCH(gs::launch_slice_stats(s->off, s->nv, s->tbase, gs::slice_tiles(s->entries, gs::SLICE_TILE), s->ctl,
+                                     s->stream));
     GS_HIP(hipMemcpyAsync(w, s->ctl + gs::SLICE_LONGEST, sizeof(w), hipMemcpyDeviceToHost, s->stream));
   }
   GS_HIP(hipStreamSynchronize(s->stream));

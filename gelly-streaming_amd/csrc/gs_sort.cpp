@@ -1,6 +1,7 @@
 // gs_sort.cpp -- the host side of the radix sort (gs_sort.hpp, kernels in gs_sort_k.hip): the
 // owner of its scratch and the one loop that queues its passes, shared by the component export
-// (gs_capi.cpp), the degree exports (gs_degree.cpp) and the triangle fold (gs_triangle.cpp).
+// (gs_capi.cpp), the degree exports (gs_degree.cpp), the triangle and spanner folds and the other
+// stand-alone summaries.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -43,14 +44,22 @@ int sort_run(SortScratch& s, const int64_t* ids, uint64_t n, const uint32_t* his
   cur->rows = n;
   for (int p = 0; p < (int)gs::kSortPasses; ++p) {
     if (skip && skip[p]) continue;
-    gs::launch_sort_pass(*cur, n, p, s.table, hist + p * gs::kSortRadix, s.key[*side], s.pay[*side], st);
-    GS_HIP(hipGetLastError());
+    GS_LAUNCH(gs::launch_sort_pass(*cur, n, p, s.table, hist + p * gs::kSortRadix, s.key[*side], s.pay[*side], st));
     cur->key = s.key[*side];
     cur->pay = s.pay[*side];
     cur->ids = nullptr;
     *side ^= 1;
   }
   return GS_OK;
+}
+
+int sort_by_pair(SortScratch& s, const int64_t* x, const int64_t* y, uint64_t n, gs::SortSrc* cur, hipStream_t st) {
+  GS_HIP(hipMemsetAsync(s.ctl, 0, gs::kSortCtlWords * 4, st));
+  GS_LAUNCH(gs::launch_sort_digits(x, y, n, s.ctl, st));
+  *cur = gs::SortSrc();
+  int side = 0;
+  if (int rc = sort_run(s, y, n, s.hist(1), nullptr, cur, &side, st)) return rc;
+  return sort_run(s, x, n, s.hist(0), nullptr, cur, &side, st);
 }
 
 }  // namespace gsi

@@ -6,7 +6,8 @@
 // flag / scan / compact idiom is gs_scan.hpp). Every launch is queued on the given stream; kernel boundaries
 // carry all ordering between workgroups (no workgroup waits on another inside a launch).
 // The host part at the end (gs_sort.cpp) owns the sort's scratch and drives its passes for
-// every caller: the component export, the degree exports, the triangle fold and the window slices.
+// every caller: the component export, the degree exports, the triangle and spanner folds, the
+// window slices and the distinct and matching exports.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -85,6 +86,9 @@ struct SortScratch {
   DevBuf<uint32_t> table;
   DevBuf<uint32_t> ctl;  // gs::kSortCtlWords, allocated on first use
   uint64_t rows = 0;     // pairs key / pay hold (0 while they are not all allocated)
+  // the eight 256-bin histogram rows of key column `col` in ctl: launch_sort_digits fills
+  // column 0 (its first key) and column 1 (its second), launch_sort_digits_one column 0
+  uint32_t* hist(int col) const { return ctl + (size_t)col * gs::kSortPasses * gs::kSortRadix; }
 };
 
 // Scratch for `rows` pairs: allocated on growth only, with a quarter of headroom rounded up
@@ -102,5 +106,11 @@ void sort_skip_digits(const uint32_t* hist, uint64_t n, bool skip[gs::kSortPasse
 // ran, the order is then *cur's order on entry -- and *side the buffer not holding them.
 int sort_run(SortScratch& s, const int64_t* ids, uint64_t n, const uint32_t* hist, const bool* skip, gs::SortSrc* cur,
              int* side, hipStream_t st);
+
+// The n pairs (x[i], y[i]) ordered by (x, y) on st: zeroes the control words, builds the digit
+// histograms of both columns, sorts by y and then stably by x, no digit skipped (the histograms
+// stay on the device). *cur names the sorted pairs, its payloads the pairs' indices. s.hist(0)
+// and s.hist(1) hold the histograms of x and y afterwards, for a caller that reads them back.
+int sort_by_pair(SortScratch& s, const int64_t* x, const int64_t* y, uint64_t n, gs::SortSrc* cur, hipStream_t st);
 
 }  // namespace gsi

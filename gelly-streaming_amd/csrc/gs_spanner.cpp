@@ -75,10 +75,7 @@ constexpr uint64_t kSpMaxEntries = 0xFFFFFFFEull;
 constexpr uint64_t kSpMaxFold = 0x7FFFFFFFull;  // arrivals of one fold: one workgroup each
 constexpr uint64_t kSpMinCap = 64;
 
-int check_sp(gs_spanner s) {
-  if (!s) return fail(GS_ERR_INVALID, "null spanner handle");
-  return GS_OK;
-}
+constexpr const char* kWhat = "spanner";  // check_handle: "null spanner handle"
 
 int check_k(int k) {
   if (k < 1 || k > gs::kSpannerMaxK) return fail(GS_ERR_INVALID, "spanner: k must be in 1..16");
@@ -90,49 +87,27 @@ uint32_t lds_set() { return gs::sp_clamp_set(testing_value(GS_TESTING_SPANNER_LD
 int ensure_adj(gs_spanner_s* s, int side, uint64_t need) {
   if (s->acap[side] >= need) return GS_OK;
   if (need > kSpMaxEntries) return fail(GS_ERR_CAPACITY, "spanner adjacency would pass 2^32 - 2 entries");
-  GS_HIP(hipStreamSynchronize(s->stream));
-  s->acap[side] = 0;
-  const uint64_t c = std::min<uint64_t>(kSpMaxEntries, need + need / 2);
-  GS_HIP(s->ax[side].alloc(c));
-  GS_HIP(s->ay[side].alloc(c));
-  s->acap[side] = c;
+  GS_HIP(grow_group(s->stream, s->acap[side], need, std::min<uint64_t>(kSpMaxEntries, need + need / 2),
+                    [&](uint64_t c) { return alloc_each(c, s->ax[side], s->ay[side]); }));
   return GS_OK;
 }
 
 int ensure_flags(gs_spanner_s* s, uint64_t n) {
-  if (s->g_cap >= n) return GS_OK;
-  GS_HIP(hipStreamSynchronize(s->stream));
-  s->g_cap = 0;
-  const uint64_t c = n + n / 4;
-  GS_HIP(s->flags.alloc(c));
-  GS_HIP(s->blk.alloc(gs::sp_blocks(c) + 1));
-  s->g_cap = c;
+  GS_HIP(grow_group(s->stream, s->g_cap, n, n + n / 4, [&](uint64_t c) {
+    const hipError_t e = s->flags.alloc(c);
+    return e != hipSuccess ? e : s->blk.alloc(gs::sp_blocks(c) + 1);
+  }));
   return GS_OK;
 }
 
 int ensure_fold_scratch(gs_spanner_s* s, uint64_t n) {
   if (int rc = ensure_flags(s, 2 * n)) return rc;
   if (int rc = sort_scratch_ensure(s->sort, 2 * n, s->stream)) return rc;
-  if (s->f_cap >= n) return GS_OK;
-  GS_HIP(hipStreamSynchronize(s->stream));
-  s->f_cap = 0;
-  const uint64_t c = n + n / 4;
-  GS_HIP(s->stage.alloc(2 * c));
-  GS_HIP(s->res.alloc(c));
-  GS_HIP(s->heavy.alloc(c));
-  GS_HIP(s->pidx.alloc(c));
-  GS_HIP(s->ps.alloc(c));
-  GS_HIP(s->pt.alloc(c));
-  GS_HIP(s->ex.alloc(2 * c));
-  GS_HIP(s->ey.alloc(2 * c));
-  GS_HIP(s->px.alloc(2 * c));
-  GS_HIP(s->py.alloc(2 * c));
-  GS_HIP(s->pj.alloc(2 * c));
-  for (int i = 0; i < 2; ++i) {
-    GS_HIP(s->status[i].alloc(c));
-    GS_HIP(s->und[i].alloc(c));
-  }
-  s->f_cap = c;
+  GS_HIP(grow_group(s->stream, s->f_cap, n, n + n / 4, [&](uint64_t c) {
+    const hipError_t e = alloc_each(2 * c, s->stage, s->ex, s->ey, s->px, s->py, s->pj);
+    return e != hipSuccess ? e : alloc_each(c, s->res, s->heavy, s->pidx, s->ps, s->pt, s->status[0], s->und[0],
+                                            s->status[1], s->und[1]);
+  }));
   return GS_OK;
 }
 
@@ -187,16 +162,14 @@ int query_impl(gs_spanner_s* s, const int64_t* src, const int64_t* dst, uint64_t
                uint8_t* out, uint64_t* nheavy) {
   const gs::SpGraph g = s->base();
   GS_HIP(hipMemsetAsync(s->ctl + gs::SP_HEAVY, 0, 8, s->stream));
-  gs::launch_sp_query(g, src, dst, n, stride, k, out, s->heavy, s->ctl, lds_set(), s->stream);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_sp_query(g, src, dst, n, stride, k, out, s->heavy, s->ctl, lds_set(), s->stream));
   unsigned long long h = 0;
   if (int rc = read_words(s, gs::SP_HEAVY, 1, &h)) return rc;
   if (h > n) return fail(GS_ERR_HIP, "spanner: heavy list longer than its launch");
   if (h) {
     gs::SpArenas ar;
     if (int rc = take_arenas(s, g.n0, h, &ar)) return rc;
-    gs::launch_sp_query_heavy(g, src, dst, n, stride, k, out, s->heavy, h, s->ctl, ar, s->stream);
-    GS_HIP(hipGetLastError());
+    GS_LAUNCH(gs::launch_sp_query_heavy(g, src, dst, n, stride, k, out, s->heavy, h, s->ctl, ar, s->stream));
     if (nheavy) *nheavy += h;
   }
   return GS_OK;
@@ -213,13 +186,10 @@ int fold_impl(gs_spanner_s* s, const int64_t* src, const int64_t* dst, uint64_t 
   // 1. the filter pass
   if (int rc = query_impl(s, src, dst, n, stride, k, s->res, &S[4])) return rc;
   // 2. the pending edges, in arrival order
-  gs::launch_sp_flag_pending(s->res, n, s->flags, s->blk, st);
-  GS_HIP(hipGetLastError());
-  gs::launch_tile_scan(s->blk, gs::sp_blocks(n), s->ctl + gs::SP_PEND, st);
-  GS_HIP(hipGetLastError());
-  gs::launch_sp_pending(src, dst, n, stride, s->flags, s->blk, s->pidx, s->ps, s->pt, s->ex, s->ey, s->und[0],
-                        s->f_cap, st);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_sp_flag_pending(s->res, n, s->flags, s->blk, st));
+  GS_LAUNCH(gs::launch_tile_scan(s->blk, gs::sp_blocks(n), s->ctl + gs::SP_PEND, st));
+  GS_LAUNCH(gs::launch_sp_pending(src, dst, n, stride, s->flags, s->blk, s->pidx, s->ps, s->pt, s->ex, s->ey, s->und[0],
+                                  s->f_cap, st));
   GS_HIP(hipMemsetAsync(s->res, 0, n, st));  // from here on: the accepted bytes
   unsigned long long np = 0;
   if (int rc = read_words(s, gs::SP_PEND, 1, &np)) return rc;
@@ -229,17 +199,9 @@ int fold_impl(gs_spanner_s* s, const int64_t* src, const int64_t* dst, uint64_t 
   if (np == 0) return check_err(s);
   // 3. their entries sorted by (x, y): by y, then stably by x
   const uint64_t ne = 2 * np;
-  uint32_t* const sctl = s->sort.ctl;
-  GS_HIP(hipMemsetAsync(sctl, 0, gs::kSortCtlWords * 4, st));
-  gs::launch_sort_digits(s->ex, s->ey, ne, sctl, st);  // rows 0..7: x, rows 8..15: y
-  GS_HIP(hipGetLastError());
   gs::SortSrc cur;
-  int side = 0;
-  if (int rc = sort_run(s->sort, s->ey, ne, sctl + gs::kSortPasses * gs::kSortRadix, nullptr, &cur, &side, st))
-    return rc;
-  if (int rc = sort_run(s->sort, s->ex, ne, sctl, nullptr, &cur, &side, st)) return rc;
-  gs::launch_sp_gather(cur.pay, s->ex, s->ey, ne, s->px, s->py, s->pj, st);
-  GS_HIP(hipGetLastError());
+  if (int rc = sort_by_pair(s->sort, s->ex, s->ey, ne, &cur, st)) return rc;
+  GS_LAUNCH(gs::launch_sp_gather(cur.pay, s->ex, s->ey, ne, s->px, s->py, s->pj, st));
   GS_HIP(hipMemsetAsync(s->status[0], 0, np, st));
   // 4. rounds
   gs::SpGraph g = s->base();
@@ -255,18 +217,16 @@ int fold_impl(gs_spanner_s* s, const int64_t* src, const int64_t* dst, uint64_t 
     GS_HIP(hipMemcpyAsync(s->status[sc ^ 1], s->status[sc], np, hipMemcpyDeviceToDevice, st));
     GS_HIP(hipMemsetAsync(s->ctl + gs::SP_HEAVY, 0, 16, st));
     g.status = s->status[sc];
-    gs::launch_sp_round(g, s->ps, s->pt, s->und[sc], und, k, s->status[sc ^ 1], s->und[sc ^ 1], s->heavy, s->ctl,
-                        lds_set(), st);
-    GS_HIP(hipGetLastError());
+    GS_LAUNCH(gs::launch_sp_round(g, s->ps, s->pt, s->und[sc], und, k, s->status[sc ^ 1], s->und[sc ^ 1], s->heavy,
+                                  s->ctl, lds_set(), st));
     unsigned long long w[2] = {0, 0};
     if (int rc = read_words(s, gs::SP_HEAVY, 2, w)) return rc;
     if (w[0] > und) return fail(GS_ERR_HIP, "spanner round: heavy list longer than its launch");
     if (w[0]) {
       gs::SpArenas ar;
       if (int rc = take_arenas(s, g.n0 + ne, 2 * w[0], &ar)) return rc;
-      gs::launch_sp_round_heavy(g, s->ps, s->pt, s->heavy, w[0], k, s->status[sc ^ 1], s->und[sc ^ 1], s->ctl, ar,
-                                st);
-      GS_HIP(hipGetLastError());
+      GS_LAUNCH(gs::launch_sp_round_heavy(g, s->ps, s->pt, s->heavy, w[0], k, s->status[sc ^ 1], s->und[sc ^ 1], s->ctl,
+                                          ar, st));
       if (int rc = read_words(s, gs::SP_UND, 1, w + 1)) return rc;
       S[4] += w[0];
     }
@@ -283,35 +243,28 @@ int fold_impl(gs_spanner_s* s, const int64_t* src, const int64_t* dst, uint64_t 
     gs::SpArenas ar;
     if (int rc = take_arenas(s, g.n0 + ne, und, &ar)) return rc;
     g.status = s->status[sc];
-    gs::launch_sp_tail(g, s->ps, s->pt, np, k, s->status[sc], s->ctl, ar, st);
-    GS_HIP(hipGetLastError());
+    GS_LAUNCH(gs::launch_sp_tail(g, s->ps, s->pt, np, k, s->status[sc], s->ctl, ar, st));
     S[3] = und;
   }
   // 6. the accepted edges: their bytes, their entries (in order already), the merge
   GS_HIP(hipMemsetAsync(s->ctl + gs::SP_ENT, 0, 16, st));
-  gs::launch_sp_mark(s->status[sc], s->pidx, np, s->res, s->ctl, st);
-  GS_HIP(hipGetLastError());
-  gs::launch_sp_flag_accepted(s->pj, s->status[sc], ne, s->flags, s->blk, st);
-  GS_HIP(hipGetLastError());
-  gs::launch_tile_scan(s->blk, gs::sp_blocks(ne), s->ctl + gs::SP_ENT, st);
-  GS_HIP(hipGetLastError());
-  gs::launch_sp_compact_pairs(s->px, s->py, ne, s->flags, s->blk, s->ex, s->ey, 2 * s->f_cap, st);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_sp_mark(s->status[sc], s->pidx, np, s->res, s->ctl, st));
+  GS_LAUNCH(gs::launch_sp_flag_accepted(s->pj, s->status[sc], ne, s->flags, s->blk, st));
+  GS_LAUNCH(gs::launch_tile_scan(s->blk, gs::sp_blocks(ne), s->ctl + gs::SP_ENT, st));
+  GS_LAUNCH(gs::launch_sp_compact_pairs(s->px, s->py, ne, s->flags, s->blk, s->ex, s->ey, 2 * s->f_cap, st));
   unsigned long long w[2] = {0, 0};
   if (int rc = read_words(s, gs::SP_ENT, 2, w)) return rc;
   const uint64_t nd = w[0], m = w[1];
   if (nd > ne || m > np || m == 0) return fail(GS_ERR_HIP, "spanner fold: accepted counts out of range");
   const int other = s->cur ^ 1;
   if (int rc = ensure_adj(s, other, s->entries + nd)) return rc;
-  gs::launch_sp_merge(s->ax[s->cur], s->ay[s->cur], s->entries, s->ex, s->ey, nd, s->ax[other], s->ay[other],
-                      s->acap[other], st);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_sp_merge(s->ax[s->cur], s->ay[s->cur], s->entries, s->ex, s->ey, nd, s->ax[other], s->ay[other],
+                                s->acap[other], st));
   s->cur = other;
   s->entries += nd;
   s->edges += m;
   GS_HIP(hipMemsetAsync(s->ctl + gs::SP_VERT, 0, 8, st));
-  gs::launch_sp_count_rows(s->ax[s->cur], s->entries, s->ctl + gs::SP_VERT, st);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_sp_count_rows(s->ax[s->cur], s->entries, s->ctl + gs::SP_VERT, st));
   unsigned long long rm = 0;
   if (int rc = read_words(s, gs::SP_ROWMAX, 1, &rm)) return rc;
   S[5] = rm;
@@ -327,22 +280,19 @@ int fold_guard(gs_spanner_s* s, const void* src, const void* dst, size_t n) {
 }
 
 int ensure_out(gs_spanner_s* s, uint64_t rows) {
-  if (s->o_cap >= rows) return GS_OK;
-  GS_HIP(hipStreamSynchronize(s->stream));
-  s->o_cap = 0;
-  const uint64_t c = rows + rows / 4;
-  GS_HIP(s->o_lo.alloc(c));
-  GS_HIP(s->o_hi.alloc(c));
-  s->o_cap = c;
+  GS_HIP(grow_group(s->stream, s->o_cap, rows, rows + rows / 4,
+                    [&](uint64_t c) { return alloc_each(c, s->o_lo, s->o_hi); }));
   return GS_OK;
 }
 
 // the edges ascending by (lo, hi): the entries with x <= y, in the adjacency's order
 int export_impl(gs_spanner_s* s, int64_t* lo, int64_t* hi, size_t cap, size_t* n, bool to_host) {
+  if (int rc = check_handle(s, kWhat)) return rc;
+  if (!n) return fail(GS_ERR_INVALID, "n is null");
+  DeviceGuard g(s->device);
   *n = s->edges;
   GS_HIP(hipStreamSynchronize(s->stream));
-  if (cap < s->edges)
-    return fail(GS_ERR_TRUNCATED, "output capacity " + std::to_string(cap) + " < " + std::to_string(s->edges));
+  if (cap < s->edges) return truncated(cap, s->edges);
   if (s->edges == 0) return GS_OK;
   if (!lo || !hi) return fail(GS_ERR_INVALID, "null arrays");
   if (int rc = ensure_flags(s, s->entries)) return rc;
@@ -352,19 +302,37 @@ int export_impl(gs_spanner_s* s, int64_t* lo, int64_t* hi, size_t cap, size_t* n
     dl = s->o_lo;
     dh = s->o_hi;
   }
-  gs::launch_sp_flag_edges(s->ax[s->cur], s->ay[s->cur], s->entries, s->flags, s->blk, s->stream);
-  GS_HIP(hipGetLastError());
-  gs::launch_tile_scan(s->blk, gs::sp_blocks(s->entries), s->ctl + gs::SP_ROWS, s->stream);
-  GS_HIP(hipGetLastError());
-  gs::launch_sp_compact_pairs(s->ax[s->cur], s->ay[s->cur], s->entries, s->flags, s->blk, dl, dh, s->edges,
-                              s->stream);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_sp_flag_edges(s->ax[s->cur], s->ay[s->cur], s->entries, s->flags, s->blk, s->stream));
+  GS_LAUNCH(gs::launch_tile_scan(s->blk, gs::sp_blocks(s->entries), s->ctl + gs::SP_ROWS, s->stream));
+  GS_LAUNCH(gs::launch_sp_compact_pairs(s->ax[s->cur], s->ay[s->cur], s->entries, s->flags, s->blk, dl, dh, s->edges,
+                                        s->stream));
   if (to_host) {
     GS_HIP(hipMemcpyAsync(lo, dl, s->edges * 8, hipMemcpyDeviceToHost, s->stream));
     GS_HIP(hipMemcpyAsync(hi, dh, s->edges * 8, hipMemcpyDeviceToHost, s->stream));
   }
   GS_HIP(hipStreamSynchronize(s->stream));
   return GS_OK;
+}
+
+// to_host: src, dst and out are host arrays (staged through s->stage, answered through s->res)
+int within_impl(gs_spanner s, const int64_t* src, const int64_t* dst, size_t n, int k, uint8_t* out, bool to_host) {
+  if (int rc = check_handle(s, kWhat)) return rc;
+  if (int rc = check_k(k)) return rc;
+  if (n && (!src || !dst || !out)) return fail(GS_ERR_INVALID, "null arrays");
+  if ((uint64_t)n > kSpMaxFold) return fail(GS_ERR_CAPACITY, "spanner: too many queries for one call");
+  if (n == 0) return GS_OK;
+  DeviceGuard g(s->device);
+  if (int rc = ensure_fold_scratch(s, n)) return rc;  // (the heavy list)
+  if (to_host) {
+    int64_t *ds = s->stage, *dd = s->stage + s->f_cap;
+    GS_HIP(hipMemcpyAsync(ds, src, n * 8, hipMemcpyHostToDevice, s->stream));
+    GS_HIP(hipMemcpyAsync(dd, dst, n * 8, hipMemcpyHostToDevice, s->stream));
+    src = ds;
+    dst = dd;
+  }
+  if (int rc = query_impl(s, src, dst, n, 1, k, to_host ? s->res.get() : out, nullptr)) return rc;
+  if (to_host) GS_HIP(hipMemcpyAsync(out, s->res, n, hipMemcpyDeviceToHost, s->stream));
+  return check_err(s);
 }
 
 }  // namespace
@@ -388,7 +356,7 @@ int gs_spanner_create(gs_spanner* out, int device, int k, uint64_t edge_hint) {
 }
 
 int gs_spanner_reset(gs_spanner s) {
-  if (int rc = check_sp(s)) return rc;
+  if (int rc = check_handle(s, kWhat)) return rc;
   DeviceGuard g(s->device);
   GS_HIP(hipMemsetAsync(s->ctl, 0, gs::SP_CTL_WORDS * 8, s->stream));
   s->entries = 0;
@@ -399,7 +367,7 @@ int gs_spanner_reset(gs_spanner s) {
 
 int gs_spanner_fold_device(gs_spanner s, const int64_t* src, const int64_t* dst, size_t n, uint8_t* accepted,
                            size_t stride) {
-  if (int rc = check_sp(s)) return rc;
+  if (int rc = check_handle(s, kWhat)) return rc;
   if (stride == 0 || stride > 0xFFFFFFFFull) return fail(GS_ERR_INVALID, "stride must be >= 1");
   if (int rc = fold_guard(s, src, dst, n)) return rc;
   if (n == 0) return GS_OK;
@@ -426,48 +394,28 @@ int fold_host(gs_spanner s, const int64_t* src, const int64_t* dst, size_t n, ui
 }  // namespace
 
 int gs_spanner_fold(gs_spanner s, const int64_t* src, const int64_t* dst, size_t n, uint8_t* accepted) {
-  if (int rc = check_sp(s)) return rc;
+  if (int rc = check_handle(s, kWhat)) return rc;
   return fold_host(s, src, dst, n, accepted, s->k);
 }
 
 // AdjacencyListGraph.addEdge over a batch: an edge joins G unless G holds it already, which is
 // the fold with k = 1 (within 1 edge = the edge, or the loop, is there).
 int gs_spanner_add(gs_spanner s, const int64_t* src, const int64_t* dst, size_t n) {
-  if (int rc = check_sp(s)) return rc;
+  if (int rc = check_handle(s, kWhat)) return rc;
   return fold_host(s, src, dst, n, nullptr, 1);
 }
 
 int gs_spanner_within_device(gs_spanner s, const int64_t* src, const int64_t* dst, size_t n, int k, uint8_t* out) {
-  if (int rc = check_sp(s)) return rc;
-  if (int rc = check_k(k)) return rc;
-  if (n && (!src || !dst || !out)) return fail(GS_ERR_INVALID, "null arrays");
-  if ((uint64_t)n > kSpMaxFold) return fail(GS_ERR_CAPACITY, "spanner: too many queries for one call");
-  if (n == 0) return GS_OK;
-  DeviceGuard g(s->device);
-  if (int rc = ensure_fold_scratch(s, n)) return rc;  // (the heavy list)
-  if (int rc = query_impl(s, src, dst, n, 1, k, out, nullptr)) return rc;
-  return check_err(s);
+  return within_impl(s, src, dst, n, k, out, false);
 }
 
 int gs_spanner_within(gs_spanner s, const int64_t* src, const int64_t* dst, size_t n, int k, uint8_t* out) {
-  if (int rc = check_sp(s)) return rc;
-  if (int rc = check_k(k)) return rc;
-  if (n && (!src || !dst || !out)) return fail(GS_ERR_INVALID, "null arrays");
-  if ((uint64_t)n > kSpMaxFold) return fail(GS_ERR_CAPACITY, "spanner: too many queries for one call");
-  if (n == 0) return GS_OK;
-  DeviceGuard g(s->device);
-  if (int rc = ensure_fold_scratch(s, n)) return rc;
-  int64_t *ds = s->stage, *dd = s->stage + s->f_cap;
-  GS_HIP(hipMemcpyAsync(ds, src, n * 8, hipMemcpyHostToDevice, s->stream));
-  GS_HIP(hipMemcpyAsync(dd, dst, n * 8, hipMemcpyHostToDevice, s->stream));
-  if (int rc = query_impl(s, ds, dd, n, 1, k, s->res, nullptr)) return rc;
-  GS_HIP(hipMemcpyAsync(out, s->res, n, hipMemcpyDeviceToHost, s->stream));
-  return check_err(s);
+  return within_impl(s, src, dst, n, k, out, true);
 }
 
 int gs_spanner_combine(gs_spanner into, gs_spanner from) {
-  if (int rc = check_sp(into)) return rc;
-  if (int rc = check_sp(from)) return rc;
+  if (int rc = check_handle(into, kWhat)) return rc;
+  if (int rc = check_handle(from, kWhat)) return rc;
   if (into->device != from->device) return fail(GS_ERR_INVALID, "spanner combine: handles on different devices");
   DeviceGuard g(into->device);
   const uint64_t m = from->edges;
@@ -483,7 +431,7 @@ int gs_spanner_combine(gs_spanner into, gs_spanner from) {
 }
 
 int gs_spanner_count(gs_spanner s, uint64_t* edges, uint64_t* vertices) {
-  if (int rc = check_sp(s)) return rc;
+  if (int rc = check_handle(s, kWhat)) return rc;
   if (!edges || !vertices) return fail(GS_ERR_INVALID, "null count pointers");
   DeviceGuard g(s->device);
   unsigned long long v = 0;
@@ -494,22 +442,16 @@ int gs_spanner_count(gs_spanner s, uint64_t* edges, uint64_t* vertices) {
 }
 
 int gs_spanner_export_device(gs_spanner s, int64_t* lo, int64_t* hi, size_t cap, size_t* n) {
-  if (int rc = check_sp(s)) return rc;
-  if (!n) return fail(GS_ERR_INVALID, "n is null");
-  DeviceGuard g(s->device);
   return export_impl(s, lo, hi, cap, n, false);
 }
 
 int gs_spanner_export(gs_spanner s, int64_t* lo, int64_t* hi, size_t cap, size_t* n) {
-  if (int rc = check_sp(s)) return rc;
-  if (!n) return fail(GS_ERR_INVALID, "n is null");
-  DeviceGuard g(s->device);
   return export_impl(s, lo, hi, cap, n, true);
 }
 
 int gs_spanner_neighbors(gs_spanner s, int64_t* v, uint64_t* offset, int64_t* neighbor, size_t cap_v, size_t cap_e,
                          size_t* nv, size_t* ne) {
-  if (int rc = check_sp(s)) return rc;
+  if (int rc = check_handle(s, kWhat)) return rc;
   if (!nv || !ne) return fail(GS_ERR_INVALID, "null count pointers");
   DeviceGuard g(s->device);
   unsigned long long verts = 0;
@@ -539,29 +481,14 @@ int gs_spanner_neighbors(gs_spanner s, int64_t* v, uint64_t* offset, int64_t* ne
   return GS_OK;
 }
 
-int gs_spanner_sync(gs_spanner s) {
-  if (int rc = check_sp(s)) return rc;
-  DeviceGuard g(s->device);
-  GS_HIP(hipStreamSynchronize(s->stream));
-  return GS_OK;
-}
-
-int gs_spanner_get_stream(gs_spanner s, void** stream) {
-  if (int rc = check_sp(s)) return rc;
-  if (!stream) return fail(GS_ERR_INVALID, "stream is null");
-  *stream = s->stream;
-  return GS_OK;
-}
-
-int gs_spanner_wait_stream(gs_spanner s, void* stream) {
-  if (int rc = check_sp(s)) return rc;
-  return s->wait_stream(stream);
-}
+int gs_spanner_sync(gs_spanner s) { return owner_sync(s, kWhat); }
+int gs_spanner_get_stream(gs_spanner s, void** stream) { return owner_get_stream(s, kWhat, stream); }
+int gs_spanner_wait_stream(gs_spanner s, void* stream) { return owner_wait_stream(s, kWhat, stream); }
 
 // gs_testing.h: the last fold. No device call.
 int gs_testing_spanner_stats(void* handle, uint64_t* out) {
   gs_spanner s = static_cast<gs_spanner>(handle);
-  if (int rc = check_sp(s)) return rc;
+  if (int rc = check_handle(s, kWhat)) return rc;
   if (!out) return fail(GS_ERR_INVALID, "out is null");
   for (int i = 0; i < 6; ++i) out[i] = s->stats[i];
   return GS_OK;

@@ -75,10 +75,7 @@ namespace {
 constexpr uint64_t kTriMaxEntries = 0xFFFFFFFFull;
 constexpr uint64_t kTriMinCap = 64;
 
-int check_tri(gs_triangles t) {
-  if (!t) return fail(GS_ERR_INVALID, "null triangle handle");
-  return GS_OK;
-}
+constexpr const char* kWhat = "triangle";  // check_handle: "null triangle handle"
 
 int count_variant() {
   const int64_t v = testing_value(GS_TESTING_TRIANGLE_VARIANT, gs::kTriangleProduct);
@@ -91,50 +88,32 @@ int alloc_table(gs_triangles_s* t, uint64_t cap) {
   GS_HIP(t->tab.alloc(cap + 1));
   t->cap = cap;
   t->logcap = log2_ceil(cap);
-  gs::launch_tri_init(t->table(), t->stream);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_tri_init(t->table(), t->stream));
   return GS_OK;
 }
 
 int ensure_adj(gs_triangles_s* t, int side, uint64_t need) {
-  if (t->acap[side] >= need) return GS_OK;
-  GS_HIP(hipStreamSynchronize(t->stream));
-  t->acap[side] = 0;
-  const uint64_t c = std::min<uint64_t>(kTriMaxEntries, need + need / 2);
-  GS_HIP(t->ax[side].alloc(c));
-  GS_HIP(t->ay[side].alloc(c));
-  GS_HIP(t->aseq[side].alloc(c));
-  t->acap[side] = c;
+  GS_HIP(grow_group(t->stream, t->acap[side], need, std::min<uint64_t>(kTriMaxEntries, need + need / 2),
+                    [&](uint64_t c) { return alloc_each(c, t->ax[side], t->ay[side], t->aseq[side]); }));
   return GS_OK;
 }
 
 int ensure_flags(gs_triangles_s* t, uint64_t n) {
-  if (t->g_cap >= n) return GS_OK;
-  GS_HIP(hipStreamSynchronize(t->stream));
-  t->g_cap = 0;
-  const uint64_t c = n + n / 4;
-  GS_HIP(t->flags.alloc(c));
-  GS_HIP(t->blk.alloc(gs::tri_blocks(c) + 1));
-  t->g_cap = c;
+  GS_HIP(grow_group(t->stream, t->g_cap, n, n + n / 4, [&](uint64_t c) {
+    const hipError_t e = t->flags.alloc(c);
+    return e != hipSuccess ? e : t->blk.alloc(gs::tri_blocks(c) + 1);
+  }));
   return GS_OK;
 }
 
 int ensure_fold_scratch(gs_triangles_s* t, uint64_t n) {
   if (int rc = ensure_flags(t, n)) return rc;
   if (int rc = sort_scratch_ensure(t->sort, n, t->stream)) return rc;
-  if (t->f_cap >= n) return GS_OK;
-  GS_HIP(hipStreamSynchronize(t->stream));
-  t->f_cap = 0;
-  const uint64_t c = gs::sort_blocks(n + n / 4) * gs::kSortTile;  // (the sort scratch's count)
-  GS_HIP(t->stage.alloc(2 * c));
-  GS_HIP(t->lo.alloc(c));
-  GS_HIP(t->hi.alloc(c));
-  GS_HIP(t->nx.alloc(c));
-  GS_HIP(t->ny.alloc(c));
-  GS_HIP(t->info.alloc(c));
-  GS_HIP(t->list1.alloc(c));
-  GS_HIP(t->list2.alloc(c));
-  t->f_cap = c;
+  // (the sort scratch's count)
+  GS_HIP(grow_group(t->stream, t->f_cap, n, gs::sort_blocks(n + n / 4) * gs::kSortTile, [&](uint64_t c) {
+    const hipError_t e = t->stage.alloc(2 * c);
+    return e != hipSuccess ? e : alloc_each(c, t->lo, t->hi, t->nx, t->ny, t->info, t->list1, t->list2);
+  }));
   return GS_OK;
 }
 
@@ -150,8 +129,7 @@ int grow_table(gs_triangles_s* t, uint64_t new_cap) {
     t->logcap = 64 - old.shift;
     return rc;
   }
-  gs::launch_tri_rehash(old, t->table(), t->adj(), t->stream);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_tri_rehash(old, t->table(), t->adj(), t->stream));
   GS_HIP(hipStreamSynchronize(t->stream));
   return GS_OK;
 }
@@ -166,32 +144,20 @@ int fold_impl(gs_triangles_s* t, const int64_t* src, const int64_t* dst, uint64_
   PhaseTimer timer(t->stream, testing_value(GS_TESTING_TRIANGLE_PROFILE, 0) == 1, t->phase_us, 4);
   timer.mark(0);
   // 1. canonise
-  gs::launch_tri_canon(src, dst, n, stride, t->lo, t->hi, t->stream);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_tri_canon(src, dst, n, stride, t->lo, t->hi, t->stream));
   timer.mark(1);
   // 2. sort by max, then stably by min; flag, scan, compact: N in (nx, ny)
   // (no digit is skipped: the histograms are on the device only)
-  uint32_t* const sctl = t->sort.ctl;
-  GS_HIP(hipMemsetAsync(sctl, 0, gs::kSortCtlWords * 4, t->stream));
-  gs::launch_sort_digits(t->lo, t->hi, n, sctl, t->stream);  // rows 0..7: min, rows 8..15: max
-  GS_HIP(hipGetLastError());
   gs::SortSrc cur;
-  int side = 0;
-  if (int rc = sort_run(t->sort, t->hi, n, sctl + gs::kSortPasses * gs::kSortRadix, nullptr, &cur, &side, t->stream))
-    return rc;
-  if (int rc = sort_run(t->sort, t->lo, n, sctl, nullptr, &cur, &side, t->stream)) return rc;
-  gs::launch_tri_flag_new(cur.pay, t->lo, t->hi, n, t->adj(), t->flags, t->blk, t->stream);
-  GS_HIP(hipGetLastError());
-  gs::launch_tile_scan(t->blk, gs::tri_blocks(n), t->ctl + gs::TRI_NEW, t->stream);
-  GS_HIP(hipGetLastError());
-  gs::launch_tri_compact_new(cur.pay, t->lo, t->hi, n, t->flags, t->blk, t->nx, t->ny, t->f_cap, t->stream);
-  GS_HIP(hipGetLastError());
+  if (int rc = sort_by_pair(t->sort, t->lo, t->hi, n, &cur, t->stream)) return rc;
+  GS_LAUNCH(gs::launch_tri_flag_new(cur.pay, t->lo, t->hi, n, t->adj(), t->flags, t->blk, t->stream));
+  GS_LAUNCH(gs::launch_tile_scan(t->blk, gs::tri_blocks(n), t->ctl + gs::TRI_NEW, t->stream));
+  GS_LAUNCH(gs::launch_tri_compact_new(cur.pay, t->lo, t->hi, n, t->flags, t->blk, t->nx, t->ny, t->f_cap, t->stream));
   // the fold's one host synchronisation: |N|, the vertex count, the digit histograms of max
   unsigned long long words[4] = {0, 0, 0, 0};
   std::vector<uint32_t> hist(gs::kSortPasses * gs::kSortRadix);
   GS_HIP(hipMemcpyAsync(words, t->ctl, sizeof(words), hipMemcpyDeviceToHost, t->stream));
-  GS_HIP(hipMemcpyAsync(hist.data(), sctl + gs::kSortPasses * gs::kSortRadix, hist.size() * 4,
-                        hipMemcpyDeviceToHost, t->stream));
+  GS_HIP(hipMemcpyAsync(hist.data(), t->sort.hist(1), hist.size() * 4, hipMemcpyDeviceToHost, t->stream));
   timer.mark(2);
   GS_HIP(hipStreamSynchronize(t->stream));
   const uint64_t m = words[gs::TRI_NEW], nv = words[gs::TRI_NV];
@@ -212,21 +178,19 @@ int fold_impl(gs_triangles_s* t, const int64_t* src, const int64_t* dst, uint64_
   // fold agrees is an identity pass for N's subset of them.
   bool skip[gs::kSortPasses];
   sort_skip_digits(hist.data(), n, skip);
+  uint32_t* const sctl = t->sort.ctl;
   GS_HIP(hipMemsetAsync(sctl, 0, gs::kSortCtlWords * 4, t->stream));
-  gs::launch_sort_digits(t->ny, t->ny, m, sctl, t->stream);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_sort_digits(t->ny, t->ny, m, sctl, t->stream));
   cur = gs::SortSrc();
-  side = 0;
+  int side = 0;
   if (int rc = sort_run(t->sort, t->ny, m, sctl, skip, &cur, &side, t->stream)) return rc;
-  gs::launch_tri_reverse(cur.pay, t->nx, t->ny, m, t->lo, t->hi, t->stream);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_tri_reverse(cur.pay, t->nx, t->ny, m, t->lo, t->hi, t->stream));
   gs::TriAdjOut out;
   out.x = t->ax[other];
   out.y = t->ay[other];
   out.seq = t->aseq[other];
   out.cap = t->acap[other];
-  gs::launch_tri_merge(t->adj(), t->nx, t->ny, t->lo, t->hi, m, out, t->seq, t->stream);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_tri_merge(t->adj(), t->nx, t->ny, t->lo, t->hi, m, out, t->seq, t->stream));
   t->cur = other;
   t->entries += 2 * m;
   t->edges += m;
@@ -234,11 +198,10 @@ int fold_impl(gs_triangles_s* t, const int64_t* src, const int64_t* dst, uint64_
   // 4. rows and count
   const int variant = count_variant();
   GS_HIP(hipMemsetAsync(t->ctl + gs::TRI_BIN1, 0, 16, t->stream));
-  gs::launch_tri_rows(t->table(), t->ctl, t->adj(), t->nx, t->ny, m, t->info, t->list1, t->list2, variant, t->stream);
-  GS_HIP(hipGetLastError());
-  gs::launch_tri_count(t->table(), t->ctl, t->adj(), t->nx, t->ny, m, t->info, t->list1, t->list2, t->seq, variant,
-                       t->stream);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_tri_rows(t->table(), t->ctl, t->adj(), t->nx, t->ny, m, t->info, t->list1, t->list2, variant,
+                                t->stream));
+  GS_LAUNCH(gs::launch_tri_count(t->table(), t->ctl, t->adj(), t->nx, t->ny, m, t->info, t->list1, t->list2, t->seq,
+                                 variant, t->stream));
   timer.mark(4);
   timer.finish();
   return GS_OK;
@@ -253,6 +216,9 @@ int fold_guard(gs_triangles_s* t, const void* src, const void* dst, size_t n) {
 }
 
 int export_impl(gs_triangles_s* t, int64_t* v, int64_t* count, size_t cap, size_t* n, int nonzero_only, bool to_host) {
+  if (int rc = check_handle(t, kWhat)) return rc;
+  if (!n) return fail(GS_ERR_INVALID, "n is null");
+  DeviceGuard g(t->device);
   *n = 0;
   if (t->entries == 0) {
     GS_HIP(hipStreamSynchronize(t->stream));
@@ -260,32 +226,27 @@ int export_impl(gs_triangles_s* t, int64_t* v, int64_t* count, size_t cap, size_
   }
   if (int rc = ensure_flags(t, t->entries)) return rc;
   const gs::TriAdj A = t->adj();
-  gs::launch_tri_flag_heads(t->table(), t->ctl, A, nonzero_only ? 1 : 0, t->flags, t->blk, t->stream);
-  GS_HIP(hipGetLastError());
-  gs::launch_tile_scan(t->blk, gs::tri_blocks(A.n), t->ctl + gs::TRI_ROWS, t->stream);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_tri_flag_heads(t->table(), t->ctl, A, nonzero_only ? 1 : 0, t->flags, t->blk, t->stream));
+  GS_LAUNCH(gs::launch_tile_scan(t->blk, gs::tri_blocks(A.n), t->ctl + gs::TRI_ROWS, t->stream));
   unsigned long long rows = 0;
   GS_HIP(hipMemcpyAsync(&rows, t->ctl + gs::TRI_ROWS, 8, hipMemcpyDeviceToHost, t->stream));
   GS_HIP(hipStreamSynchronize(t->stream));
   *n = rows;
-  if (cap < rows)
-    return fail(GS_ERR_TRUNCATED, "output capacity " + std::to_string(cap) + " < " + std::to_string(rows));
+  if (cap < rows) return truncated(cap, rows);
   if (rows == 0) return GS_OK;
   if (!v || !count) return fail(GS_ERR_INVALID, "null arrays");
   int64_t *dv = v, *dc = count;
   if (to_host) {
-    if (t->o_cap < rows) {
+    if (t->o_cap < rows) {  // (not grow_group: the stream is idle, the wait for `rows` above)
       t->o_cap = 0;
       const uint64_t c = rows + rows / 4;
-      GS_HIP(t->o_v.alloc(c));
-      GS_HIP(t->o_c.alloc(c));
+      GS_HIP(alloc_each(c, t->o_v, t->o_c));
       t->o_cap = c;
     }
     dv = t->o_v;
     dc = t->o_c;
   }
-  gs::launch_tri_compact_rows(t->table(), t->ctl, A, t->flags, t->blk, dv, dc, rows, t->stream);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_tri_compact_rows(t->table(), t->ctl, A, t->flags, t->blk, dv, dc, rows, t->stream));
   if (to_host) {
     GS_HIP(hipMemcpyAsync(v, dv, rows * 8, hipMemcpyDeviceToHost, t->stream));
     GS_HIP(hipMemcpyAsync(count, dc, rows * 8, hipMemcpyDeviceToHost, t->stream));
@@ -317,10 +278,9 @@ int gs_triangle_create(gs_triangles* out, int device, uint64_t edge_hint) {
 }
 
 int gs_triangle_reset(gs_triangles t) {
-  if (int rc = check_tri(t)) return rc;
+  if (int rc = check_handle(t, kWhat)) return rc;
   DeviceGuard g(t->device);
-  gs::launch_tri_init(t->table(), t->stream);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_tri_init(t->table(), t->stream));
   GS_HIP(hipMemsetAsync(t->ctr, 0, (size_t)gs::CTR_COUNT * gs::kCtrStride * 4, t->stream));
   GS_HIP(hipMemsetAsync(t->ctl, 0, gs::TRI_CTL_WORDS * 8, t->stream));
   t->entries = 0;
@@ -329,7 +289,7 @@ int gs_triangle_reset(gs_triangles t) {
 }
 
 int gs_triangle_fold_device(gs_triangles t, const int64_t* src, const int64_t* dst, size_t n, size_t stride) {
-  if (int rc = check_tri(t)) return rc;
+  if (int rc = check_handle(t, kWhat)) return rc;
   if (stride == 0 || stride > 0xFFFFFFFFull) return fail(GS_ERR_INVALID, "stride must be >= 1");
   if (int rc = fold_guard(t, src, dst, n)) return rc;
   if (n == 0) return GS_OK;
@@ -338,7 +298,7 @@ int gs_triangle_fold_device(gs_triangles t, const int64_t* src, const int64_t* d
 }
 
 int gs_triangle_fold(gs_triangles t, const int64_t* src, const int64_t* dst, size_t n) {
-  if (int rc = check_tri(t)) return rc;
+  if (int rc = check_handle(t, kWhat)) return rc;
   if (int rc = fold_guard(t, src, dst, n)) return rc;
   if (n == 0) return GS_OK;
   DeviceGuard g(t->device);
@@ -352,7 +312,7 @@ int gs_triangle_fold(gs_triangles t, const int64_t* src, const int64_t* dst, siz
 }
 
 int gs_triangle_count(gs_triangles t, uint64_t* triangles, uint64_t* edges, uint64_t* vertices) {
-  if (int rc = check_tri(t)) return rc;
+  if (int rc = check_handle(t, kWhat)) return rc;
   if (!triangles || !edges || !vertices) return fail(GS_ERR_INVALID, "null count pointers");
   DeviceGuard g(t->device);
   unsigned long long w[3] = {0, 0, 0};
@@ -365,7 +325,7 @@ int gs_triangle_count(gs_triangles t, uint64_t* triangles, uint64_t* edges, uint
 }
 
 int gs_triangle_count_device(gs_triangles t, uint64_t* out) {
-  if (int rc = check_tri(t)) return rc;
+  if (int rc = check_handle(t, kWhat)) return rc;
   if (!out) return fail(GS_ERR_INVALID, "out is null");
   DeviceGuard g(t->device);
   GS_HIP(hipMemcpyAsync(out, t->ctl, 24, hipMemcpyDeviceToDevice, t->stream));
@@ -373,53 +333,31 @@ int gs_triangle_count_device(gs_triangles t, uint64_t* out) {
 }
 
 int gs_triangle_find_device(gs_triangles t, const int64_t* v, size_t n, int64_t* count, uint8_t* found) {
-  if (int rc = check_tri(t)) return rc;
+  if (int rc = check_handle(t, kWhat)) return rc;
   if (n && (!v || !count)) return fail(GS_ERR_INVALID, "null arrays");
   DeviceGuard g(t->device);
-  gs::launch_tri_find(t->table(), t->ctl, v, n, count, found, t->stream);
-  GS_HIP(hipGetLastError());
+  GS_LAUNCH(gs::launch_tri_find(t->table(), t->ctl, v, n, count, found, t->stream));
   return GS_OK;
 }
 
 int gs_triangle_export_device(gs_triangles t, int64_t* v, int64_t* count, size_t cap, size_t* n, int nonzero_only) {
-  if (int rc = check_tri(t)) return rc;
-  if (!n) return fail(GS_ERR_INVALID, "n is null");
-  DeviceGuard g(t->device);
   return export_impl(t, v, count, cap, n, nonzero_only, false);
 }
 
 int gs_triangle_export(gs_triangles t, int64_t* v, int64_t* count, size_t cap, size_t* n, int nonzero_only) {
-  if (int rc = check_tri(t)) return rc;
-  if (!n) return fail(GS_ERR_INVALID, "n is null");
-  DeviceGuard g(t->device);
   return export_impl(t, v, count, cap, n, nonzero_only, true);
 }
 
-int gs_triangle_sync(gs_triangles t) {
-  if (int rc = check_tri(t)) return rc;
-  DeviceGuard g(t->device);
-  GS_HIP(hipStreamSynchronize(t->stream));
-  return GS_OK;
-}
-
-int gs_triangle_get_stream(gs_triangles t, void** stream) {
-  if (int rc = check_tri(t)) return rc;
-  if (!stream) return fail(GS_ERR_INVALID, "stream is null");
-  *stream = t->stream;
-  return GS_OK;
-}
-
-int gs_triangle_wait_stream(gs_triangles t, void* stream) {
-  if (int rc = check_tri(t)) return rc;
-  return t->wait_stream(stream);
-}
+int gs_triangle_sync(gs_triangles t) { return owner_sync(t, kWhat); }
+int gs_triangle_get_stream(gs_triangles t, void** stream) { return owner_get_stream(t, kWhat, stream); }
+int gs_triangle_wait_stream(gs_triangles t, void* stream) { return owner_wait_stream(t, kWhat, stream); }
 
 // gs_testing.h: out[0] = intersection steps since reset, out[1] = the longest row a new edge
 // met, out[2..5] = microseconds of the last profiled fold's canonise / sort and dedup / merge
 // / count phases. Synchronises.
 int gs_testing_triangle_stats(void* handle, uint64_t* out) {
   gs_triangles t = static_cast<gs_triangles>(handle);
-  if (int rc = check_tri(t)) return rc;
+  if (int rc = check_handle(t, kWhat)) return rc;
   if (!out) return fail(GS_ERR_INVALID, "out is null");
   DeviceGuard g(t->device);
   unsigned long long w[2] = {0, 0};
@@ -435,7 +373,7 @@ int gs_testing_triangle_stats(void* handle, uint64_t* out) {
 // last fold that had new edges (both 0 under the wave variant and after reset). Synchronises.
 int gs_testing_triangle_bins(void* handle, uint64_t* out) {
   gs_triangles t = static_cast<gs_triangles>(handle);
-  if (int rc = check_tri(t)) return rc;
+  if (int rc = check_handle(t, kWhat)) return rc;
   if (!out) return fail(GS_ERR_INVALID, "out is null");
   DeviceGuard g(t->device);
   static_assert(gs::TRI_BIN2 == gs::TRI_BIN1 + 1, "the two list lengths are adjacent words");
