@@ -91,6 +91,10 @@ EXPORTED_SYMBOLS = (
     "gs_matching_events", "gs_matching_events_device", "gs_matching_count", "gs_matching_export",
     "gs_matching_export_device", "gs_matching_mate_device", "gs_matching_sync", "gs_matching_get_stream",
     "gs_matching_wait_stream", "gs_testing_matching_stats", "gs_testing_matching_tune",
+    "gs_trisample_create", "gs_trisample_destroy", "gs_trisample_reset", "gs_trisample_fold", "gs_trisample_fold_device",
+    "gs_trisample_rows", "gs_trisample_rows_device", "gs_trisample_estimate", "gs_trisample_states",
+    "gs_trisample_states_device", "gs_trisample_sync", "gs_trisample_get_stream", "gs_trisample_wait_stream",
+    "gs_testing_trisample_stats", "gs_testing_trisample_tune",
 )
 
 # Pairs per workgroup of the component export's radix-sort kernels (csrc/gs_sort.hpp kSortTile):
@@ -160,6 +164,17 @@ MATCHING_ITER_CAP = 6
 MATCHING_SAFE_BITS = 61
 MATCHING_TILE = 1024
 MATCHING_EVENTS = {"add": 0, "remove": 1}  # gs_matching_event
+
+# The sampling triangle estimate (csrc/gs_trisample_seq.hpp): arrivals per workgroup of the coin
+# pass and of the search pass, the limits of a handle, the reference's master seed (the Java int
+# literal 0xDEADBEEF, widened) and the arrivals of one device fold (longer ones are cut).
+TRISAMPLE_CHUNK = 256
+TRISAMPLE_TILE = 1024
+TRISAMPLE_MAX_SAMPLES = 1 << 20
+TRISAMPLE_MAX_VERTICES = (1 << 31) - 1
+TRISAMPLE_MAX_ARRIVALS = (1 << 31) - 1
+TRISAMPLE_SEED = -559038737
+TRISAMPLE_MAX_FOLD = 1 << 20
 
 FAIL_BIT = 1 << 62  # count words: a failed signed verdict (GS_FAIL_BIT)
 DIGEST_FAILED = (1 << 64) - 1  # gs_digest of a signed summary whose verdict failed (GS_DIGEST_FAILED)
@@ -373,6 +388,22 @@ def lib():
     L.gs_matching_wait_stream.argtypes = [_vp, _vp]
     L.gs_testing_matching_stats.argtypes = [_vp, ctypes.POINTER(_u64)]
     L.gs_testing_matching_tune.argtypes = [_vp, ctypes.c_int, ctypes.c_int64]
+    L.gs_trisample_create.argtypes = [ctypes.POINTER(_vp), ctypes.c_int, _u64, ctypes.c_int64, ctypes.c_int64, _u64]
+    L.gs_trisample_destroy.argtypes = [_vp]
+    L.gs_trisample_reset.argtypes = [_vp]
+    L.gs_trisample_fold.argtypes = [_vp, _vp, _vp, _sz, ctypes.POINTER(_sz)]
+    L.gs_trisample_fold_device.argtypes = [_vp, _vp, _vp, _sz, _sz, ctypes.POINTER(_sz)]
+    L.gs_trisample_rows.argtypes = [_vp, _vp, _vp, _vp, _sz, ctypes.POINTER(_sz)]
+    L.gs_trisample_rows_device.argtypes = [_vp, _vp, _vp, _vp, _sz, ctypes.POINTER(_sz)]
+    L.gs_trisample_estimate.argtypes = [_vp, ctypes.POINTER(_u64), ctypes.POINTER(ctypes.c_int32),
+                                        ctypes.POINTER(ctypes.c_int32)]
+    L.gs_trisample_states.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp]
+    L.gs_trisample_states_device.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp]
+    L.gs_trisample_sync.argtypes = [_vp]
+    L.gs_trisample_get_stream.argtypes = [_vp, ctypes.POINTER(_vp)]
+    L.gs_trisample_wait_stream.argtypes = [_vp, _vp]
+    L.gs_testing_trisample_stats.argtypes = [_vp, ctypes.POINTER(_u64)]
+    L.gs_testing_trisample_tune.argtypes = [_vp, ctypes.c_int, ctypes.c_int64]
     L.gs_testing_set.argtypes = [ctypes.c_int, _i64]
     L.gs_testing_get.argtypes = [ctypes.c_int]
     L.gs_testing_get.restype = _i64
@@ -1600,6 +1631,116 @@ class Matching(_ResetHandle):
             _check(lib().gs_testing_matching_tune(self._h, 1, int(iter_cap)))
         if sharpen is not None:
             _check(lib().gs_testing_matching_tune(self._h, 2, -1 if sharpen else 1))
+
+
+# ---------------------------------------------------------------- sampling triangle estimate
+class TriangleSampler(_ResetHandle):
+    """The sampling triangle estimate of example/BroadcastTriangleCount.java at parallelism 1 with
+    the seeded coin of example/IncidenceSamplingTriangleCount.java (the gs_trisample_* section of
+    include/gs_summary.h): `samples` instances each keep one candidate (src, trg, third), resampled
+    at arrival t with probability 1/t by a coin that is exact to java.util.Random; the rows are
+    (edge count, estimate, betaSum) whenever the estimate changes, the same however the stream is
+    cut into folds. `reset`: no arrival folded, the generators reseeded; capacity and tuning are
+    kept. Owns a gs_trisample handle."""
+
+    _PREFIX = "gs_trisample"
+
+    def __init__(self, samples=10000, vertices=1000, seed=-559038737, third_seed=0, device=0):
+        self.device = device
+        self.samples = int(samples)
+        h = _vp()
+        _check(lib().gs_trisample_create(ctypes.byref(h), device, int(samples), int(vertices), int(seed),
+                                         int(third_seed) & ((1 << 64) - 1)))
+        self._h = h
+
+    def fold(self, src, dst):
+        """Fold host arrivals (int64 arrays) in order; returns the fold's row count."""
+        s, d = _edges(src, dst)
+        rows = _sz()
+        _check(lib().gs_trisample_fold(self._h, s.ctypes.data, d.ctypes.data, len(s), ctypes.byref(rows)))
+        return rows.value
+
+    def fold_device(self, src, dst, n=None, stride=1, after=None):
+        """Fold device-resident arrivals (torch tensors on this device or raw pointers), element i
+        at index i * stride; `after`: a stream the arrays were written on. The fold synchronises
+        with the host; returns the fold's row count."""
+        if n is None:
+            n = (src.numel() + stride - 1) // stride
+        if after is not None:
+            self.wait_stream(after)
+        rows = _sz()
+        _check(lib().gs_trisample_fold_device(self._h, _ptr(src), _ptr(dst), int(n), int(stride), ctypes.byref(rows)))
+        return rows.value
+
+    def rows(self):
+        """The last fold's rows as numpy int32 arrays (edges, estimate, beta_sum)."""
+        got = _sz()
+        rc = lib().gs_trisample_rows(self._h, None, None, None, 0, ctypes.byref(got))
+        if rc != GS_ERR_TRUNCATED:  # (the row count of a fold with rows)
+            _check(rc)
+        n = max(got.value, 1)
+        e, est, b = (np.empty(n, np.int32) for _ in range(3))
+        _check(lib().gs_trisample_rows(self._h, e.ctypes.data, est.ctypes.data, b.ctypes.data, n, ctypes.byref(got)))
+        k = got.value
+        return e[:k].copy(), est[:k].copy(), b[:k].copy()
+
+    def rows_device(self, edges, estimate, beta_sum):
+        """The same rows into DEVICE int32 arrays (capacity of the first one given; any may be
+        None); returns the row count."""
+        got = _sz()
+        first = next(x for x in (edges, estimate, beta_sum) if x is not None)
+        cap = first.numel() if hasattr(first, "numel") else len(first)
+        _check(lib().gs_trisample_rows_device(self._h, _ptr(edges), _ptr(estimate), _ptr(beta_sum), cap,
+                                              ctypes.byref(got)))
+        return got.value
+
+    def estimate(self):
+        """(arrivals folded, betaSum now, the last emitted estimate). No device call."""
+        a, b, e = _u64(), ctypes.c_int32(), ctypes.c_int32()
+        _check(lib().gs_trisample_estimate(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(e)))
+        return a.value, b.value, e.value
+
+    def states(self):
+        """Every instance's candidate as numpy arrays (src, trg, third int64, flags uint8 -- bit 0
+        srcEdgeFound, bit 1 trgEdgeFound, bit 2 beta --, sampled_at int32)."""
+        s, t, th = (np.empty(self.samples, np.int64) for _ in range(3))
+        f = np.empty(self.samples, np.uint8)
+        at = np.empty(self.samples, np.int32)
+        _check(lib().gs_trisample_states(self._h, s.ctypes.data, t.ctypes.data, th.ctypes.data, f.ctypes.data,
+                                         at.ctypes.data))
+        return s, t, th, f, at
+
+    def states_device(self, src, trg, third, flags, sampled_at):
+        """The same columns into DEVICE arrays of `samples` elements (any may be None); queued on
+        self.stream."""
+        _check(lib().gs_trisample_states_device(self._h, _ptr(src), _ptr(trg), _ptr(third), _ptr(flags),
+                                                _ptr(sampled_at)))
+
+    def stats(self):
+        """gs_testing_trisample_stats: the last fold."""
+        return self.phases()[0]
+
+    def phases(self):
+        """(stats, microseconds of the last fold's coin pass, sort and segments, search pass,
+        outcomes and rows): the times are zero unless tune(profile=True)."""
+        out = (_u64 * 8)()
+        _check(lib().gs_testing_trisample_stats(self._h, out))
+        return ({"coins": out[0], "segments": out[1], "max_attempts": out[2], "rows": out[3]},
+                {"coin": out[4], "segments": out[5], "search": out[6], "rows": out[7]})
+
+    def tune(self, chunk=None, tile=None, profile=None, keys=None):
+        """gs_testing_trisample_tune, per handle: the arrivals per workgroup of the coin pass and
+        of the search pass (at most TRISAMPLE_TILE), whether a fold times its phases, and the most
+        keys the resample list is first sized for. A value <= 0 restores the product value; None
+        leaves a control as it is."""
+        if keys is not None:
+            _check(lib().gs_testing_trisample_tune(self._h, 3, int(keys)))
+        if profile is not None:
+            _check(lib().gs_testing_trisample_tune(self._h, 2, 1 if profile else -1))
+        if chunk is not None:
+            _check(lib().gs_testing_trisample_tune(self._h, 0, int(chunk)))
+        if tile is not None:
+            _check(lib().gs_testing_trisample_tune(self._h, 1, int(tile)))
 
 
 # ---------------------------------------------------------------- native multi-GPU group

@@ -22,6 +22,7 @@
 //   BipartitenessCheck          library/BipartitenessCheck.java:37-133
 //   AdjacencyListGraph          summaries/AdjacencyListGraph.java:27-140 (GPU-resident adjacency)
 //   Spanner                     library/Spanner.java:40-118
+//   BroadcastTriangleCount      example/BroadcastTriangleCount.java:41-174 (S sampler instances on the GPU)
 //
 // Summaries are held by std::shared_ptr (Java object references). A GPU-backed
 // summary buffers its per-edge callbacks (union / merge of a one-edge candidate)
@@ -1370,6 +1371,82 @@ class CentralizedWeightedMatching {
 
  private:
   gs_matching h_ = nullptr;
+};
+
+// ---------------------------------------------------------------------------
+// sampling triangle estimate (gs_summary.h, the gs_trisample_* section)
+// ---------------------------------------------------------------------------
+// TriangleEstimate (util/TriangleEstimate.java:23-44): a Tuple3 (f0 = source subtask,
+// f1 = edge count, f2 = beta sum)
+struct TriangleEstimate {
+  int f0 = 0, f1 = 0, f2 = 0;
+  TriangleEstimate() = default;
+  TriangleEstimate(int source, int edges, int beta) : f0(source), f1(edges), f2(beta) {}
+  int getSource() const { return f0; }
+  int getEdgeCount() const { return f1; }
+  int getBeta() const { return f2; }
+};
+
+// BroadcastTriangleCount (example/BroadcastTriangleCount.java:41-174): TriangleSampler and
+// TriangleSummer at parallelism 1 over the edge stream, the coin seeded as in
+// example/IncidenceSamplingTriangleCount.java. The instances live on the device; `batch` arrivals
+// are folded per call, with the same rows whatever the batch size.
+class BroadcastTriangleCount {
+ public:
+  static constexpr int64_t kSeed = -559038737;  // new Random(0xDEADBEEF)
+  explicit BroadcastTriangleCount(int samples = 10000, int vertexCount = 1000, int device = 0, int64_t seed = kSeed,
+                                  uint64_t thirdSeed = 0) {
+    gs_check(gs_trisample_create(&h_, device, (uint64_t)(samples < 0 ? 0 : samples), vertexCount, seed, thirdSeed));
+  }
+  ~BroadcastTriangleCount() { gs_trisample_destroy(h_); }
+  BroadcastTriangleCount(const BroadcastTriangleCount&) = delete;
+  BroadcastTriangleCount& operator=(const BroadcastTriangleCount&) = delete;
+
+  // the (edge count, estimate) tuples TriangleSummer collects (:155-172), in order
+  template <typename K, typename EV>
+  std::vector<std::pair<int, int>> run(const EdgeStream<K, EV>& stream, size_t batch = 1 << 16) {
+    std::vector<std::pair<int, int>> out;
+    if (batch == 0) batch = 1;
+    const size_t n = stream.edges.size();
+    std::vector<int64_t> s, d;
+    std::vector<int32_t> edges, estimate;
+    sampler_.clear();
+    for (size_t at = 0; at < n; at += batch) {
+      const size_t len = std::min(batch, n - at);
+      s.resize(len);
+      d.resize(len);
+      for (size_t i = 0; i < len; ++i) {
+        s[i] = (int64_t)stream.edges[at + i].getSource();
+        d[i] = (int64_t)stream.edges[at + i].getTarget();
+      }
+      size_t rows = 0;
+      gs_check(gs_trisample_fold(h_, s.data(), d.data(), len, &rows));
+      if (rows == 0) continue;
+      edges.resize(rows);
+      estimate.resize(rows);
+      std::vector<int32_t> beta(rows);
+      gs_check(gs_trisample_rows(h_, edges.data(), estimate.data(), beta.data(), rows, &rows));
+      for (size_t r = 0; r < rows; ++r) {
+        out.push_back({edges[r], estimate[r]});
+        sampler_.push_back(TriangleEstimate(0, edges[r], beta[r]));
+      }
+    }
+    return out;
+  }
+  // the TriangleEstimates behind the last run's rows (source subtask 0)
+  const std::vector<TriangleEstimate>& estimates() const { return sampler_; }
+  // (arrivals folded, beta sum now, last emitted estimate)
+  std::tuple<uint64_t, int, int> estimate() const {
+    uint64_t arrivals = 0;
+    int32_t beta = 0, est = 0;
+    gs_check(gs_trisample_estimate(h_, &arrivals, &beta, &est));
+    return {arrivals, beta, est};
+  }
+  gs_trisample handle() const { return h_; }
+
+ private:
+  gs_trisample h_ = nullptr;
+  std::vector<TriangleEstimate> sampler_;
 };
 
 }  // namespace gelly

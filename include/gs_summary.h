@@ -802,6 +802,78 @@ int gs_matching_sync(gs_matching m);
 int gs_matching_get_stream(gs_matching m, void** stream);
 int gs_matching_wait_stream(gs_matching m, void* stream);
 
+/* ---- sampling triangle estimate ------------------------------------------------
+ * example/BroadcastTriangleCount.java (TriangleSampler and TriangleSummer at parallelism 1,
+ * util/TriangleEstimate.java) with the seeded coin of example/IncidenceSamplingTriangleCount.java
+ * (EdgeSampleMapper, util/SampledEdge.java): `samples` instances, each holding one candidate
+ * (src, trg, third). For arrival number t (from 1) and every instance i:
+ *   coin     nextDouble() * (double)t <= 1.0 on the instance's own java.util.Random, exact to the
+ *            documented 48-bit LCG; the instance seeds are (long) master.nextInt() of
+ *            new Random(seed), drawn in instance order. One nextDouble per instance and arrival,
+ *            so the coin is a function of (seed, i, t); it is always true at t = 1.
+ *   sample   on success the candidate becomes (src, trg, third) and its flags are cleared. The
+ *            reference draws third from the unseeded Math.random(); here it is counter-based:
+ *            h = mix64(mix64(third_seed + 0x9E3779B97F4A7C15 * (i + 1)) ^ t), attempt a = 0, 1, ..:
+ *            third = floor((mix64(h ^ a) >> 11) * 2^-53 * vertices), the first one that differs
+ *            from src and trg (mix64: the finaliser of gs_gen.h's generators).
+ *   observe  while beta == 0 the arrival is compared in either direction with {src, third} and
+ *            {trg, third}; beta = 1 once both were seen. Ids outside [0, vertices) never match a
+ *            third vertex.
+ *   rows     betaSum(t) = the instances with beta == 1 after arrival t. A row (t, estimate,
+ *            betaSum) is emitted at t iff betaSum(t) != betaSum(t - 1) and its estimate differs
+ *            from the estimate at the previous arrival whose betaSum changed (0 before any) --
+ *            the two previousResult fields of the reference. estimate =
+ *            (int)((((1.0 / samples) * betaSum) * t) * (vertices - 2)) in double, left to right,
+ *            cast as Java casts (truncate, saturate, NaN -> 0).
+ * The result of folding a stream does not depend on where it is cut into folds. The work of a fold
+ * is instances x arrivals: a coin pass and a search pass on the device.
+ *
+ * Synchronisation: a fold waits for the handle's stream twice (the count of coin successes, the
+ * fold's counts). Every allocation is counted by gs_hbm_bytes and released by
+ * gs_trisample_destroy. Null handles and pointers return GS_ERR_INVALID before any device call.
+ *
+ * gs_trisample_create: samples in 1 .. 2^20, vertices in 3 .. 2^31 - 1 (else GS_ERR_INVALID); seed
+ *   is a Java long (the reference's is the int literal 0xDEADBEEF widened, -559038737).
+ * gs_trisample_reset: no arrival folded, every candidate cleared, the generators reseeded.
+ * gs_trisample_fold / _fold_device: n arrivals from HOST arrays (copied before the call returns) /
+ *   DEVICE arrays read on the handle's stream, element i at index i * stride; *rows (may be NULL)
+ *   = the fold's row count. More than 2^31 - 1 arrivals in total: GS_ERR_INVALID, state untouched.
+ *   A fold of more than 2^20 arrivals is cut into pieces by the library, with the same result; its
+ *   rows are then not kept (gs_trisample_rows returns GS_ERR_INVALID until the next fold).
+ * gs_trisample_rows / _rows_device: the last fold's rows (edge count, estimate, betaSum) into
+ *   HOST / DEVICE arrays of capacity cap (any array may be NULL); *n = the rows. cap < rows:
+ *   GS_ERR_TRUNCATED, *n set, nothing written.
+ * gs_trisample_estimate: arrivals folded, betaSum now, the last emitted estimate (0 before any
+ *   row). No device call.
+ * gs_trisample_states / _states_device: per instance src, trg, third, flags (bit 0 srcEdgeFound,
+ *   bit 1 trgEdgeFound, bit 2 beta) and sampled_at (the edge count at which the candidate was
+ *   sampled) into HOST / DEVICE arrays of `samples` elements (any may be NULL); third = -1 and
+ *   sampled_at = 0 before the first edge.
+ * gs_trisample_sync / _get_stream / _wait_stream: as gs_sync / gs_get_stream / gs_wait_stream.
+ * Not built: parallelism above 1 (per-subtask sample shares, the per-source result map),
+ * IncidenceSampling's intermediate emissions (the sums it emits while only some instances have
+ * seen the current edge; its instance states after every edge equal Broadcast's under the same
+ * draws, and those are reproduced), combine, serialization, multi-GPU groups. */
+typedef struct gs_trisample_s* gs_trisample;
+int gs_trisample_create(gs_trisample* out, int device, uint64_t samples, int64_t vertices, int64_t seed,
+                        uint64_t third_seed);
+int gs_trisample_destroy(gs_trisample t); /* NULL is GS_OK */
+int gs_trisample_reset(gs_trisample t);
+int gs_trisample_fold(gs_trisample t, const int64_t* src, const int64_t* dst, size_t n, size_t* rows);
+int gs_trisample_fold_device(gs_trisample t, const int64_t* src, const int64_t* dst, size_t n, size_t stride,
+                             size_t* rows);
+int gs_trisample_rows(gs_trisample t, int32_t* edges, int32_t* estimate, int32_t* beta_sum, size_t cap, size_t* n);
+int gs_trisample_rows_device(gs_trisample t, int32_t* edges, int32_t* estimate, int32_t* beta_sum, size_t cap,
+                             size_t* n);
+int gs_trisample_estimate(gs_trisample t, uint64_t* arrivals, int32_t* beta_sum, int32_t* estimate);
+int gs_trisample_states(gs_trisample t, int64_t* src, int64_t* trg, int64_t* third, uint8_t* flags,
+                        int32_t* sampled_at);
+int gs_trisample_states_device(gs_trisample t, int64_t* src, int64_t* trg, int64_t* third, uint8_t* flags,
+                               int32_t* sampled_at);
+int gs_trisample_sync(gs_trisample t);
+int gs_trisample_get_stream(gs_trisample t, void** stream);
+int gs_trisample_wait_stream(gs_trisample t, void* stream);
+
 /* ---- introspection -----------------------------------------------------------
  * The HIP stream (hipStream_t) the handle enqueues on, and per-kernel timing:
  * when profiling is on, every launch is bracketed by HIP events on the stream it

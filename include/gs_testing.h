@@ -132,6 +132,25 @@ int gs_testing_matching_stats(void* m, uint64_t* out);
  * value. Returns GS_OK or GS_ERR_INVALID. */
 int gs_testing_matching_tune(void* m, int what, int64_t value);
 
+/* The last fold of a trisample handle (`t` is a gs_trisample; no device call; zero after a
+ * reset): out[0] = coin successes (resamples), out[1] = segments searched (one carried-in
+ * candidate per instance plus one per resample), out[2] = the longest third-vertex draw, in
+ * attempts, out[3] = rows; out[4..7] = microseconds of the fold's coin pass with its count read,
+ * of the sort and the segments, of the search pass, and of the outcomes and rows with the control
+ * read -- zero unless the handle's profile control is on. Eight words. */
+int gs_testing_trisample_stats(void* t, uint64_t* out);
+
+/* Per-handle controls of a trisample handle's folds (`t` is a gs_trisample; not a knob of
+ * gs_testing_set), so that a test can put a boundary anywhere: what = 0 the arrivals per
+ * workgroup of the coin pass (product: 256), what = 1 the arrivals per workgroup of the search
+ * pass (product: 1024, which is also the most its LDS stage holds: larger values are clamped),
+ * what = 2 profile: bracket the four phases of a fold with events and wait for them (product: off;
+ * needed by tools/trisample_bench.py), what = 3 the most keys the resample list is first sized for
+ * (product: the expected count S (H(t0 + n) - H(t0)) plus eight deviations): a small value makes
+ * the coin pass overflow the list, which is then grown to the count and the pass run again.
+ * A value <= 0 restores the product value. Returns GS_OK or GS_ERR_INVALID. */
+int gs_testing_trisample_tune(void* t, int what, int64_t value);
+
 #ifdef __cplusplus
 }
 #endif
