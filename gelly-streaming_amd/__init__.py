@@ -919,13 +919,13 @@ class Summary(_ResetHandle):
     def set_hot_index(self, log2_entries=0, first_after_edges=0, rebuild_every_folds=1):
         """gs_set_hot_index: the plain CC fold's index of frequent ids. log2_entries < 0 turns it
         off, 0 restores the defaults (on for tables of at least 256 MiB), 1..20 forces an index
-        of that size whatever the table's, first built after first_after_edges edges and then
-        every rebuild_every_folds folds."""
+        of at most 2^log2_entries ids (two per 16-byte bucket) whatever the table's size, first
+        built after first_after_edges edges and then every rebuild_every_folds folds."""
         _check(lib().gs_set_hot_index(self._h, int(log2_entries), int(first_after_edges), int(rebuild_every_folds)))
 
     def hot_index_stats(self):
-        """gs_hot_index_stats: builds queued, entries the live index holds, log2 of its size
-        (0: none), refreshes queued."""
+        """gs_hot_index_stats: builds queued, ids the live index holds (entries), log2 of the ids
+        it can hold (0: none), refreshes queued."""
         a = (_u64 * 4)()
         _check(lib().gs_hot_index_stats(self._h, a))
         return dict(zip(("builds", "entries", "log2_entries", "refreshes"), list(a)))

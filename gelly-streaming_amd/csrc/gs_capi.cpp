@@ -162,18 +162,30 @@ void reset_capacity_tracking(gs_summary* h, uint64_t nv) {
 }
 
 // ---- hot index of the plain CC fold (gs_hot_k.hip) ----
-// Defaults from the calibration under concurrency (profiles/hot_index_calib.txt): 2^16 entries
-// (1 MiB, inside every XCD's L2); never more by default (2^17: a wash, 2^18: slower,
-// profiles/r04_calib_hot.txt). A table below 256 MiB probes fast enough without it.
-constexpr int kHotLog2 = 16;
+// Defaults from the grid on the flagship step (profiles/hot_buckets_grid.txt): 2^17 ids in 2^16
+// buckets (1 MiB, inside every XCD's L2; 2 MiB is slower), a refresh every 16 folds, the whole
+// 2^20-edge batch as a build's sample. A table below 256 MiB probes fast enough without an index.
+// The three are compile-time switches so that tools/hot_grid.py can run the grid again (one
+// library per setting) when the fold or the build changes.
+#ifndef GS_HOT_LOG2
+#define GS_HOT_LOG2 17
+#endif
+#ifndef GS_HOT_REFRESH_EVERY
+#define GS_HOT_REFRESH_EVERY 16
+#endif
+#ifndef GS_HOT_SAMPLE_LOG2
+#define GS_HOT_SAMPLE_LOG2 20
+#endif
+constexpr int kHotLog2 = GS_HOT_LOG2;
 constexpr int kHotMaxLog2 = 20;
 constexpr uint64_t kHotFirstEdges = 1ull << 26;
 constexpr uint32_t kHotEvery = 2048;
-constexpr uint32_t kHotRefreshPerBuild = 16;  // refreshes between two builds (every / 16 folds apart)
+constexpr uint32_t kHotRefreshEvery = GS_HOT_REFRESH_EVERY;  // the default rule: a refresh every this many folds
+constexpr uint32_t kHotRefreshPerBuild = 16;  // a forced index: refreshes every / 16 folds apart
 constexpr uint64_t kHotMinTableBytes = 256ull << 20;
-constexpr size_t kHotSampleEdges = 1u << 18;  // of the sampled micro-batch
+constexpr size_t kHotSampleEdges = 1u << GS_HOT_SAMPLE_LOG2;  // of the sampled micro-batch
 
-// log2 entries of the index this summary's plain folds use as it is set up now (0: none)
+// log2 ids of the index this summary's plain folds use as it is set up now (0: none)
 int hot_log2(const gs_summary* h) {
   if (h->kind != GS_KIND_CC || h->hot_cfg < 0) return 0;
   if (h->track || h->changes || h->srv_on || h->side || h->group_lanes) return 0;
@@ -215,8 +227,11 @@ int hot_before_fold(gs_summary* h) {
 // After a fold of c edges queued on st (hl = hot_log2(h) > 0): when a build is due it is queued
 // behind that fold, on its stream, from its edges, into the buffer no fold reads. No fold waits
 // for it: the folds go on with the live buffer (or none) until hot_before_fold sees it done.
-// Between two builds, every 1/16 of their distance, a refresh renews the live entries'
-// ancestors the same way (a cadence below 16 folds needs none).
+// Between two builds a refresh finds the root above the live index's ancestor again -- every
+// kHotRefreshEvery folds by the default rule, every 1/16 of the builds' distance for a forced
+// index (a cadence below 16 folds needs none): one wave behind the fold, writing
+// one word of the live header, so it needs no buffer and no event of its own. A later build
+// rewrites that buffer only behind the events of every stream's last reader, the refresh included.
 int hot_after_fold(gs_summary* h, const int64_t* src, const int64_t* dst, size_t c, size_t stride, hipStream_t st,
                    int hl) {
   h->hot_edges += c;
@@ -226,11 +241,17 @@ int hot_after_fold(gs_summary* h, const int64_t* src, const int64_t* dst, size_t
   const uint64_t first = h->hot_cfg ? h->hot_first : kHotFirstEdges;
   const uint32_t every = h->hot_cfg ? h->hot_every : kHotEvery;
   const bool build = h->hot_live < 0 ? h->hot_edges >= first : h->hot_folds >= every;
-  const uint32_t refresh_every = every / kHotRefreshPerBuild;
-  if (!build && !(h->hot_live >= 0 && refresh_every && h->hot_folds_r >= refresh_every)) return GS_OK;
+  const uint32_t refresh_every = h->hot_cfg ? every / kHotRefreshPerBuild : kHotRefreshEvery;
+  if (!build) {
+    if (!(h->hot_live >= 0 && refresh_every && h->hot_folds_r >= refresh_every)) return GS_OK;
+    h->hot_refreshes++;
+    h->hot_folds_r = 0;
+    GS_LAUNCH(gs::launch_hot_refresh(h->table(), h->hot_buf[h->hot_live], hl, st));
+    return GS_OK;
+  }
   if (h->hot_alloc_log2 != hl) {  // first use (gs_set_hot_index freed the buffers of another size)
     h->hot_alloc_log2 = 0;
-    for (auto& b : h->hot_buf) GS_HIP(b.alloc(1ull << hl));
+    for (auto& b : h->hot_buf) GS_HIP(b.alloc(gs::hot_buckets(hl) + 1));  // the buckets and their header
     GS_HIP(h->hot_scratch.alloc(gs::hot_scratch_words(hl)));
     if (!h->hot_built) {
       GS_HIP(h->hot_built.create());
@@ -245,15 +266,10 @@ int hot_after_fold(gs_summary* h, const int64_t* src, const int64_t* dst, size_t
       if (i == gs_summary::kLanes || h->lane[i]) GS_HIP(hipStreamWaitEvent(st, h->hot_read[b][i], 0));
     h->hot_read_on[b] = false;
   }
-  if (build) {  // (counted whether or not the launch is accepted)
-    h->hot_folds = 0;
-    h->hot_builds++;
-    GS_LAUNCH(gs::launch_hot_build(h->table(), src, dst, (uint32_t)std::min(c, kHotSampleEdges), (uint32_t)stride,
-                                   h->hot_buf[b], hl, h->hot_scratch, st));
-  } else {
-    h->hot_refreshes++;
-    GS_LAUNCH(gs::launch_hot_refresh(h->table(), h->hot_buf[h->hot_live], h->hot_buf[b], hl, st));
-  }
+  h->hot_folds = 0;  // (counted whether or not the launch is accepted)
+  h->hot_builds++;
+  GS_LAUNCH(gs::launch_hot_build(h->table(), src, dst, (uint32_t)std::min(c, kHotSampleEdges), (uint32_t)stride,
+                                 h->hot_buf[b], hl, h->hot_scratch, st));
   GS_HIP(hipEventRecord(h->hot_built, st));
   h->hot_building = b;
   h->hot_folds_r = 0;
@@ -797,7 +813,7 @@ int fold_device_impl(gs_summary* h, const int64_t* src, const int64_t* dst, cons
       if (int rc = hot_before_fold(h)) return rc;
       if (h->hot_live >= 0 && h->hot_alloc_log2 == hot) {
         f.hot.e = h->hot_buf[h->hot_live];
-        f.hot.shift = 64 - hot;
+        f.hot.shift = 65 - hot;  // 2^(hot - 1) buckets
       }
     }
     {
@@ -2016,7 +2032,7 @@ int gs_set_pipelining(gs_handle h, int depth) {
 int gs_set_hot_index(gs_handle h, int log2_entries, uint64_t first_after_edges, uint32_t rebuild_every_folds) {
   if (int rc = check_any(h)) return rc;
   if (h->kind != GS_KIND_CC) return fail(GS_ERR_INVALID, "the hot index serves connected-components summaries only");
-  if (log2_entries > kHotMaxLog2) return fail(GS_ERR_INVALID, "hot index: at most 2^20 entries");
+  if (log2_entries > kHotMaxLog2) return fail(GS_ERR_INVALID, "hot index: at most 2^20 ids");
   DeviceGuard g(h->device);
   if (int rc = join_lanes(h)) return rc;
   GS_HIP(hipStreamSynchronize(h->stream));  // nothing reads or builds a buffer any more
@@ -2043,10 +2059,10 @@ int gs_hot_index_stats(gs_handle h, uint64_t* out4) {
   out4[1] = 0;
   out4[2] = h->hot_live >= 0 ? (uint64_t)h->hot_alloc_log2 : 0;
   out4[3] = h->hot_refreshes;
-  if (h->hot_live >= 0) {  // the entries the live index holds
-    std::vector<gs::HotEntry> e(1ull << h->hot_alloc_log2);
-    GS_HIP(hipMemcpy(e.data(), h->hot_buf[h->hot_live], e.size() * sizeof(gs::HotEntry), hipMemcpyDeviceToHost));
-    for (const gs::HotEntry& x : e) out4[1] += x.slot != gs::kNoSlot;
+  if (h->hot_live >= 0) {  // the keys the live index holds
+    std::vector<gs::HotBucket> e(gs::hot_buckets(h->hot_alloc_log2));
+    GS_HIP(hipMemcpy(e.data(), h->hot_buf[h->hot_live], e.size() * sizeof(gs::HotBucket), hipMemcpyDeviceToHost));
+    for (const gs::HotBucket& x : e) out4[1] += (x.key[0] != gs::kEmpty) + (x.key[1] != gs::kEmpty);
   }
   return GS_OK;
 }

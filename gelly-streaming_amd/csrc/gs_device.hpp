@@ -178,31 +178,38 @@ __device__ __forceinline__ void load_slot(const Slot* p, int64_t& key, uint32_t&
   link = v.z;
 }
 
-// Hot index (gs_hot_k.hip): a direct-mapped, L2-sized table of the stream's
-// most frequent ids, probed by the plain CC fold before the relabel table. An entry names its
-// key's slot and a slot that was an ancestor of it when the entry was built (its root then).
-// Within one life of the table a key's slot never changes and an ancestor stays an ancestor
-// (links only move to ancestors, hooks only give a root a parent), so two slots with a common
-// ancestor are in one component for good: an entry may settle an edge, and is used for nothing
-// else. An empty entry has slot == kNoSlot; kEmpty is never a key here (its vertex lives in r0).
-struct alignas(16) HotEntry {
-  int64_t key;
-  uint32_t slot;
-  uint32_t anc;
+// Hot index (gs_hot_k.hip): an L2-sized table of the stream's most frequent
+// ids, probed by the plain CC fold before the relabel table. A bucket is 16 B: two keys, read
+// with one load. A key is held only if the relabel table holds it and slot G -- one slot per
+// build, in the header behind the buckets -- is an ancestor of its slot. G2 is a root found from
+// G some time after the build: an ancestor of G. Within one life of the table a key's slot never
+// changes and an ancestor stays an ancestor (links only move to ancestors, hooks only give a root
+// a parent), so every held key is under G, and under any value G2 ever had, for good: an index
+// answer may settle an edge, and is used for nothing else. An empty place holds kEmpty, which is
+// never a key here (its vertex lives in r0).
+struct alignas(16) HotBucket {
+  int64_t key[2];
+};
+struct alignas(16) HotHeader {
+  uint32_t g, g2;  // kNoSlot: the build held no key
+  uint32_t pad[2];
 };
 struct HotIndex {
-  const HotEntry* e = nullptr;  // null: no live index
-  int shift = 63;               // 64 - log2(entries)
+  const HotBucket* e = nullptr;  // null: no live index; the header is e[1 << (64 - shift)]
+  int shift = 64;                // 64 - log2(buckets), >= 32
 };
+// the bucket of a key: the top bits of a multiplicative hash (one bucket: shift == 64, position 0)
 __device__ __forceinline__ uint32_t hot_pos(int64_t key, int shift) {
-  return (uint32_t)(((uint64_t)key * 0xD6E8FEB86659FD93ull) >> shift);
+  return (uint32_t)((((uint64_t)key * 0xD6E8FEB86659FD93ull) >> 32) >> (shift - 32));
 }
-// the entry at p as one 16-B load; true when it answers `key`
-__device__ __forceinline__ bool hot_load(const HotEntry* p, int64_t key, uint32_t& slot, uint32_t& anc) {
+__device__ __forceinline__ const HotHeader* hot_header(const HotIndex& x) {
+  return reinterpret_cast<const HotHeader*>(x.e + (1ull << (64 - x.shift)));
+}
+// the bucket at p as one 16-B load; true when it holds `key`
+__device__ __forceinline__ bool hot_load(const HotBucket* p, int64_t key) {
   const uint4 v = *reinterpret_cast<const uint4*>(p);
-  slot = v.z;
-  anc = v.w;
-  return (int64_t)(((uint64_t)v.y << 32) | v.x) == key && v.z != kNoSlot && key != kEmpty;
+  const int64_t k0 = (int64_t)(((uint64_t)v.y << 32) | v.x), k1 = (int64_t)(((uint64_t)v.w << 32) | v.z);
+  return ((k0 == key) | (k1 == key)) & (key != kEmpty);  // (no short circuit: the load stays one)
 }
 
 __device__ __forceinline__ uint32_t load_link_fresh(const Slot* p) {

@@ -376,12 +376,12 @@ struct gs_summary : gsi::StreamOwner {
   // hot index of the plain CC fold (gs_set_hot_index; gs_hot_k.hip): two
   // buffers, one read by the folds while a build fills the other on the lane that folded the
   // sampled batch. hot_drop ends an index with the life of the table it was built from.
-  int hot_cfg = 0;             // log2 entries asked for: < 0 off, 0 the default rule, > 0 forced
+  int hot_cfg = 0;             // log2 ids asked for: < 0 off, 0 the default rule, > 0 forced
   uint64_t hot_first = 0;      // first build after this many edges of the table's life
   uint32_t hot_every = 0;      // then a build every this many folds
-  gsi::DevBuf<gs::HotEntry> hot_buf[2];  // (first use: the first build)
+  gsi::DevBuf<gs::HotBucket> hot_buf[2];  // (first use: the first build)
   gsi::DevBuf<unsigned long long> hot_scratch;
-  int hot_alloc_log2 = 0;      // log2 entries the buffers hold (0: none)
+  int hot_alloc_log2 = 0;      // log2 ids the buffers hold (0: none)
   int hot_live = -1;           // the buffer the folds read (-1: no index)
   int hot_building = -1;       // the buffer a queued build writes, adopted once hot_built has passed
   gsi::Event hot_built;

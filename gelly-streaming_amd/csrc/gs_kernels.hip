@@ -521,27 +521,29 @@ __device__ __forceinline__ void fold_block(const Table& t, const Delta& D, const
   uint32_t l0u = 0, l0v = 0;
   if (HOT) {
     // Hot index: both index probes go out first, together; an endpoint's table probe only if its
-    // index probe missed. With a hit the edge is tested as the shortcut below tests it -- a hit
-    // side's slot and ancestor for its slot and parent, a missed side's first-probe slot and
-    // link -- and a common ancestor settles it: the vertices exist and are in one component, so
-    // the thread has nothing to insert, find, hook or store. A test that fails (or a missed side
-    // whose first probe is not its key) discards the index answers: the hit sides are probed in
-    // the table and the edge goes on as without an index.
+    // index probe missed. Every held key is under the index's ancestor G for good, so two hits
+    // settle the edge. With one hit the missed side's first probe settles it when that slot
+    // holds the missed key and is, or hangs directly under, G or G2 (an ancestor of G: a stale
+    // value of it still is). A settled edge's vertices exist and are in one component: the
+    // thread has nothing to insert, find, hook or store. Otherwise the index answer is
+    // forgotten: the hit side is probed in the table and the edge goes on as without an index.
     static_assert(!HOT || (!SIGNED && !TRACK && !TAKE && !ROWS), "the hot index serves the plain CC fold only");
-    uint32_t xsu = 0, xau = 0, xsv = 0, xav = 0;
+    // a uniform address, read once and not per hit; through the constant address space, so that
+    // it is one scalar load (a value that is stale for the whole kernel is as good)
+    const auto* hh = (const __attribute__((address_space(4))) HotHeader*)hot_header(a.hot);
+    const uint32_t g = hh->g, g2 = hh->g2;
     bool hitu = false, hitv = false;
     if (valid) {
-      const HotEntry *eu = a.hot.e + hot_pos(ks, a.hot.shift), *ev = a.hot.e + hot_pos(kd, a.hot.shift);
-      hitu = hot_load(eu, ks, xsu, xau);
-      hitv = hot_load(ev, kd, xsv, xav);
+      hitu = hot_load(a.hot.e + hot_pos(ks, a.hot.shift), ks);
+      hitv = hot_load(a.hot.e + hot_pos(kd, a.hot.shift), kd);
       if (!hitu) load_slot(t.tab + hu, k0u, l0u);
       if (!hitv) load_slot(t.tab + hv, k0v, l0v);
     }
     if (hitu || hitv) {
-      const bool oku = hitu || (k0u == ks && ks != kEmpty), okv = hitv || (k0v == kd && kd != kEmpty);
-      const uint32_t s_u = hitu ? xsu : hu, p_u = hitu ? xau : l0u >> 1;
-      const uint32_t s_v = hitv ? xsv : hv, p_v = hitv ? xav : l0v >> 1;
-      if (oku && okv && (s_u == s_v || p_u == p_v || p_u == s_v || p_v == s_u)) {
+      // the missed side of a one-hit edge: its key, first-probe slot, and what that probe read
+      const int64_t km = hitu ? kd : ks, k0m = hitu ? k0v : k0u;
+      const uint32_t sm = hitu ? hv : hu, pm = (hitu ? l0v : l0u) >> 1;
+      if ((hitu && hitv) || (k0m == km && km != kEmpty && (pm == g || pm == g2 || sm == g || sm == g2))) {
         GS_DBG(CTR_DBG_EDGES);
         GS_DBG(CTR_DBG_HOTHIT);
         valid = false;  // done: the rest of the block's work sees an idle lane

@@ -105,13 +105,15 @@ void launch_find_one(const Table& t, int64_t key, int64_t* out, hipStream_t st);
 void launch_find_batch(const Table& t, const int64_t* v, uint64_t n, int64_t* label, uint8_t* found, uint8_t* parity,
                        hipStream_t st);
 
-// hot index build (gs_hot_k.hip): out[2^log2] from the first n edges of a micro-batch; scratch
-// holds hot_scratch_words(log2) words
-uint64_t hot_scratch_words(int log2_entries);
+// hot index build (gs_hot_k.hip): an index of at most 2^log2 ids (2^(log2 - 1) buckets and the
+// header behind them: hot_buckets(log2) + 1 elements of `out`) from the first n edges of a
+// micro-batch; scratch holds hot_scratch_words(log2) words
+inline uint64_t hot_buckets(int log2_ids) { return 1ull << (log2_ids - 1); }
+uint64_t hot_scratch_words(int log2_ids);
 void launch_hot_build(const Table& t, const int64_t* src, const int64_t* dst, uint32_t n, uint32_t stride,
-                      HotEntry* out, int log2_entries, unsigned long long* scratch, hipStream_t st);
-// out = the entries of `in` with their ancestors found again
-void launch_hot_refresh(const Table& t, const HotEntry* in, HotEntry* out, int log2_entries, hipStream_t st);
+                      HotBucket* out, int log2_ids, unsigned long long* scratch, hipStream_t st);
+// the header's G2 found again from its G (one wave)
+void launch_hot_refresh(const Table& t, HotBucket* live, int log2_ids, hipStream_t st);
 
 // change emission (gs_changes_k.hip)
 void launch_iota(uint32_t* nxt, uint64_t n, hipStream_t st);

@@ -144,28 +144,35 @@ int gs_fold_device_after(gs_handle h, const int64_t* src, const int64_t* dst, co
  * (DESIGN.md section 7). */
 int gs_set_pipelining(gs_handle h, int depth);
 
-/* Hot index of the plain connected-components fold: a small direct-mapped table of the
- * stream's most frequent ids {id -> slot, an ancestor of the slot}, resident in every L2,
- * probed before the relabel table. An edge both of whose endpoints it places under one
- * ancestor is done without touching the relabel table; it is used for nothing else, so
- * results are unchanged. It is rebuilt from a sample of a micro-batch, off the folds'
+/* Hot index of the plain connected-components fold: a small table of the stream's most
+ * frequent ids, resident in every L2, probed before the relabel table. A bucket is 16 bytes:
+ * two ids, read with one load. An id is held only if the relabel table holds it and one slot
+ * chosen per build -- the root most of the sampled hot ids reached -- is an ancestor of its
+ * slot: one index serves one component, the one that dominates the stream. A small header
+ * beside the buckets names that ancestor and a root found from it later. An edge with both
+ * endpoints in the index, or with one in it and the other hanging directly under one of the
+ * header's two slots, is done without a find, hook, insert or store; the index is used for
+ * nothing else, so results are unchanged. It is rebuilt from a micro-batch, off the folds'
  * critical path, and dropped whenever the table is reset, rebuilt, combined into or
  * deserialized.
  * By default it is on for GS_KIND_CC summaries whose table has at least 256 MiB, in plain
  * host and device folds (no delta or change tracking, no window takes, no window server, no
- * exchange group): 2^16 entries, first built after 2^26 edges since the reset, then every
- * 2048 folds; between two builds the entries' ancestors are renewed every 1/16 of that distance
- * (a refresh: one small kernel; none when builds are less than 16 folds apart). (The library reads no environment variable: the Python binding turns the
- * default off for summaries created while GS_HOT_INDEX=0 is set, for A/B runs.)
+ * exchange group): 2^17 ids (2^16 buckets, 1 MiB), first built after 2^26 edges since the
+ * reset, then every 2048 folds, with a refresh every 16 folds (one wave: the root above the
+ * index's ancestor found again, one word stored into the live header). (The library reads
+ * no environment variable: the Python binding turns the default off for summaries created
+ * while GS_HOT_INDEX=0 is set, for A/B runs.)
  *   log2_entries < 0  : off;
  *   log2_entries == 0 : the defaults above (the other two arguments are ignored);
- *   log2_entries 1..20: 2^log2_entries entries whatever the table's size, first built after
- *                       first_after_edges edges, then every rebuild_every_folds folds.
+ *   log2_entries 1..20: at most 2^log2_entries ids (2^(log2_entries - 1) buckets; 1: one
+ *                       bucket) whatever the table's size, first built after
+ *                       first_after_edges edges, then every rebuild_every_folds folds, with a
+ *                       refresh every rebuild_every_folds / 16 folds (none below 16).
  * GS_ERR_INVALID for signed and degree summaries. The call waits for the handle's work.
- * gs_hot_index_stats: out4 = {builds queued since create, entries the live index holds,
- * log2 of its entries (0: no live index), refreshes queued since create}; it waits for the
- * handle's work as well. The debug-counter build counts the edges the index settled and those
- * that fell back to the table (gs_debug_counters). */
+ * gs_hot_index_stats: out4 = {builds queued since create, ids the live index holds,
+ * log2 of the ids it can hold (0: no live index), refreshes queued since create}; it waits
+ * for the handle's work as well. The debug-counter build counts the edges the index settled
+ * and those that fell back to the table (gs_debug_counters). */
 int gs_set_hot_index(gs_handle h, int log2_entries, uint64_t first_after_edges, uint32_t rebuild_every_folds);
 int gs_hot_index_stats(gs_handle h, uint64_t* out4);
 

@@ -9,8 +9,10 @@
 //   C : B with non-temporal main-table loads (leave the L2 to hot lines)
 //   D : A with non-temporal main loads (reference for C)
 //   M : direct-mapped hot table (one 16-B probe, the highest-count key per slot)
-// Last, A against M1 with entries {key, slot, anc} under the pipelined fold's conditions: three
-// probe kernels in flight on three streams (profiles/hot_index_calib.txt).
+// Last, A against M1 with entries {key, slot, anc} and against K2, buckets of two keys under one
+// shared ancestor (2^16 and 2^17 buckets), under the pipelined fold's conditions: three probe
+// kernels in flight on three streams (profiles/hot_index_calib.txt). A second argument skips
+// everything before that last part.
 // Build: hipcc -O3 --offload-arch=gfx950 -Iinclude tools/calib_hot.hip
 //          -Lgelly-streaming_amd/lib -lgs_summary -Wl,-rpath,$PWD/gelly-streaming_amd/lib -o tools/bin/calib_hot
 #include <hip/hip_runtime.h>
@@ -265,6 +267,73 @@ __global__ __launch_bounds__(256) void k_probe_ix(const uint4* tab, uint32_t mas
   if (((su ^ sv) + (pu ^ pv)) == 0x12345671u) sink[0] = su;
 }
 
+// K2: buckets of two keys {key0, key1}. Ranks are {count, tag of the key}; one pass keeps the two
+// highest per bucket (the rank that loses to the winner or is displaced by it goes into the second
+// max), then each ranked key the main table holds takes its half of the bucket.
+__device__ __forceinline__ unsigned long long rank_of(unsigned long long c, int64_t key) {
+  return (c << 32) | (uint32_t)(((uint64_t)key * 0x9E3779B97F4A7C15ull) >> 32);
+}
+__global__ void k_k2_max(const uint4* cnt, uint64_t n, uint64_t T, unsigned long long* b1, unsigned long long* b2, int hsh) {
+  for (uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; s < n; s += (uint64_t)gridDim.x * blockDim.x) {
+    const uint4 v = cnt[s];
+    const int64_t key = key_of(v);
+    const unsigned long long c = ((unsigned long long)v.w << 32) | v.z;
+    if (key == kEmpty || c < T) continue;
+    const unsigned long long r = rank_of(c, key);
+    const uint32_t h = hhot(key, hsh);
+    const unsigned long long old = atomicMax(b1 + h, r);
+    const unsigned long long lower = old < r ? old : r;
+    if (old != r && lower) atomicMax(b2 + h, lower);
+  }
+}
+__global__ void k_k2_place(const uint4* cnt, uint64_t n, uint64_t T, const unsigned long long* b1,
+                           const unsigned long long* b2, uint4* hot, int hsh, const uint4* tab, uint32_t mask, int sh,
+                           unsigned long long* nsel) {
+  for (uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; s < n; s += (uint64_t)gridDim.x * blockDim.x) {
+    const uint4 v = cnt[s];
+    const int64_t key = key_of(v);
+    const unsigned long long c = ((unsigned long long)v.w << 32) | v.z;
+    if (key == kEmpty || c < T) continue;
+    const unsigned long long r = rank_of(c, key);
+    const uint32_t h = hhot(key, hsh);
+    const int w = b1[h] == r ? 0 : (b2[h] == r ? 1 : -1);
+    if (w < 0) continue;
+    uint32_t m = hmain(key, sh);
+    bool found = false;
+    for (uint32_t p = 0; p <= mask; ++p) {
+      const int64_t k = key_of(tab[m]);
+      found = k == key;
+      if (found || k == kEmpty) break;
+      m = (m + 1) & mask;
+    }
+    if (!found) continue;
+    unsigned long long* kp = reinterpret_cast<unsigned long long*>(hot + h) + w;  // (cnt holds each key once)
+    *kp = (unsigned long long)key;
+    atomicAdd(nsel, 1ull);
+  }
+}
+// What the fold does per edge with two-key buckets: both bucket probes first; two hits need no
+// table access; with one hit the missed side's first probe is compared with the shared ancestor.
+__global__ __launch_bounds__(256) void k_probe_k2(const uint4* tab, uint32_t mask, int sh, const uint4* hot, int hsh,
+                                                  uint32_t g, const int64_t* src, const int64_t* dst, uint32_t n,
+                                                  uint32_t* sink) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int64_t ku = __builtin_nontemporal_load(src + i), kv = __builtin_nontemporal_load(dst + i);
+  const uint4 a = hot[hhot(ku, hsh)], b = hot[hhot(kv, hsh)];
+  const bool hu = (key_of(a) == ku) | ((int64_t)(((uint64_t)a.w << 32) | a.z) == ku);
+  const bool hv = (key_of(b) == kv) | ((int64_t)(((uint64_t)b.w << 32) | b.z) == kv);
+  if (hu & hv) return;
+  const uint32_t mu = hmain(ku, sh), mv = hmain(kv, sh);
+  uint4 x{}, y{};
+  uint32_t pu = g, pv = g;
+  if (!hu) x = tab[mu];
+  if (!hv) y = tab[mv];
+  if (!hu) pu = probe_main<false>(tab, mask, sh, ku, mu, x);
+  if (!hv) pv = probe_main<false>(tab, mask, sh, kv, mv, y);
+  if (((pu >> 1) ^ (pv >> 1)) == 0x12345671u) sink[0] = pu;
+}
+
 int main(int argc, char** argv) {
   setvbuf(stdout, nullptr, _IONBF, 0);
   const int logs = 27, scale = 26;
@@ -319,7 +388,9 @@ int main(int argc, char** argv) {
   hipEvent_t e0, e1;
   CK(hipEventCreate(&e0));
   CK(hipEventCreate(&e1));
+  const bool pipelined_only = argc > 2;
   auto run = [&](int mode, int logH, const char* name) -> int {
+    if (pipelined_only) return 0;
     const uint32_t hmask = (1u << logH) - 1;
     const int hsh = 64 - logH;
     float best = 1e9f;
@@ -410,18 +481,21 @@ int main(int argc, char** argv) {
   // batches, as the 3-deep pipelined step runs them. A = main only, M1 = direct-mapped index of
   // {key, slot, anc} entries first. The variants alternate within every repetition; a repetition is
   // kRounds passes over the NB batches, timed on the host from the first launch to a device synchronise.
-  constexpr int kStreams = 3, kReps = 7, kRounds = 8, kVar = 3;
+  constexpr int kStreams = 3, kReps = 7, kRounds = 8, kVar = 5;
   hipStream_t st[kStreams];
   for (int i = 0; i < kStreams; ++i) CK(hipStreamCreateWithFlags(&st[i], hipStreamNonBlocking));
-  uint4* hotv[kVar] = {nullptr, nullptr, nullptr};
-  const int logv[kVar] = {0, 15, 16};
-  const char* namev[kVar] = {"A  main only", "M1 index 2^15", "M1 index 2^16"};
+  uint4* hotv[kVar] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  const int logv[kVar] = {0, 15, 16, 16, 17};  // entries (M1) or buckets (K2)
+  const char* namev[kVar] = {"A  main only", "M1 index 2^15", "M1 index 2^16", "K2 2^16 buckets", "K2 2^17 buckets"};
+  unsigned long long* best2;
+  CK(hipMalloc(&best2, (1ull << 20) * 8));
   printf("3 streams, %d x %u batches per repetition, %d repetitions, variants alternated\n", kRounds, NB, kReps);
   for (int v = 1; v < kVar; ++v) {
     const uint64_t H = 1ull << logv[v];
+    const bool k2 = v >= 3;
     uint64_t T = 63, acc = 0;
     for (int c = 63; c >= 2; --c) {
-      if (acc + hh[c] > H) break;
+      if (acc + hh[c] > (k2 ? 2 * H : H)) break;
       acc += hh[c];
       T = c;
     }
@@ -430,14 +504,21 @@ int main(int argc, char** argv) {
     CK(hipMemset2D(reinterpret_cast<char*>(hotv[v]) + 7, 16, 0x80, 1, H));
     CK(hipMemset(best, 0, H * 8));
     CK(hipMemset(nsel, 0, 8));
-    k_dm_max<<<2048, 256>>>(cnt, cslots, T, best, 64 - logv[v]);
-    k_dm_place<<<2048, 256>>>(cnt, cslots, T, best, hotv[v], 64 - logv[v], nsel);
-    CK(hipMemset(nsel, 0, 8));
-    k_dm_fill<<<(uint32_t)(H / 256), 256>>>(hotv[v], (uint32_t)H, tab, (uint32_t)(slots - 1), sh, nsel);
+    if (k2) {
+      CK(hipMemset2D(reinterpret_cast<char*>(hotv[v]) + 15, 16, 0x80, 1, H));  // the second key := INT64_MIN too
+      CK(hipMemset(best2, 0, H * 8));
+      k_k2_max<<<2048, 256>>>(cnt, cslots, T, best, best2, 64 - logv[v]);
+      k_k2_place<<<2048, 256>>>(cnt, cslots, T, best, best2, hotv[v], 64 - logv[v], tab, (uint32_t)(slots - 1), sh, nsel);
+    } else {
+      k_dm_max<<<2048, 256>>>(cnt, cslots, T, best, 64 - logv[v]);
+      k_dm_place<<<2048, 256>>>(cnt, cslots, T, best, hotv[v], 64 - logv[v], nsel);
+      CK(hipMemset(nsel, 0, 8));
+      k_dm_fill<<<(uint32_t)(H / 256), 256>>>(hotv[v], (uint32_t)H, tab, (uint32_t)(slots - 1), sh, nsel);
+    }
     unsigned long long ns = 0;
     CK(hipMemcpy(&ns, nsel, 8, hipMemcpyDeviceToHost));
-    printf("index 2^%d entries (%llu KiB): T=%llu, %llu entries filled\n", logv[v], (unsigned long long)(H * 16 >> 10),
-           (unsigned long long)T, ns);
+    printf("%s 2^%d %s (%llu KiB): T=%llu, %llu keys held\n", k2 ? "buckets" : "index", logv[v], k2 ? "buckets" : "entries",
+           (unsigned long long)(H * 16 >> 10), (unsigned long long)T, ns);
   }
   double us[kVar][kReps];
   for (int rep = -1; rep < kReps; ++rep) {  // repetition -1 warms up and is not kept
@@ -451,6 +532,7 @@ int main(int argc, char** argv) {
           const int64_t* d = dst + (size_t)b * B;
           hipStream_t q = st[(r * NB + b) % kStreams];
           if (v == 0) k_probe_ix<false><<<B / 256, 256, 0, q>>>(tab, (uint32_t)(slots - 1), sh, nullptr, 0, s, d, B, sink);
+          else if (v >= 3) k_probe_k2<<<B / 256, 256, 0, q>>>(tab, (uint32_t)(slots - 1), sh, hotv[v], 64 - logv[v], 7u, s, d, B, sink);
           else k_probe_ix<true><<<B / 256, 256, 0, q>>>(tab, (uint32_t)(slots - 1), sh, hotv[v], 64 - logv[v], s, d, B, sink);
         }
       CK(hipDeviceSynchronize());
