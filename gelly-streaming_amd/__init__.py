@@ -87,6 +87,7 @@ EXPORTED_SYMBOLS = (
     "gs_spanner_add", "gs_spanner_within", "gs_spanner_within_device", "gs_spanner_combine", "gs_spanner_count",
     "gs_spanner_export_device", "gs_spanner_export", "gs_spanner_neighbors", "gs_spanner_sync",
     "gs_spanner_get_stream", "gs_spanner_wait_stream", "gs_testing_spanner_stats",
+    "gs_testing_spanner_generation",
     "gs_matching_create", "gs_matching_destroy", "gs_matching_reset", "gs_matching_fold", "gs_matching_fold_device",
     "gs_matching_events", "gs_matching_events_device", "gs_matching_count", "gs_matching_export",
     "gs_matching_export_device", "gs_matching_mate_device", "gs_matching_sync", "gs_matching_get_stream",
@@ -148,9 +149,13 @@ DISTINCT_MODES = {"directed": 0, "undirected": 1}  # gs_distinct_mode
 
 # The k-spanner summary (csrc/gs_spanner_seq.hpp, csrc/gs_spanner.hpp): the range of k, the vertices
 # per side a wave's on-chip sets hold before a search takes the heavy path, the arenas of the
-# heavy path's pool and the rounds before the serial tail.
+# heavy path's pool and the rounds before the serial tail; the elements per workgroup of the three
+# flag / compact passes (SPANNER_TILE) and the generations a stamp arena takes before it is cleared
+# (kSpMaxGen).
 SPANNER_MAX_K = 16
 SPANNER_LDS_SET = 256
+SPANNER_TILE = 1024
+SPANNER_MAX_GEN = 0x7FFFFFF0
 SPANNER_ARENAS = 32
 SPANNER_ROUND_CAP = 16
 
@@ -372,6 +377,7 @@ def lib():
     L.gs_spanner_get_stream.argtypes = [_vp, ctypes.POINTER(_vp)]
     L.gs_spanner_wait_stream.argtypes = [_vp, _vp]
     L.gs_testing_spanner_stats.argtypes = [_vp, ctypes.POINTER(_u64)]
+    L.gs_testing_spanner_generation.argtypes = [_vp, ctypes.c_int64, ctypes.POINTER(_u64)]
     L.gs_matching_create.argtypes = [ctypes.POINTER(_vp), ctypes.c_int, _u64]
     L.gs_matching_destroy.argtypes = [_vp]
     L.gs_matching_reset.argtypes = [_vp]
@@ -1516,6 +1522,13 @@ class Spanner(_ResetHandle):
         _check(lib().gs_testing_spanner_stats(self._h, out))
         return {"filter_drops": out[0], "pending": out[1], "rounds": out[2], "tail": out[3], "heavy": out[4],
                 "longest_row": out[5]}
+
+    def generation(self, set=None):
+        """gs_testing_spanner_generation: the generations the heavy search's stamp arenas have
+        used since their last clear; `set` moves the counter first (clamped to SPANNER_MAX_GEN)."""
+        out = _u64()
+        _check(lib().gs_testing_spanner_generation(self._h, -1 if set is None else int(set), ctypes.byref(out)))
+        return out.value
 
 
 # ---------------------------------------------------------------- weighted matching

@@ -494,4 +494,15 @@ int gs_testing_spanner_stats(void* handle, uint64_t* out) {
   return GS_OK;
 }
 
+// gs_testing.h: the generation counter of the heavy search's arenas, read and (set >= 0) moved,
+// so that a test reaches the clear of take_arenas without 2^31 searches. No device call.
+int gs_testing_spanner_generation(void* handle, int64_t set, uint64_t* out) {
+  gs_spanner s = static_cast<gs_spanner>(handle);
+  if (int rc = check_handle(s, kWhat)) return rc;
+  if (!out) return fail(GS_ERR_INVALID, "out is null");
+  if (set >= 0) s->gen = (uint32_t)std::min<int64_t>(set, gs::kSpMaxGen);
+  *out = s->gen;
+  return GS_OK;
+}
+
 }  // extern "C"

@@ -116,6 +116,13 @@ int gs_testing_distinct_phases(void* d, uint64_t* out);
  * rounds), out[5] = the longest row (adjacency plus pending entries) a search expanded. Six words. */
 int gs_testing_spanner_stats(void* s, uint64_t* out);
 
+/* Per-handle control of a spanner handle's heavy searches (`s` is a gs_spanner; no device call;
+ * not a knob of gs_testing_set): the generations its stamp arenas have used since they were last
+ * cleared. With set >= 0 the counter becomes min(set, 0x7FFFFFF0), so that a test can put the
+ * next heavy search or tail right before the clear that a handle otherwise reaches after 2^31
+ * searches; set < 0 only reads. *out = the counter afterwards. Returns GS_OK or GS_ERR_INVALID. */
+int gs_testing_spanner_generation(void* s, int64_t set, uint64_t* out);
+
 /* The last fold of a matching handle (`m` is a gs_matching; no device call; zero after a reset
  * but the last word): out[0] = rounds run (the tail's included), out[1] = fixpoint passes in
  * total, out[2] = arrivals still pending when the tail took over (the arrivals the tail

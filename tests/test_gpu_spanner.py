@@ -51,6 +51,59 @@ class Model:
                 self.add(s, t)
         return out
 
+    def fold_rounds(self, src, dst, round_cap=None, slow_rule=None):
+        """SpannerSeq::fold_rounds (csrc/gs_spanner_seq.hpp) as the device drives it: the filter
+        pass on G0, rounds that read the statuses of the round before, then the tail in arrival
+        order. round_cap None: the product rule (16 rounds, and -- slow_rule -- a round that
+        decides less than 1/8 of its edges is the last); a set cap fixes the rounds alone.
+        Returns (mask, rounds, tail, filter_drops); the graph ends as after fold()."""
+        cap = 16 if round_cap is None else round_cap
+        slow_rule = round_cap is None if slow_rule is None else slow_rule
+        pend = [i for i, (s, t) in enumerate(zip(src, dst)) if not self.within(s, t)]
+        st = [0] * len(pend)  # 0 undecided, 1 accepted, 2 dropped
+
+        rows = {}  # vertex -> [(neighbour, pending index)]
+        for j, a in enumerate(pend):
+            rows.setdefault(src[a], []).append((dst[a], j))
+            rows.setdefault(dst[a], []).append((src[a], j))
+
+        def view(i, upper, status):  # within k in G0 + the pending j < i that are accepted / not dropped?
+            s, t = src[pend[i]], dst[pend[i]]
+            seen, frontier = {s}, [s]
+            for _ in range(1 if s == t else self.k):  # (only its own loop reaches s again)
+                nxt = []
+                for u in frontier:
+                    more = [y for y, j in rows.get(u, ()) if j < i and (status[j] == 1 or (upper and status[j] == 0))]
+                    for y in (*self.adj.get(u, ()), *more):
+                        if y == t:
+                            return True
+                        if y not in seen:
+                            seen.add(y)
+                            nxt.append(y)
+                frontier = nxt
+            return False
+
+        rounds, und = 0, len(pend)
+        while und and rounds < cap:
+            nst = list(st)
+            for i in range(len(pend)):
+                if st[i] == 0:
+                    nst[i] = 1 if not view(i, True, st) else 2 if view(i, False, st) else 0
+            before, st, und = und, nst, nst.count(0)
+            rounds += 1
+            if slow_rule and (before - und) * 8 < before:
+                break
+        tail = und
+        for i in range(len(pend)):
+            if st[i] == 0:
+                st[i] = 2 if view(i, False, st) else 1
+        mask = [False] * len(src)
+        for i, j in enumerate(pend):
+            if st[i] == 1:
+                mask[j] = True
+                self.add(src[j], dst[j])
+        return mask, rounds, tail, len(src) - len(pend)
+
     def edges(self):
         return sorted((u, v) for u in self.adj for v in self.adj[u] if u <= v)
 

@@ -30,6 +30,10 @@ def test_names_are_declared_exported_and_bound(gs):
     assert n in gs.EXPORTED_SYMBOLS and hasattr(ctypes.CDLL(gs.LIB_PATH), n)
     assert re.search(r"\bint %s\(void\* s, uint64_t\* out\);" % n, testing)
     assert getattr(L, n).argtypes
+    n = "gs_testing_spanner_generation"
+    assert n in gs.EXPORTED_SYMBOLS and hasattr(ctypes.CDLL(gs.LIB_PATH), n)
+    assert re.search(r"\bint %s\(void\* s, int64_t set, uint64_t\* out\);" % n, testing)
+    assert getattr(L, n).argtypes
     # the header says which k is rejected
     assert "1 <= k <= 16; any other k returns GS_ERR_INVALID" in text
 
@@ -56,6 +60,7 @@ def test_null_handles_and_pointers_are_rejected(gs):
         lambda: L.gs_spanner_get_stream(None, ctypes.byref(p)),
         lambda: L.gs_spanner_wait_stream(None, None),
         lambda: L.gs_testing_spanner_stats(None, ctypes.byref(w)),
+        lambda: L.gs_testing_spanner_generation(None, -1, ctypes.byref(w)),
     )
     for c in calls:
         assert c() == gs.GS_ERR_INVALID
@@ -82,7 +87,7 @@ def test_k_outside_the_range_is_rejected_before_any_device_call(gs):
 
 def test_python_class_has_the_methods(gs):
     for m in ("close", "reset", "sync", "wait_stream", "fold", "fold_device", "add", "within", "within_device", "combine",
-              "count", "edges", "edges_device", "neighbors", "stats", "__enter__", "__exit__"):
+              "count", "edges", "edges_device", "neighbors", "stats", "generation", "__enter__", "__exit__"):
         assert callable(getattr(gs.Spanner, m)), m
     assert isinstance(gs.Spanner.stream, property)
 
@@ -97,6 +102,8 @@ def test_spanner_constants_match_the_kernels(gs):
     assert gs.SPANNER_LDS_SET == int(re.search(r"constexpr uint32_t kSpannerLdsSet = (\d+);", seq).group(1))
     assert gs.SPANNER_ARENAS == int(re.search(r"constexpr uint32_t kSpannerArenas = (\d+);", hpp).group(1))
     assert gs.SPANNER_ROUND_CAP == int(re.search(r"constexpr uint32_t kSpannerRoundCap = (\d+);", hpp).group(1))
+    assert gs.SPANNER_TILE == int(re.search(r"constexpr uint32_t SPANNER_TILE = (\d+);", hpp).group(1)) == 1024
+    assert gs.SPANNER_MAX_GEN == int(re.search(r"constexpr uint32_t kSpMaxGen = (0x[0-9A-Fa-f]+)u;", seq).group(1), 16)
 
 
 def test_spanner_knobs_roundtrip(gs):
