@@ -1741,11 +1741,18 @@ class TriangleSampler(_ResetHandle):
         return ({"coins": out[0], "segments": out[1], "max_attempts": out[2], "rows": out[3]},
                 {"coin": out[4], "segments": out[5], "search": out[6], "rows": out[7]})
 
-    def tune(self, chunk=None, tile=None, profile=None, keys=None):
+    def tune(self, chunk=None, tile=None, profile=None, keys=None, piece=None, edge_count=None):
         """gs_testing_trisample_tune, per handle: the arrivals per workgroup of the coin pass and
-        of the search pass (at most TRISAMPLE_TILE), whether a fold times its phases, and the most
-        keys the resample list is first sized for. A value <= 0 restores the product value; None
-        leaves a control as it is."""
+        of the search pass (at most TRISAMPLE_TILE), whether a fold times its phases, the most
+        keys the resample list is first sized for, and the arrivals of one device piece of a fold
+        (at most TRISAMPLE_MAX_FOLD; a longer fold keeps no rows). A value <= 0 restores the
+        product value; None leaves a control as it is. `edge_count` is an action: it sets the
+        arrivals folded so far (0 .. TRISAMPLE_MAX_ARRIVALS) and nothing else, after which the
+        handle corresponds to no real stream -- only for tests right before the arrival limit."""
+        if piece is not None:
+            _check(lib().gs_testing_trisample_tune(self._h, 4, int(piece)))
+        if edge_count is not None:
+            _check(lib().gs_testing_trisample_tune(self._h, 5, int(edge_count)))
         if keys is not None:
             _check(lib().gs_testing_trisample_tune(self._h, 3, int(keys)))
         if profile is not None:

@@ -51,7 +51,7 @@ struct gs_trisample_s : StreamOwner {
   uint64_t rows = 0;
   bool rows_kept = true;  // false after a fold the library cut into pieces
   // gs_testing_trisample_tune (< 0: product) and gs_testing_trisample_stats
-  int64_t tune[4] = {-1, -1, -1, -1};
+  int64_t tune[5] = {-1, -1, -1, -1, -1};
   uint64_t stats[4] = {0, 0, 0, 0};
   uint64_t phase_us[4] = {0, 0, 0, 0};  // of the last profiled fold: coin, sort and segments, search, outcomes and rows
 };
@@ -60,8 +60,13 @@ namespace {
 
 constexpr const char* kWhat = "trisample";  // check_handle: "null trisample handle"
 
+// the arrivals of one device piece of a fold (gs_testing_trisample_tune, what = 4)
+uint64_t piece_of(const gs_trisample_s* h) {
+  return h->tune[4] > 0 ? (uint64_t)std::min<int64_t>(h->tune[4], (int64_t)gs::kTsMaxFold) : gs::kTsMaxFold;
+}
+
 int ensure_scratch(gs_trisample_s* h, uint64_t n) {
-  GS_HIP(grow_group(h->stream, h->n_cap, n, std::min<uint64_t>(gs::kTsMaxFold, n + n / 4), [&](uint64_t c) {
+  GS_HIP(grow_group(h->stream, h->n_cap, n, std::min(piece_of(h), n + n / 4), [&](uint64_t c) {
     hipError_t e = alloc_each(c, h->delta, h->chg_t, h->chg_beta, h->chg_est, h->row_t, h->row_est, h->row_beta);
     if (e == hipSuccess) e = alloc_each(gs::ts_row_tiles(c) + 1, h->tsum, h->tcnt);
     return e;
@@ -92,7 +97,7 @@ int fold_guard(gs_trisample_s* h, const void* src, const void* dst, size_t n) {
   return GS_OK;
 }
 
-// 0 < n <= kTsMaxFold device arrivals on h->stream
+// 0 < n <= piece_of(h) device arrivals on h->stream
 int fold_piece(gs_trisample_s* h, const int64_t* src, const int64_t* dst, uint64_t n, uint64_t stride) {
   hipStream_t st = h->stream;
   const uint32_t S = h->S, t0 = (uint32_t)h->folded, n32 = (uint32_t)n;
@@ -181,7 +186,7 @@ void forget_last(gs_trisample_s* h) {
   h->rows_kept = true;
 }
 
-// the whole fold, cut into pieces of at most kTsMaxFold arrivals; host: the arrays are HOST arrays
+// the whole fold, cut into pieces of at most piece_of(h) arrivals; host: the arrays are HOST arrays
 int fold_all(gs_trisample_s* h, const int64_t* src, const int64_t* dst, size_t n, uint64_t stride, bool host,
              size_t* rows) {
   forget_last(h);
@@ -189,11 +194,12 @@ int fold_all(gs_trisample_s* h, const int64_t* src, const int64_t* dst, size_t n
   if (n == 0) return GS_OK;
   DeviceGuard g(h->device);
   uint64_t sum[4] = {0, 0, 0, 0};
-  for (uint64_t at = 0; at < n; at += gs::kTsMaxFold) {
-    const uint64_t len = std::min<uint64_t>(gs::kTsMaxFold, n - at);
+  const uint64_t piece = piece_of(h);
+  for (uint64_t at = 0; at < n; at += piece) {
+    const uint64_t len = std::min<uint64_t>(piece, n - at);
     const int64_t *ps = src + at * stride, *pd = dst + at * stride;
     if (host) {
-      GS_HIP(grow_group(h->stream, h->h_cap, len, std::min<uint64_t>(gs::kTsMaxFold, len + len / 4),
+      GS_HIP(grow_group(h->stream, h->h_cap, len, std::min(piece, len + len / 4),
                         [&](uint64_t c) { return h->stage.alloc(2 * c); }));
       int64_t* s0 = h->stage;
       GS_HIP(hipMemcpyAsync(s0, ps, len * 8, hipMemcpyHostToDevice, h->stream));
@@ -207,7 +213,7 @@ int fold_all(gs_trisample_s* h, const int64_t* src, const int64_t* dst, size_t n
     sum[2] = std::max(sum[2], h->stats[2]);
     sum[3] += h->stats[3];
   }
-  if (n > gs::kTsMaxFold) {
+  if (n > piece) {
     std::copy(sum, sum + 4, h->stats);
     h->rows = 0;
     h->rows_kept = false;
@@ -354,8 +360,15 @@ int gs_testing_trisample_stats(void* handle, uint64_t* out) {
 
 int gs_testing_trisample_tune(void* handle, int what, int64_t value) {
   gs_trisample t = static_cast<gs_trisample>(handle);
+  // (the arguments first: they are checked without a handle, and so without a device)
+  if (what < 0 || what > 5) return fail(GS_ERR_INVALID, "trisample tune: unknown control");
+  if (what == 5 && (value < 0 || value > (int64_t)gs::kTsMaxArrivals))
+    return fail(GS_ERR_INVALID, "trisample tune: edge_count must be in 0 .. 2^31 - 1");
   if (int rc = check_handle(t, kWhat)) return rc;
-  if (what < 0 || what > 3) return fail(GS_ERR_INVALID, "trisample tune: unknown control");
+  if (what == 5) {  // an action: the arrival count alone
+    t->folded = (uint64_t)value;
+    return GS_OK;
+  }
   t->tune[what] = value <= 0 ? -1 : value;
   return GS_OK;
 }

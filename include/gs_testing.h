@@ -154,8 +154,17 @@ int gs_testing_trisample_stats(void* t, uint64_t* out);
  * what = 2 profile: bracket the four phases of a fold with events and wait for them (product: off;
  * needed by tools/trisample_bench.py), what = 3 the most keys the resample list is first sized for
  * (product: the expected count S (H(t0 + n) - H(t0)) plus eight deviations): a small value makes
- * the coin pass overflow the list, which is then grown to the count and the pass run again.
- * A value <= 0 restores the product value. Returns GS_OK or GS_ERR_INVALID. */
+ * the coin pass overflow the list, which is then grown to the count and the pass run again,
+ * what = 4 piece: the arrivals of one device piece of a fold (product: 2^20; clamped to 1..2^20):
+ * a longer fold is cut into pieces by the host, its stats are the sums (max_attempts: the maximum)
+ * over the pieces and its rows are not kept; the fold scratch and the staging of a host fold grow
+ * up to it. For what = 0..4 a value <= 0 restores the product value.
+ * what = 5 edge_count is an action, not a stored setting: the handle's arrival count becomes
+ * `value`, which must lie in 0..2^31 - 1 (GS_ERR_INVALID otherwise); the generators' states, the
+ * candidates, betaSum and the last estimate stay as they are. The handle afterwards corresponds to
+ * NO real stream: its only use is to put a fold right before the limit of 2^31 - 1 arrivals, as
+ * gs_testing_spanner_generation does for the spanner's stamp generations. A reset undoes it.
+ * Returns GS_OK or GS_ERR_INVALID (what outside 0..5 included). */
 int gs_testing_trisample_tune(void* t, int what, int64_t value);
 
 #ifdef __cplusplus

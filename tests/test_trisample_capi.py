@@ -90,6 +90,27 @@ def test_python_class_has_the_methods(gs):
     import inspect
     assert str(inspect.signature(gs.TriangleSampler.__init__)) == \
         "(self, samples=10000, vertices=1000, seed=-559038737, third_seed=0, device=0)"
+    assert str(inspect.signature(gs.TriangleSampler.tune)) == \
+        "(self, chunk=None, tile=None, profile=None, keys=None, piece=None, edge_count=None)"
+
+
+def test_tune_rejects_an_unknown_control_and_an_edge_count_out_of_range(gs):
+    """The controls are 0..5 (include/gs_testing.h); edge_count (5) takes 0 .. 2^31 - 1. The
+    arguments are checked before the handle, so this needs no device; a valid control on a null
+    handle still names the handle."""
+    L = gs.lib()
+    for what, value, word in ((6, 1, b"unknown control"), (-1, 1, b"unknown control"),
+                              (5, -1, b"edge_count"), (5, 1 << 31, b"edge_count")):
+        assert L.gs_testing_trisample_tune(None, what, value) == gs.GS_ERR_INVALID
+        assert word in L.gs_last_error(), (what, value)
+    for what, value in ((4, 16), (5, 0), (5, gs.TRISAMPLE_MAX_ARRIVALS)):
+        assert L.gs_testing_trisample_tune(None, what, value) == gs.GS_ERR_INVALID
+        assert b"null" in L.gs_last_error(), (what, value)
+    with open(os.path.join(ROOT, "include", "gs_testing.h")) as f:
+        testing = f.read()
+    for phrase in ("what = 4 piece", "what = 5 edge_count is an action", "NO real stream",
+                   "gs_testing_spanner_generation does"):
+        assert phrase in testing, phrase
 
 
 def test_trisample_constants_match_the_headers(gs):
