@@ -96,6 +96,11 @@ EXPORTED_SYMBOLS = (
     "gs_trisample_rows", "gs_trisample_rows_device", "gs_trisample_estimate", "gs_trisample_states",
     "gs_trisample_states_device", "gs_trisample_sync", "gs_trisample_get_stream", "gs_trisample_wait_stream",
     "gs_testing_trisample_stats", "gs_testing_trisample_tune",
+    "gs_degstream_create", "gs_degstream_destroy", "gs_degstream_reset", "gs_degstream_fold", "gs_degstream_fold_device",
+    "gs_degstream_rows", "gs_degstream_rows_device", "gs_degstream_records", "gs_degstream_records_device",
+    "gs_degstream_size", "gs_degstream_degrees", "gs_degstream_degrees_device", "gs_degstream_distribution",
+    "gs_degstream_distribution_device", "gs_degstream_sync", "gs_degstream_get_stream", "gs_degstream_wait_stream",
+    "gs_testing_degstream_stats", "gs_testing_degstream_tune",
 )
 
 # Pairs per workgroup of the component export's radix-sort kernels (csrc/gs_sort.hpp kSortTile):
@@ -180,6 +185,16 @@ TRISAMPLE_MAX_VERTICES = (1 << 31) - 1
 TRISAMPLE_MAX_ARRIVALS = (1 << 31) - 1
 TRISAMPLE_SEED = -559038737
 TRISAMPLE_MAX_FOLD = 1 << 20
+
+# The degree streams (csrc/gs_degstream.hpp, csrc/gs_degstream_seq.hpp): sorted positions per
+# workgroup of the two seeded segmented scans and of the record compaction (a segment that crosses
+# a multiple of it is joined through the scan of the tile aggregates), the count array's first
+# capacity in degrees, the occurrences a handle takes between resets and the edges of the largest
+# fold whose rows are kept.
+DEGSTREAM_TILE = 2048
+DEGSTREAM_MIN_COUNTS = 1024
+DEGSTREAM_MAX_TOTAL = (1 << 31) - 1
+DEGSTREAM_MAX_FOLD = 1 << 24
 
 FAIL_BIT = 1 << 62  # count words: a failed signed verdict (GS_FAIL_BIT)
 DIGEST_FAILED = (1 << 64) - 1  # gs_digest of a signed summary whose verdict failed (GS_DIGEST_FAILED)
@@ -410,6 +425,23 @@ def lib():
     L.gs_trisample_wait_stream.argtypes = [_vp, _vp]
     L.gs_testing_trisample_stats.argtypes = [_vp, ctypes.POINTER(_u64)]
     L.gs_testing_trisample_tune.argtypes = [_vp, ctypes.c_int, ctypes.c_int64]
+    L.gs_degstream_create.argtypes = [ctypes.POINTER(_vp), ctypes.c_int, ctypes.c_int, _u64]
+    L.gs_degstream_destroy.argtypes = [_vp]
+    L.gs_degstream_reset.argtypes = [_vp]
+    L.gs_degstream_fold.argtypes = [_vp, _vp, _vp, _vp, _sz]
+    L.gs_degstream_fold_device.argtypes = [_vp, _vp, _vp, _vp, _sz, _sz]
+    for name in ("rows", "records"):
+        getattr(L, "gs_degstream_" + name).argtypes = [_vp, _vp, _vp, _vp, _sz, ctypes.POINTER(_sz)]
+        getattr(L, "gs_degstream_" + name + "_device").argtypes = [_vp, _vp, _vp, _vp, _sz, ctypes.POINTER(_sz)]
+    for name in ("degrees", "distribution"):
+        getattr(L, "gs_degstream_" + name).argtypes = [_vp, _vp, _vp, _sz, ctypes.POINTER(_sz)]
+        getattr(L, "gs_degstream_" + name + "_device").argtypes = [_vp, _vp, _vp, _sz, ctypes.POINTER(_sz)]
+    L.gs_degstream_size.argtypes = [_vp, ctypes.POINTER(_u64)]
+    L.gs_degstream_sync.argtypes = [_vp]
+    L.gs_degstream_get_stream.argtypes = [_vp, ctypes.POINTER(_vp)]
+    L.gs_degstream_wait_stream.argtypes = [_vp, _vp]
+    L.gs_testing_degstream_stats.argtypes = [_vp, ctypes.POINTER(_u64)]
+    L.gs_testing_degstream_tune.argtypes = [_vp, ctypes.c_int, ctypes.c_int64]
     L.gs_testing_set.argtypes = [ctypes.c_int, _i64]
     L.gs_testing_get.argtypes = [ctypes.c_int]
     L.gs_testing_get.restype = _i64
@@ -1761,6 +1793,145 @@ class TriangleSampler(_ResetHandle):
             _check(lib().gs_testing_trisample_tune(self._h, 0, int(chunk)))
         if tile is not None:
             _check(lib().gs_testing_trisample_tune(self._h, 1, int(tile)))
+
+
+# ---------------------------------------------------------------- degree streams
+class DegreeStream(_ResetHandle):
+    """Every running degree and every distribution record of an edge stream (the gs_degstream_*
+    section of include/gs_summary.h): per endpoint occurrence the row (vertex, old, new) with
+    new = max(old + c, 0) -- SimpleEdgeStream.getDegrees / getInDegrees / getOutDegrees for
+    direction "all" / "in" / "out" -- and the (degree, count) records example/DegreeDistribution.java
+    emits at every change, exactly in arrival order however the stream is cut into folds.
+    `reset`: no vertex, every count 0; capacity is kept. Owns a gs_degstream handle."""
+
+    _PREFIX = "gs_degstream"
+
+    DIRECTIONS = {"all": DEGREE_ALL, "in": DEGREE_IN, "out": DEGREE_OUT}
+
+    def __init__(self, direction="all", device=0, vertex_hint=1 << 16):
+        self.dir = self.DIRECTIONS[direction] if isinstance(direction, str) else int(direction)
+        self.device = device
+        h = _vp()
+        _check(lib().gs_degstream_create(ctypes.byref(h), device, self.dir, int(vertex_hint)))
+        self._h = h
+
+    def fold(self, src, dst, deletions=None):
+        """Fold host edges (int64 arrays) in order; deletions: optional uint8 per edge, bit 0 =
+        deletion."""
+        s, d = _edges(src, dst)
+        e = None
+        if deletions is not None:
+            e = np.ascontiguousarray(np.asarray(deletions, dtype=np.uint8))
+            assert e.shape == s.shape
+        _check(lib().gs_degstream_fold(self._h, s.ctypes.data, d.ctypes.data, _ptr(e), len(s)))
+
+    def fold_device(self, src, dst, n=None, stride=1, deletions=None, after=None):
+        """Fold device-resident edges (torch tensors on this device or raw pointers), element i at
+        index i * stride, deletions[i] its deletion byte; `after`: a stream the arrays were written
+        on. The fold synchronises with the host once."""
+        if n is None:
+            n = (src.numel() + stride - 1) // stride
+        if after is not None:
+            self.wait_stream(after)
+        _check(lib().gs_degstream_fold_device(self._h, _ptr(src), _ptr(dst), _ptr(deletions), int(n), int(stride)))
+
+    def size(self):
+        """gs_degstream_size. No device call."""
+        out = (_u64 * 5)()
+        _check(lib().gs_degstream_size(self._h, out))
+        return {"vertices": out[0], "occurrences": out[1], "records": out[2], "total": out[3], "max_degree": out[4]}
+
+    def rows(self):
+        """The last fold's degree rows as numpy arrays (vertex int64, old uint32, new uint32), one
+        per endpoint occurrence in arrival order."""
+        got = _sz()
+        n = max(self.size()["occurrences"], 1)
+        v = np.empty(n, np.int64)
+        o, w = (np.empty(n, np.uint32) for _ in range(2))
+        _check(lib().gs_degstream_rows(self._h, v.ctypes.data, o.ctypes.data, w.ctypes.data, n, ctypes.byref(got)))
+        k = got.value
+        return v[:k].copy(), o[:k].copy(), w[:k].copy()
+
+    def rows_device(self, vertex, old, new):
+        """The same rows into DEVICE arrays (capacity of the first one given; any may be None);
+        returns the row count."""
+        got = _sz()
+        _check(lib().gs_degstream_rows_device(self._h, _ptr(vertex), _ptr(old), _ptr(new), _cap_of(None, vertex, old, new),
+                                              ctypes.byref(got)))
+        return got.value
+
+    def records(self):
+        """The last fold's distribution records as numpy uint32 arrays (occurrence index in the
+        fold, degree, count after the record), in arrival order."""
+        got = _sz()
+        n = max(self.size()["records"], 1)
+        o, d, c = (np.empty(n, np.uint32) for _ in range(3))
+        _check(lib().gs_degstream_records(self._h, o.ctypes.data, d.ctypes.data, c.ctypes.data, n, ctypes.byref(got)))
+        k = got.value
+        return o[:k].copy(), d[:k].copy(), c[:k].copy()
+
+    def records_device(self, occurrence, degree, count):
+        """The same records into DEVICE uint32 arrays; returns the record count."""
+        got = _sz()
+        _check(lib().gs_degstream_records_device(self._h, _ptr(occurrence), _ptr(degree), _ptr(count),
+                                                 _cap_of(None, occurrence, degree, count), ctypes.byref(got)))
+        return got.value
+
+    def _state(self, name, sort):
+        got = _sz()
+        rc = getattr(lib(), name)(self._h, None, None, 0, ctypes.byref(got))
+        if rc != GS_ERR_TRUNCATED:  # (the row count of a state with rows)
+            _check(rc)
+        n = max(got.value, 1)
+        a, b = (np.empty(n, np.int64) for _ in range(2))
+        _check(getattr(lib(), name)(self._h, a.ctypes.data, b.ctypes.data, n, ctypes.byref(got)))
+        a, b = a[:got.value].copy(), b[:got.value].copy()
+        if sort:
+            order = np.argsort(a, kind="stable")
+            a, b = a[order], b[order]
+        return a, b
+
+    def degrees(self, sorted=True):
+        """(vertex, degree) numpy int64 arrays of the vertices with degree > 0: ascending by vertex
+        (sorted on the host), or in first-seen order."""
+        return self._state("gs_degstream_degrees", sorted)
+
+    def degrees_device(self, vertex, degree):
+        """The same rows, in first-seen order, into DEVICE int64 arrays; returns the row count."""
+        got = _sz()
+        _check(lib().gs_degstream_degrees_device(self._h, _ptr(vertex), _ptr(degree), _cap_of(None, vertex, degree),
+                                                 ctypes.byref(got)))
+        return got.value
+
+    def distribution(self):
+        """(degree, count) numpy int64 arrays: the degrees with count > 0, ascending."""
+        return self._state("gs_degstream_distribution", False)
+
+    def distribution_device(self, degree, count):
+        """The distribution into DEVICE int64 arrays; returns its length."""
+        got = _sz()
+        _check(lib().gs_degstream_distribution_device(self._h, _ptr(degree), _ptr(count), _cap_of(None, degree, count),
+                                                      ctypes.byref(got)))
+        return got.value
+
+    def stats(self):
+        """gs_testing_degstream_stats: the last fold (synchronises)."""
+        return self.phases()[0]
+
+    def phases(self):
+        """(stats, microseconds of the last fold's ranks and keys, sort by rank, clamped scan with
+        the record counts and the control read, record rows with the sort by degree, seeded sum):
+        the times are zero unless tune(profile=True)."""
+        out = (_u64 * 9)()
+        _check(lib().gs_testing_degstream_stats(self._h, out))
+        return ({"tiles": out[0], "crossed": out[1], "count_capacity": out[2], "count_growths": out[3]},
+                {"ranks": out[4], "sort_rank": out[5], "scan": out[6], "sort_degree": out[7], "sum": out[8]})
+
+    def tune(self, profile=None):
+        """gs_testing_degstream_tune, per handle: whether a fold times its phases (and then waits
+        for the handle's stream a second time). None leaves the control as it is."""
+        if profile is not None:
+            _check(lib().gs_testing_degstream_tune(self._h, 0, 1 if profile else -1))
 
 
 # ---------------------------------------------------------------- native multi-GPU group

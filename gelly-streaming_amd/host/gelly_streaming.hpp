@@ -907,6 +907,66 @@ class SimpleEdgeStream {
   // numberOfEdges (SimpleEdgeStream.java:388-404): a host count.
   long numberOfEdges() const { return (long)edges_.edges.size(); }
 
+  // The continuous forms: every value the reference's operators emit, in arrival order, where
+  // the members above return the last one. The stream's edges are folded through a degstream
+  // handle (gs_summary.h, the gs_degstream_* section) on `device`.
+  // getDegreeStream: the running Vertex<K, Long> of every endpoint occurrence (DegreeMapFunction,
+  // SimpleEdgeStream.java:461-478); direction ALL / IN / OUT as getDegrees / getInDegrees /
+  // getOutDegrees.
+  std::vector<Vertex<K, long>> getDegreeStream(EdgeDirection direction = EdgeDirection::ALL, int device = 0) const {
+    DegstreamHandle h(device, degree_dir(direction), edges_.edges.size());
+    fold_degstream(h.d, std::vector<uint8_t>());
+    uint64_t size[5] = {0, 0, 0, 0, 0};
+    gs_check(gs_degstream_size(h.d, size));
+    std::vector<int64_t> v(size[1] + 1);
+    std::vector<uint32_t> deg(size[1] + 1);
+    size_t got = 0;
+    gs_check(gs_degstream_rows(h.d, v.data(), nullptr, deg.data(), v.size(), &got));
+    std::vector<Vertex<K, long>> out(got);
+    for (size_t i = 0; i < got; ++i) out[i] = Vertex<K, long>{(K)v[i], (long)deg[i]};
+    return out;
+  }
+
+  // degreeDistributionStream: the (degree, count) record example/DegreeDistribution.java emits at
+  // every change (DegreeDistribution.java:84-132), in arrival order. deletions: empty (every edge
+  // an addition) or one byte per edge, bit 0 = deletion (EventType).
+  std::vector<std::pair<long, long>> degreeDistributionStream(const std::vector<uint8_t>& deletions = {},
+                                                              int device = 0) const {
+    if (!deletions.empty() && deletions.size() != edges_.edges.size())
+      throw GsException(GS_ERR_INVALID, "degreeDistributionStream: one deletion byte per edge");
+    DegstreamHandle h(device, GS_DEGREE_ALL, edges_.edges.size());
+    fold_degstream(h.d, deletions);
+    uint64_t size[5] = {0, 0, 0, 0, 0};
+    gs_check(gs_degstream_size(h.d, size));
+    std::vector<uint32_t> deg(size[2] + 1), cnt(size[2] + 1);
+    size_t got = 0;
+    gs_check(gs_degstream_records(h.d, nullptr, deg.data(), cnt.data(), deg.size(), &got));
+    std::vector<std::pair<long, long>> out(got);
+    for (size_t i = 0; i < got; ++i) out[i] = std::make_pair((long)deg[i], (long)cnt[i]);
+    return out;
+  }
+
+  // numberOfVerticesStream (SimpleEdgeStream.java:366-386): GlobalAggregateMapper over
+  // VertexCountMapper emits k at the k-th first-seen endpoint. The first-seen endpoints are the
+  // distinct handle's new vertices.
+  std::vector<long> numberOfVerticesStream(int device = 0) const {
+    DistinctHandle h(device, edges_.edges.size());
+    fold_distinct(h.d);
+    size_t got = 0;
+    const int rc = gs_distinct_new_vertices(h.d, nullptr, nullptr, 0, &got);
+    if (rc != GS_ERR_TRUNCATED) gs_check(rc);
+    std::vector<long> out(got);
+    for (size_t k = 0; k < got; ++k) out[k] = (long)(k + 1);
+    return out;
+  }
+
+  // numberOfEdgesStream (SimpleEdgeStream.java:388-404): the running count 1..n, one per edge.
+  std::vector<long> numberOfEdgesStream() const {
+    std::vector<long> out(edges_.edges.size());
+    for (size_t i = 0; i < out.size(); ++i) out[i] = (long)(i + 1);
+    return out;
+  }
+
   // distinct (SimpleEdgeStream.java:301-323): the stream of first-seen (source, target) pairs,
   // each with the value and timestamp of its first occurrence, in arrival order. The documented
   // and pinned behaviour (TestDistinct.java:38-44), not DistinctEdgeMapper's single set of
@@ -966,6 +1026,28 @@ class SimpleEdgeStream {
       dst[i] = (int64_t)edges_.edges[i].getTarget();
     }
     gs_check(gs_distinct_fold(d, src.data(), dst.data(), n));
+  }
+
+  struct DegstreamHandle {
+    gs_degstream d = nullptr;
+    DegstreamHandle(int device, int dir, size_t edges) { gs_check(gs_degstream_create(&d, device, dir, 2 * edges)); }
+    ~DegstreamHandle() { gs_degstream_destroy(d); }
+    DegstreamHandle(const DegstreamHandle&) = delete;
+    DegstreamHandle& operator=(const DegstreamHandle&) = delete;
+  };
+
+  static int degree_dir(EdgeDirection direction) {
+    return direction == EdgeDirection::IN ? GS_DEGREE_IN : direction == EdgeDirection::OUT ? GS_DEGREE_OUT : GS_DEGREE_ALL;
+  }
+
+  void fold_degstream(gs_degstream d, const std::vector<uint8_t>& deletions) const {
+    const size_t n = edges_.edges.size();
+    std::vector<int64_t> src(n), dst(n);
+    for (size_t i = 0; i < n; ++i) {
+      src[i] = (int64_t)edges_.edges[i].getSource();
+      dst[i] = (int64_t)edges_.edges[i].getTarget();
+    }
+    gs_check(gs_degstream_fold(d, src.data(), dst.data(), deletions.empty() ? nullptr : deletions.data(), n));
   }
 
   struct DegreeHandle {

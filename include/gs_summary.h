@@ -881,6 +881,87 @@ int gs_trisample_sync(gs_trisample t);
 int gs_trisample_get_stream(gs_trisample t, void** stream);
 int gs_trisample_wait_stream(gs_trisample t, void* stream);
 
+/* ---- degree streams ------------------------------------------------------------------
+ * Every value the reference's degree operators emit, not only the last one: the running
+ * Vertex<K, Long> of SimpleEdgeStream.getDegrees / getInDegrees / getOutDegrees
+ * (DegreeMapFunction, SimpleEdgeStream.java:461-478) and the (degree, count) record that
+ * example/DegreeDistribution.java emits at every change (DegreeDistribution.java:84-132).
+ *
+ * A degstream handle is its own opaque type with its own create call; its direction
+ * (gs_degree_dir) is fixed at create. Every id is legal, INT64_MIN and INT64_MAX included.
+ *   occurrences  the collected endpoints of a fold in arrival order: for edge i the source
+ *                (GS_DEGREE_OUT or _ALL), then the target (GS_DEGREE_IN or _ALL); a self-loop
+ *                gives two occurrences of one vertex under _ALL. An endpoint that is not
+ *                collected is neither looked up nor inserted. An occurrence carries c = +1, or
+ *                c = -1 when bit 0 of the edge's deletion byte is set; d is the vertex's
+ *                degree before it, 0 while the vertex is absent.
+ *   rows         old = d, new = max(d + c, 0); the row is (vertex, old, new). A vertex is
+ *                present iff d > 0 and an absent vertex forgets a deletion -- the reference's
+ *                clamp at removal (VertexDegreeCounts), which the degree summary's net counts
+ *                do not have. Without deletions `new` is what DegreeMapFunction emits.
+ *   records      per occurrence, in this order: old > 0: (new, +1) if new > 0, then (old, -1);
+ *                old == 0 and c > 0: (1, +1); old == 0 and c < 0: none. Taken in arrival
+ *                order, count[degree] += delta and the record's row is (occurrence index in
+ *                the fold, degree, count[degree]). A count may reach 0 and is then emitted as
+ *                0; it never falls below.
+ * The rows and records are a function of the stream order alone, however the stream is cut
+ * into folds: the fold runs in parallel (two stable sorts and two seeded segmented scans,
+ * DESIGN.md section 6i) and is exact to that order.
+ *
+ * Overflow: the handle keeps the occurrences folded since the last reset; a fold that would
+ * take them past 2^31 - 1 fails with GS_ERR_CAPACITY before any work, so no degree or count
+ * can wrap.
+ *
+ * Synchronisation: a fold waits for the handle's stream once (new vertices, record count,
+ * largest new degree, error word); the record sort and sum behind it are queued. Every
+ * allocation is counted by gs_hbm_bytes and released by gs_degstream_destroy. Null handles and
+ * pointers return GS_ERR_INVALID before any device call.
+ *
+ * gs_degstream_create: dir is a gs_degree_dir; vertex_hint sizes the first allocation only.
+ * gs_degstream_reset: no vertex, every count 0, no occurrence folded; capacity kept.
+ * gs_degstream_fold / _fold_device: n edges from HOST arrays (copied before the call returns) /
+ *   DEVICE arrays read on the handle's stream, element i = src[i*stride], dst[i*stride], del[i];
+ *   del may be NULL (every edge an addition). The largest fold whose rows are kept has 2^24
+ *   edges; a longer one is cut into pieces by the library, with the same state afterwards, and
+ *   gs_degstream_rows / _records return GS_ERR_INVALID until the next fold.
+ * gs_degstream_rows / _rows_device: the last fold's (vertex, old, new) per occurrence into HOST /
+ *   DEVICE arrays of capacity cap (any array may be NULL); *n = the rows. cap < rows:
+ *   GS_ERR_TRUNCATED, *n set, nothing written.
+ * gs_degstream_records / _records_device: the last fold's (occurrence, degree, count) per
+ *   record, in arrival order; cap and n as for rows.
+ * gs_degstream_size: out[0..4] = new vertices, occurrences and records of the last fold, the
+ *   occurrences since reset, the largest degree since reset. No device call.
+ * gs_degstream_degrees / _degrees_device: the current (vertex, degree) rows with degree > 0, in
+ *   first-seen order; gs_degstream_distribution / _distribution_device: the current (degree,
+ *   count) rows with count > 0, ascending by degree. *n on the host (synchronises); capacity
+ *   rule as above.
+ * gs_degstream_sync / _get_stream / _wait_stream: as gs_sync / gs_get_stream / gs_wait_stream.
+ * Not built: combine, serialization, multi-GPU groups, parallelism above 1 (where the order of
+ * records across keys is Flink's). */
+typedef struct gs_degstream_s* gs_degstream;
+int gs_degstream_create(gs_degstream* out, int device, int dir, uint64_t vertex_hint);
+int gs_degstream_destroy(gs_degstream d); /* NULL is GS_OK */
+int gs_degstream_reset(gs_degstream d);
+int gs_degstream_fold(gs_degstream d, const int64_t* src, const int64_t* dst, const uint8_t* del, size_t n);
+int gs_degstream_fold_device(gs_degstream d, const int64_t* src, const int64_t* dst, const uint8_t* del, size_t n,
+                             size_t stride);
+int gs_degstream_rows(gs_degstream d, int64_t* vertex, uint32_t* old_degree, uint32_t* new_degree, size_t cap,
+                      size_t* n);
+int gs_degstream_rows_device(gs_degstream d, int64_t* vertex, uint32_t* old_degree, uint32_t* new_degree, size_t cap,
+                             size_t* n);
+int gs_degstream_records(gs_degstream d, uint32_t* occurrence, uint32_t* degree, uint32_t* count, size_t cap,
+                         size_t* n);
+int gs_degstream_records_device(gs_degstream d, uint32_t* occurrence, uint32_t* degree, uint32_t* count, size_t cap,
+                                size_t* n);
+int gs_degstream_size(gs_degstream d, uint64_t* out);
+int gs_degstream_degrees(gs_degstream d, int64_t* vertex, int64_t* degree, size_t cap, size_t* n);
+int gs_degstream_degrees_device(gs_degstream d, int64_t* vertex, int64_t* degree, size_t cap, size_t* n);
+int gs_degstream_distribution(gs_degstream d, int64_t* degree, int64_t* count, size_t cap, size_t* n);
+int gs_degstream_distribution_device(gs_degstream d, int64_t* degree, int64_t* count, size_t cap, size_t* n);
+int gs_degstream_sync(gs_degstream d);
+int gs_degstream_get_stream(gs_degstream d, void** stream);
+int gs_degstream_wait_stream(gs_degstream d, void* stream);
+
 /* ---- introspection -----------------------------------------------------------
  * The HIP stream (hipStream_t) the handle enqueues on, and per-kernel timing:
  * when profiling is on, every launch is bracketed by HIP events on the stream it

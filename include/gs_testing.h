@@ -167,6 +167,23 @@ int gs_testing_trisample_stats(void* t, uint64_t* out);
  * Returns GS_OK or GS_ERR_INVALID (what outside 0..5 included). */
 int gs_testing_trisample_tune(void* t, int what, int64_t value);
 
+/* The last fold of a degstream handle (`d` is a gs_degstream; synchronises; zero after a reset
+ * but the last two words): out[0] = tiles of the occurrence scan, out[1] = tiles of the fold's
+ * two scans (occurrences by vertex, records by degree) that began inside a segment, so that the
+ * segment's carry crossed a tile boundary, out[2] = the count array's capacity in degrees (first
+ * capacity: 1024), out[3] = growths of the count array since create; out[4..8] = microseconds of
+ * the fold's five phases -- ranks and keys, the sort by rank, the clamped scan with the record
+ * counts and the control read, the record rows with the sort by degree, the seeded sum -- zero
+ * unless the handle's profile control is on. Nine words. */
+int gs_testing_degstream_stats(void* d, uint64_t* out);
+
+/* Per-handle control of a degstream handle's folds (`d` is a gs_degstream; not a knob of
+ * gs_testing_set): what = 0 profile: bracket the five phases of a fold with events and wait for
+ * them, so that the fold ends with a second wait (product: off; needed by
+ * tools/degstream_bench.py). A value <= 0 restores the product value. Returns GS_OK or
+ * GS_ERR_INVALID. */
+int gs_testing_degstream_tune(void* d, int what, int64_t value);
+
 #ifdef __cplusplus
 }
 #endif

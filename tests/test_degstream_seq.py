@@ -1,0 +1,80 @@
+"""CPU: the degree streams' rules header (csrc/gs_degstream_seq.hpp: the maps x -> max(x + a, b),
+their composition, the segmented combine, the record rule, the sequential definition ds_fold_seq
+and the kernels' decomposition ds_fold_parts) in a stand-alone program built with the address and
+undefined-behaviour sanitizers (tests/cpp/degstream_seq_sanitize.cpp): ds_fold_seq against brute
+force, ds_fold_parts against ds_fold_seq at every tile size and every cut, and the pins of
+tests/golden/degree_pins.json in order. The header is the one the kernels include."""
+import json
+import os
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "gelly-streaming_amd", "csrc")
+
+
+def _pins_text():
+    """The pins as the program reads them: '#name count' and then count lines."""
+    with open(os.path.join(ROOT, "tests", "golden", "degree_pins.json")) as f:
+        pins = json.load(f)
+    sections = {"sample_edges": ["%d %d +" % (s, t) for s, t, _ in pins["sample_edges"]["edges"]]}
+    for name in ("get_degrees", "get_in_degrees", "get_out_degrees"):
+        sections[name] = pins[name]["lines"]
+    for name in ("degrees_data", "degrees_result", "degrees_data_zero", "degrees_result_zero"):
+        sections[name] = pins[name]["text"].split("\n")
+    return "".join("#%s %d\n%s\n" % (k, len(v), "\n".join(v)) for k, v in sections.items())
+
+
+def test_rules_and_decomposition_under_address_and_undefined_sanitizers(tmp_path):
+    if shutil.which("g++") is None:
+        pytest.skip("g++ not available")
+    exe = str(tmp_path / "degstream_seq_san")
+    build = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined",
+                            "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-I" + CSRC,
+                            os.path.join(ROOT, "tests", "cpp", "degstream_seq_sanitize.cpp"), "-o", exe],
+                           capture_output=True, text=True, timeout=300)
+    assert build.returncode == 0, build.stderr[-3000:]
+    pins = tmp_path / "pins.txt"
+    pins.write_text(_pins_text())
+    # a preloaded library may precede the ASan runtime: do not treat that as an error
+    env = dict(os.environ, ASAN_OPTIONS="verify_asan_link_order=0:detect_leaks=1:abort_on_error=0",
+               UBSAN_OPTIONS="print_stacktrace=1")
+    run = subprocess.run([exe, str(pins)], capture_output=True, text=True, timeout=300, env=env)
+    assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-4000:]
+    assert "all checks passed" in run.stdout
+    assert "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr, run.stderr[-4000:]
+
+
+def test_kernels_and_host_include_the_checked_header():
+    with open(os.path.join(CSRC, "gs_degstream.hpp")) as f:
+        hpp = f.read()
+    assert '#include "gs_degstream_seq.hpp"' in hpp and '#include "gs_distinct.hpp"' in hpp
+    with open(os.path.join(CSRC, "gs_degstream_k.hip")) as f:
+        text = f.read()
+    assert '#include "gs_degstream.hpp"' in text and '#include "gs_scan.hpp"' in text
+    for fn in ("ds_seg_combine(", "ds_seg_element(", "ds_seg_before(", "ds_seg_identity(", "ds_apply(",
+               "ds_record_count(", "ds_record(", "ds_sign(", "ds_occ_edge(", "ds_occ_is_dst(", "ds_occurrences(",
+               "ds_tiles(", "block_excl_scan<", "block_count_to<"):
+        assert fn in text, fn
+    with open(os.path.join(CSRC, "gs_degstream.cpp")) as f:
+        host = f.read()
+    assert '#include "gs_degstream.hpp"' in host and '#include "gs_vtable.hpp"' in host
+    for fn in ("kDsMaxTotal", "kDsMaxFold", "ds_occurrences(", "ds_count_cap(", "launch_dist_vertices(",
+               "launch_tile_scan(", "sort_run(", "launch_sort_digits_one(", "grow_group(", "check_handle(",
+               "GS_LAUNCH(", ": StreamOwner, VertexTable"):
+        assert fn in host, fn
+    # the definition and the decomposition are made of the same rules
+    with open(os.path.join(CSRC, "gs_degstream_seq.hpp")) as f:
+        seq = f.read()
+    for fn in ("ds_apply(", "ds_element(", "ds_record_count(", "ds_record(", "ds_seg_combine(", "ds_seg_before("):
+        assert seq.count(fn) >= 2, fn
+    assert "inline void ds_fold_seq(" in seq and "inline uint64_t ds_fold_parts(" in seq
+    # no second open-addressing insert: the vertex table is the distinct streams'
+    assert "atomicCAS" not in text and "atomicCAS" not in host
+    # no workgroup waits on another: no spin, no grid-wide barrier
+    assert "while (" not in text and "cooperative" not in text
+    # the header itself reads standard headers only (and the HIP runtime under a HIP compiler)
+    incs = [ln.split()[1] for ln in seq.splitlines() if ln.startswith("#include")]
+    assert all(i.startswith("<") for i in incs), incs
