@@ -101,6 +101,10 @@ EXPORTED_SYMBOLS = (
     "gs_degstream_size", "gs_degstream_degrees", "gs_degstream_degrees_device", "gs_degstream_distribution",
     "gs_degstream_distribution_device", "gs_degstream_sync", "gs_degstream_get_stream", "gs_degstream_wait_stream",
     "gs_testing_degstream_stats", "gs_testing_degstream_tune",
+    "gs_tristream_create", "gs_tristream_destroy", "gs_tristream_reset", "gs_tristream_fold", "gs_tristream_fold_device",
+    "gs_tristream_rows", "gs_tristream_rows_device", "gs_tristream_records", "gs_tristream_records_device",
+    "gs_tristream_size", "gs_tristream_count", "gs_tristream_counts", "gs_tristream_counts_device", "gs_tristream_sync",
+    "gs_tristream_get_stream", "gs_tristream_wait_stream", "gs_testing_tristream_stats", "gs_testing_tristream_tune",
 )
 
 # Pairs per workgroup of the component export's radix-sort kernels (csrc/gs_sort.hpp kSortTile):
@@ -195,6 +199,21 @@ DEGSTREAM_TILE = 2048
 DEGSTREAM_MIN_COUNTS = 1024
 DEGSTREAM_MAX_TOTAL = (1 << 31) - 1
 DEGSTREAM_MAX_FOLD = 1 << 24
+
+# The triangle streams (csrc/gs_tristream.hpp, csrc/gs_tristream_seq.hpp): positions per workgroup
+# of the scan over the arrivals and of the seeded segmented sum over the records (a segment that
+# crosses a multiple of it is joined through the scan of the tile aggregates), the arrivals a
+# handle takes between resets, the arrivals of the largest fold whose rows are kept, the records
+# one fold may emit, and how a repeated pair is treated (gs_tristream_repeats); the lanes that share
+# one arrival's walked row in the intersection while that row has at most TRISTREAM_SHORT_ROW
+# entries (a longer one takes a wave of 64).
+TRISTREAM_TILE = 2048
+TRISTREAM_LANES = 8
+TRISTREAM_SHORT_ROW = 32
+TRISTREAM_MAX_TOTAL = (1 << 31) - 1
+TRISTREAM_MAX_FOLD = 1 << 22
+TRISTREAM_MAX_RECORDS = 1 << 27
+TRISTREAM_REPEATS = {"count": 0, "ignore": 1}
 
 FAIL_BIT = 1 << 62  # count words: a failed signed verdict (GS_FAIL_BIT)
 DIGEST_FAILED = (1 << 64) - 1  # gs_digest of a signed summary whose verdict failed (GS_DIGEST_FAILED)
@@ -442,6 +461,23 @@ def lib():
     L.gs_degstream_wait_stream.argtypes = [_vp, _vp]
     L.gs_testing_degstream_stats.argtypes = [_vp, ctypes.POINTER(_u64)]
     L.gs_testing_degstream_tune.argtypes = [_vp, ctypes.c_int, ctypes.c_int64]
+    L.gs_tristream_create.argtypes = [ctypes.POINTER(_vp), ctypes.c_int, ctypes.c_int, _u64]
+    L.gs_tristream_destroy.argtypes = [_vp]
+    L.gs_tristream_reset.argtypes = [_vp]
+    L.gs_tristream_fold.argtypes = [_vp, _vp, _vp, _sz]
+    L.gs_tristream_fold_device.argtypes = [_vp, _vp, _vp, _sz, _sz]
+    for name in ("rows", "counts"):
+        getattr(L, "gs_tristream_" + name).argtypes = [_vp, _vp, _vp, _sz, ctypes.POINTER(_sz)]
+        getattr(L, "gs_tristream_" + name + "_device").argtypes = [_vp, _vp, _vp, _sz, ctypes.POINTER(_sz)]
+    L.gs_tristream_records.argtypes = [_vp, _vp, _vp, _vp, _sz, ctypes.POINTER(_sz)]
+    L.gs_tristream_records_device.argtypes = [_vp, _vp, _vp, _vp, _sz, ctypes.POINTER(_sz)]
+    L.gs_tristream_size.argtypes = [_vp, ctypes.POINTER(_u64)]
+    L.gs_tristream_count.argtypes = [_vp, ctypes.POINTER(_u64)]
+    L.gs_tristream_sync.argtypes = [_vp]
+    L.gs_tristream_get_stream.argtypes = [_vp, ctypes.POINTER(_vp)]
+    L.gs_tristream_wait_stream.argtypes = [_vp, _vp]
+    L.gs_testing_tristream_stats.argtypes = [_vp, ctypes.POINTER(_u64)]
+    L.gs_testing_tristream_tune.argtypes = [_vp, ctypes.c_int, ctypes.c_int64]
     L.gs_testing_set.argtypes = [ctypes.c_int, _i64]
     L.gs_testing_get.argtypes = [ctypes.c_int]
     L.gs_testing_get.restype = _i64
@@ -1932,6 +1968,130 @@ class DegreeStream(_ResetHandle):
         for the handle's stream a second time). None leaves the control as it is."""
         if profile is not None:
             _check(lib().gs_testing_degstream_tune(self._h, 0, 1 if profile else -1))
+
+
+# ---------------------------------------------------------------- triangle streams
+class TriangleStream(_ResetHandle):
+    """Every record of example/ExactTriangleCount.java's continuous stream (the gs_tristream_*
+    section of include/gs_summary.h): per arrival that closes c > 0 triangles the records
+    (w, t(w) += 1) for every common neighbour w ascending, then (u, t(u) += c), (v, t(v) += c),
+    and the row (closed, total); exactly in arrival order however the stream is cut into folds.
+    repeats="count" (the reference) intersects a repeated pair again, "ignore" gives it c = 0.
+    `reset`: G empty, every counter 0; capacity is kept. Owns a gs_tristream handle."""
+
+    _PREFIX = "gs_tristream"
+
+    def __init__(self, repeats="count", edge_hint=0, device=0):
+        self.repeats = TRISTREAM_REPEATS[repeats] if isinstance(repeats, str) else int(repeats)
+        self.device = device
+        h = _vp()
+        _check(lib().gs_tristream_create(ctypes.byref(h), device, self.repeats, int(edge_hint)))
+        self._h = h
+
+    def fold(self, src, dst):
+        """Fold host arrivals (int64 arrays) in order."""
+        s, d = _edges(src, dst)
+        _check(lib().gs_tristream_fold(self._h, s.ctypes.data, d.ctypes.data, len(s)))
+
+    def fold_device(self, src, dst, n=None, stride=1, after=None):
+        """Fold device-resident arrivals (torch tensors on this device or raw pointers), element i
+        at index i * stride; `after`: a stream the arrays were written on. The fold synchronises
+        with the host twice."""
+        if n is None:
+            n = (src.numel() + stride - 1) // stride
+        if after is not None:
+            self.wait_stream(after)
+        _check(lib().gs_tristream_fold_device(self._h, _ptr(src), _ptr(dst), int(n), int(stride)))
+
+    def size(self):
+        """gs_tristream_size. No device call."""
+        out = (_u64 * 4)()
+        _check(lib().gs_tristream_size(self._h, out))
+        return {"arrivals": out[0], "records": out[1], "new_pairs": out[2], "total": out[3]}
+
+    def count(self):
+        """gs_tristream_count: T, |G|, the vertices of G, the arrivals since reset (synchronises)."""
+        out = (_u64 * 4)()
+        _check(lib().gs_tristream_count(self._h, out))
+        return {"triangles": out[0], "edges": out[1], "vertices": out[2], "arrivals": out[3]}
+
+    def rows(self):
+        """The last fold's rows as numpy arrays (closed uint32, total int64), one per arrival."""
+        got = _sz()
+        n = max(self.size()["arrivals"], 1)
+        c = np.empty(n, np.uint32)
+        t = np.empty(n, np.int64)
+        _check(lib().gs_tristream_rows(self._h, c.ctypes.data, t.ctypes.data, n, ctypes.byref(got)))
+        k = got.value
+        return c[:k].copy(), t[:k].copy()
+
+    def rows_device(self, closed, total):
+        """The same rows into DEVICE arrays (capacity of the first one given; either may be None);
+        returns the row count."""
+        got = _sz()
+        _check(lib().gs_tristream_rows_device(self._h, _ptr(closed), _ptr(total), _cap_of(None, closed, total),
+                                              ctypes.byref(got)))
+        return got.value
+
+    def records(self):
+        """The last fold's records as numpy arrays (arrival index in the fold uint32, vertex int64,
+        count int64), in emission order."""
+        got = _sz()
+        n = max(self.size()["records"], 1)
+        a = np.empty(n, np.uint32)
+        v, c = (np.empty(n, np.int64) for _ in range(2))
+        _check(lib().gs_tristream_records(self._h, a.ctypes.data, v.ctypes.data, c.ctypes.data, n, ctypes.byref(got)))
+        k = got.value
+        return a[:k].copy(), v[:k].copy(), c[:k].copy()
+
+    def records_device(self, arrival, vertex, count):
+        """The same records into DEVICE arrays; returns the record count."""
+        got = _sz()
+        _check(lib().gs_tristream_records_device(self._h, _ptr(arrival), _ptr(vertex), _ptr(count),
+                                                 _cap_of(None, arrival, vertex, count), ctypes.byref(got)))
+        return got.value
+
+    def local_counts(self):
+        """(vertex, t) numpy int64 arrays of the vertices with t > 0, ascending by vertex."""
+        got = _sz()
+        rc = lib().gs_tristream_counts(self._h, None, None, 0, ctypes.byref(got))
+        if rc != GS_ERR_TRUNCATED:  # (the row count of a state with rows)
+            _check(rc)
+        n = max(got.value, 1)
+        v, c = (np.empty(n, np.int64) for _ in range(2))
+        _check(lib().gs_tristream_counts(self._h, v.ctypes.data, c.ctypes.data, n, ctypes.byref(got)))
+        return v[:got.value].copy(), c[:got.value].copy()
+
+    def local_counts_device(self, vertex, count):
+        """The same rows into DEVICE int64 arrays; returns the row count."""
+        got = _sz()
+        _check(lib().gs_tristream_counts_device(self._h, _ptr(vertex), _ptr(count), _cap_of(None, vertex, count),
+                                                ctypes.byref(got)))
+        return got.value
+
+    def stats(self):
+        """gs_testing_tristream_stats: the last fold (synchronises)."""
+        return self.phases()[0]
+
+    def phases(self):
+        """(stats, microseconds of the last fold's ranks with sort and dedupe, merge, rows and count,
+        offsets and write, record ranks and sort, scan and counters): the times are zero unless
+        tune(profile=True)."""
+        out = (_u64 * 10)()
+        _check(lib().gs_testing_tristream_stats(self._h, out))
+        return ({"tiles": out[0], "crossed": out[1], "longest_row": out[2], "steps": out[3]},
+                {"sort_dedupe": out[4], "merge": out[5], "count": out[6], "write": out[7], "record_sort": out[8],
+                 "scan": out[9]})
+
+    def tune(self, profile=None, max_records=None):
+        """gs_testing_tristream_tune, per handle: whether a fold times its phases (and then waits
+        for the handle's stream once more), and the records a fold may emit before it fails with
+        GS_ERR_CAPACITY (a value <= 0 restores TRISTREAM_MAX_RECORDS). None leaves a control as it
+        is."""
+        if profile is not None:
+            _check(lib().gs_testing_tristream_tune(self._h, 0, 1 if profile else -1))
+        if max_records is not None:
+            _check(lib().gs_testing_tristream_tune(self._h, 1, int(max_records)))
 
 
 # ---------------------------------------------------------------- native multi-GPU group

@@ -2,8 +2,8 @@
 // gs_capi.cpp (include/gs_summary.h), gs_group.cpp (include/gs_group.h),
 // gs_changes.cpp (per-window change emission), gs_degree.cpp and gs_sort.cpp; and what every
 // handle type is made from -- the summary here, and the stand-alone summaries of gs_slice.cpp,
-// gs_triangle.cpp, gs_distinct.cpp, gs_spanner.cpp, gs_matching.cpp, gs_trisample.cpp and
-// gs_degstream.cpp: the error macros
+// gs_triangle.cpp, gs_distinct.cpp, gs_spanner.cpp, gs_matching.cpp, gs_trisample.cpp,
+// gs_degstream.cpp and gs_tristream.cpp: the error macros
 // (GS_HIP, GS_LAUNCH), the phase timer, the stream owner each handle derives from with the entry
 // points all of them have (sync, get_stream, wait_stream, the null check, the truncation error).
 // Every device array a handle owns is a DevBuf (gs_devbuf.hpp), every event, stream and pinned
@@ -126,7 +126,7 @@ struct DeviceGuard {
 // begins phase i. finish() waits for the stream and sets all `phases` words of phase_us:
 // microseconds for a phase whose two events were recorded, zero for one that did not run.
 struct PhaseTimer {
-  static constexpr int kMaxPhases = 5;
+  static constexpr int kMaxPhases = 6;
   hipStream_t st;
   bool on;
   uint64_t* us;

@@ -7,7 +7,7 @@
 // carry all ordering between workgroups (no workgroup waits on another inside a launch).
 // The host part at the end (gs_sort.cpp) owns the sort's scratch and drives its passes for
 // every caller: the component export, the degree exports, the triangle and spanner folds, the
-// window slices, the distinct and matching exports and the degree streams' folds.
+// window slices, the distinct and matching exports and the degree and triangle streams' folds.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

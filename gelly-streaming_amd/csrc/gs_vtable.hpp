@@ -1,8 +1,9 @@
 // gs_vtable.hpp -- VertexTable: the owner of the distinct streams' vertex table (gs_distinct.hpp:
 // DistVSlot, launch_dist_vertices) and of the vertex list beside it, and the one way it grows.
 // The distinct streams (gs_distinct.cpp), the weighted matching (gs_matching.cpp), which keeps
-// one state record per rank next to the list, and the degree streams (gs_degstream.cpp), which
-// keep one degree per rank there, derive their handles from it. Host only.
+// one state record per rank next to the list, the degree streams (gs_degstream.cpp), which keep
+// one degree per rank there, and the triangle streams (gs_tristream.cpp), which keep one 64-bit
+// triangle counter per rank there, derive their handles from it. Host only.
 #pragma once
 #include "gs_distinct.hpp"
 #include "gs_internal.hpp"

@@ -1205,9 +1205,9 @@ class WindowTriangles {
 };
 
 // ExactTriangleCount (example/ExactTriangleCount.java:52-56): buildNeighborhood,
-// IntersectNeighborhoods, SumAndEmitCounters. run() folds the stream in batches of
-// `batch` edges and returns the final counter map: key -1 the total, every other key a
-// vertex with at least one triangle. Equal to the reference's final counters on a stream
+// IntersectNeighborhoods, SumAndEmitCounters. stream() returns every emitted tuple in order;
+// run() folds the stream in batches of `batch` edges and returns the final counter map: key -1
+// the total, every other key a vertex with at least one triangle. Equal to the reference's final counters on a stream
 // without repeated edges and self-loops (it counts a repeated edge's triangles again).
 class ExactTriangleCount {
  public:
@@ -1236,7 +1236,53 @@ class ExactTriangleCount {
     return out;
   }
 
+  // stream(): the example's continuous output, every Tuple2 SumAndEmitCounters emits
+  // (ExactTriangleCount.java:121-133), through a tristream handle in the reference's mode (a
+  // repeated edge is intersected again): per arrival that closes triangles the running counts of
+  // the common neighbours, ascending, of the two endpoints, and (-1, total). The sequence does
+  // not depend on `batch`. Self-loops emit nothing (the reference's artefacts are not
+  // reproduced).
+  template <typename K, typename EV>
+  std::vector<std::pair<int64_t, long>> stream(const EdgeStream<K, EV>& stream, size_t batch = 0) const {
+    const size_t n = stream.edges.size();
+    TristreamHandle h(device_, n);
+    std::vector<int64_t> src(n), dst(n);
+    for (size_t i = 0; i < n; ++i) {
+      src[i] = (int64_t)stream.edges[i].getSource();
+      dst[i] = (int64_t)stream.edges[i].getTarget();
+    }
+    if (batch == 0) batch = std::max<size_t>(n, 1);
+    batch = std::min<size_t>(batch, (size_t)1 << 22);  // (the largest fold whose rows the handle keeps)
+    std::vector<std::pair<int64_t, long>> out;
+    std::vector<uint32_t> closed, arrival;
+    std::vector<int64_t> total, vertex, count;
+    for (size_t i = 0; i < n; i += batch) {
+      const size_t len = std::min(batch, n - i);
+      gs_check(gs_tristream_fold(h.d, src.data() + i, dst.data() + i, len));
+      uint64_t size[4] = {0, 0, 0, 0};
+      gs_check(gs_tristream_size(h.d, size));
+      closed.resize(size[0] + 1), total.resize(size[0] + 1);
+      arrival.resize(size[1] + 1), vertex.resize(size[1] + 1), count.resize(size[1] + 1);
+      size_t rows = 0, recs = 0;
+      gs_check(gs_tristream_rows(h.d, closed.data(), total.data(), closed.size(), &rows));
+      gs_check(gs_tristream_records(h.d, arrival.data(), vertex.data(), count.data(), arrival.size(), &recs));
+      size_t r = 0;
+      for (size_t a = 0; a < rows; ++a) {
+        for (; r < recs && arrival[r] == a; ++r) out.push_back(std::make_pair(vertex[r], (long)count[r]));
+        if (closed[a]) out.push_back(std::make_pair((int64_t)-1, (long)total[a]));
+      }
+    }
+    return out;
+  }
+
  private:
+  struct TristreamHandle {
+    gs_tristream d = nullptr;
+    TristreamHandle(int device, size_t edges) { gs_check(gs_tristream_create(&d, device, GS_TRISTREAM_COUNT, edges)); }
+    ~TristreamHandle() { gs_tristream_destroy(d); }
+    TristreamHandle(const TristreamHandle&) = delete;
+    TristreamHandle& operator=(const TristreamHandle&) = delete;
+  };
   int device_;
 };
 

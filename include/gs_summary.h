@@ -962,6 +962,83 @@ int gs_degstream_sync(gs_degstream d);
 int gs_degstream_get_stream(gs_degstream d, void** stream);
 int gs_degstream_wait_stream(gs_degstream d, void* stream);
 
+/* ---- triangle streams ----------------------------------------------------------------
+ * Every record example/ExactTriangleCount.java emits, not only the final counters:
+ * buildNeighborhood(false), ProjectCanonicalEdges, IntersectNeighborhoods and
+ * SumAndEmitCounters (ExactTriangleCount.java:52-56, 74-134) at parallelism 1.
+ *
+ * A tristream handle is its own opaque type with its own create call; how it treats a repeated
+ * pair (gs_tristream_repeats) is fixed at create. Every id is legal, INT64_MIN, INT64_MAX and -1
+ * included. State: G, a set of unordered pairs {u, v}, u != v, each with first{u,v}, the number
+ * of the arrival that added it (1-based, every arrival counted, loops included); a 64-bit
+ * counter t(v) per vertex; the 64-bit total T. Arrival number t = (s, d):
+ *   1. s == d: nothing is emitted, G, t() and T stay; its row is (closed 0, total T). The
+ *      reference's self-loop artefacts are NOT reproduced.
+ *   2. u = min(s, d), v = max(s, d) in signed order; {u, v} not in G: it joins with first = t.
+ *   3. C = { w : {u, w} in G with first < t and {v, w} in G with first < t }, c = |C|.
+ *   4. GS_TRISTREAM_COUNT (the reference): a repeated pair is intersected again.
+ *      GS_TRISTREAM_IGNORE: an arrival whose pair was in G before it has c = 0; the final T and
+ *      t(v) then equal the triangle summary's (gs_triangle_*).
+ *   5. c > 0: the records, in this order: (w, t(w) += 1) for every w of C ascending in signed
+ *      order; (u, t(u) += c); (v, t(v) += c); then T += c. The total is not a record: -1 may be a
+ *      vertex (the C++ mirror puts (-1, total) back).
+ *   6. the arrival's row is (closed = c, total = T after).
+ * The rows and records are a function of the stream order alone, however the stream is cut
+ * into folds: the fold runs in parallel and is exact to that order.
+ *
+ * Limits: the arrivals since the last reset stay at or below 2^31 - 1, and one fold emits at most
+ * 2^27 records. A fold past either fails with GS_ERR_CAPACITY and leaves G, the counters, the
+ * rows and the records as they were before the call: fold smaller pieces, the stream is the
+ * same. (A fold of more than 2^22 arrivals is cut into pieces by the library; when a later
+ * piece fails, the pieces before it are folded and gs_tristream_size tells how far.)
+ *
+ * Synchronisation: a fold waits for the handle's stream twice (the new pairs; the record count);
+ * the ordered write, the record sort and the sum behind them are queued. Every allocation is
+ * counted by gs_hbm_bytes and released by gs_tristream_destroy. Null handles and pointers
+ * return GS_ERR_INVALID before any device call.
+ *
+ * gs_tristream_create: repeats_mode is a gs_tristream_repeats; edge_hint sizes the first
+ *   allocation only.
+ * gs_tristream_reset: G empty, every counter 0, no arrival folded; capacity kept.
+ * gs_tristream_fold / _fold_device: n arrivals from HOST arrays (copied before the call
+ *   returns) / DEVICE arrays read on the handle's stream, element i = src[i*stride],
+ *   dst[i*stride]. The largest fold whose rows are kept has 2^22 arrivals; a longer one is cut
+ *   into pieces by the library, with the same state afterwards, and gs_tristream_rows /
+ *   _records return GS_ERR_INVALID until the next fold.
+ * gs_tristream_rows / _rows_device: the last fold's (closed, total) per arrival into HOST /
+ *   DEVICE arrays of capacity cap (either may be NULL); *n = the rows. cap < rows:
+ *   GS_ERR_TRUNCATED, *n set, nothing written.
+ * gs_tristream_records / _records_device: the last fold's (arrival index in the fold, vertex,
+ *   count) per record, in emission order; cap and n as for rows.
+ * gs_tristream_size: out[0..3] = arrivals, records and new pairs of the last fold, the arrivals
+ *   since reset. No device call.
+ * gs_tristream_count: out[0..3] = T, |G|, the vertices of G, the arrivals since reset.
+ *   Synchronises.
+ * gs_tristream_counts / _counts_device: the current (vertex, t) rows with t > 0, ascending by
+ *   vertex in signed order. *n on the host (synchronises); capacity rule as above.
+ * gs_tristream_sync / _get_stream / _wait_stream: as gs_sync / gs_get_stream / gs_wait_stream.
+ * Not built: deletions, combine, serialization, multi-GPU groups, parallelism above 1, and the
+ * neighbourhood sets buildNeighborhood emits (the adjacency with its stamps holds them). */
+typedef enum { GS_TRISTREAM_COUNT = 0, GS_TRISTREAM_IGNORE = 1 } gs_tristream_repeats;
+typedef struct gs_tristream_s* gs_tristream;
+int gs_tristream_create(gs_tristream* out, int device, int repeats_mode, uint64_t edge_hint);
+int gs_tristream_destroy(gs_tristream d); /* NULL is GS_OK */
+int gs_tristream_reset(gs_tristream d);
+int gs_tristream_fold(gs_tristream d, const int64_t* src, const int64_t* dst, size_t n);
+int gs_tristream_fold_device(gs_tristream d, const int64_t* src, const int64_t* dst, size_t n, size_t stride);
+int gs_tristream_rows(gs_tristream d, uint32_t* closed, int64_t* total, size_t cap, size_t* n);
+int gs_tristream_rows_device(gs_tristream d, uint32_t* closed, int64_t* total, size_t cap, size_t* n);
+int gs_tristream_records(gs_tristream d, uint32_t* arrival, int64_t* vertex, int64_t* count, size_t cap, size_t* n);
+int gs_tristream_records_device(gs_tristream d, uint32_t* arrival, int64_t* vertex, int64_t* count, size_t cap,
+                                size_t* n);
+int gs_tristream_size(gs_tristream d, uint64_t* out);
+int gs_tristream_count(gs_tristream d, uint64_t* out);
+int gs_tristream_counts(gs_tristream d, int64_t* vertex, int64_t* count, size_t cap, size_t* n);
+int gs_tristream_counts_device(gs_tristream d, int64_t* vertex, int64_t* count, size_t cap, size_t* n);
+int gs_tristream_sync(gs_tristream d);
+int gs_tristream_get_stream(gs_tristream d, void** stream);
+int gs_tristream_wait_stream(gs_tristream d, void* stream);
+
 /* ---- introspection -----------------------------------------------------------
  * The HIP stream (hipStream_t) the handle enqueues on, and per-kernel timing:
  * when profiling is on, every launch is bracketed by HIP events on the stream it

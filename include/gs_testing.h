@@ -184,6 +184,23 @@ int gs_testing_degstream_stats(void* d, uint64_t* out);
  * GS_ERR_INVALID. */
 int gs_testing_degstream_tune(void* d, int what, int64_t value);
 
+/* The last fold of a tristream handle (`d` is a gs_tristream; synchronises; zero after a reset):
+ * out[0] = tiles of the record scan, out[1] = tiles of it that began inside a segment, so that
+ * the segment's carry crossed a tile boundary, out[2] = the longest row an arrival met, out[3] =
+ * intersection steps (the sum over the arrivals of the walked row's length); out[4..9] =
+ * microseconds of the fold's six phases -- ranks, sort and dedupe; merge; rows and count with
+ * the control read; offsets and write; record ranks and sort; scan and counters -- zero unless
+ * the handle's profile control is on. Ten words. */
+int gs_testing_tristream_stats(void* d, uint64_t* out);
+
+/* Per-handle controls of a tristream handle's folds (`d` is a gs_tristream; not knobs of
+ * gs_testing_set). what = 0 profile: bracket the six phases of a fold with events and wait for
+ * them (product: off; needed by tools/tristream_bench.py). what = 1 record limit: the records a
+ * fold may emit before it fails with GS_ERR_CAPACITY (product and maximum: 2^27), so that a
+ * test reaches the limit with a few hundred arrivals. A value <= 0 restores the product value.
+ * Returns GS_OK or GS_ERR_INVALID. */
+int gs_testing_tristream_tune(void* d, int what, int64_t value);
+
 #ifdef __cplusplus
 }
 #endif

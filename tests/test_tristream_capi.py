@@ -1,0 +1,134 @@
+"""CPU: the triangle streams' entry points exist, are declared in gs_summary.h, exported and bound,
+and reject null arguments before touching a device; the pins file has its shape. No compute calls
+here (the results are checked on the GPU in test_gpu_tristream.py)."""
+import ctypes
+import json
+import os
+import re
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAMES = ("gs_tristream_create", "gs_tristream_destroy", "gs_tristream_reset", "gs_tristream_fold",
+         "gs_tristream_fold_device", "gs_tristream_rows", "gs_tristream_rows_device", "gs_tristream_records",
+         "gs_tristream_records_device", "gs_tristream_size", "gs_tristream_count", "gs_tristream_counts",
+         "gs_tristream_counts_device", "gs_tristream_sync", "gs_tristream_get_stream", "gs_tristream_wait_stream")
+TESTING = ("gs_testing_tristream_stats", "gs_testing_tristream_tune")
+
+
+def test_names_are_declared_exported_and_bound(gs):
+    with open(os.path.join(ROOT, "include", "gs_summary.h")) as f:
+        text = f.read()
+    L = gs.lib()
+    assert re.search(r"typedef struct gs_tristream_s\* gs_tristream;", text)
+    assert re.search(r"typedef enum \{ GS_TRISTREAM_COUNT = 0, GS_TRISTREAM_IGNORE = 1 \} gs_tristream_repeats;", text)
+    for n in NAMES:
+        assert n in gs.EXPORTED_SYMBOLS
+        assert not re.search(r"\d", n)
+        assert hasattr(ctypes.CDLL(gs.LIB_PATH), n)
+        assert re.search(r"\bint %s\(gs_tristream\*? \w+[,)]" % n, text), n
+        assert getattr(L, n).argtypes, n
+    with open(os.path.join(ROOT, "include", "gs_testing.h")) as f:
+        testing = f.read()
+    for n in TESTING:
+        assert n in gs.EXPORTED_SYMBOLS and hasattr(ctypes.CDLL(gs.LIB_PATH), n)
+        assert getattr(L, n).argtypes
+    assert re.search(r"\bint gs_testing_tristream_stats\(void\* d, uint64_t\* out\);", testing)
+    assert re.search(r"\bint gs_testing_tristream_tune\(void\* d, int what, int64_t value\);", testing)
+    # no knob was added to gs_testing_set
+    assert re.search(r"GS_TESTING_KNOBS = 13\b", testing)
+    # the header states the rules, the limits, the self-loop departure and what is not built
+    for phrase in ("first < t", "(w, t(w) += 1) for every w of C ascending in signed", "The total is not a record",
+                   "self-loop artefacts are NOT reproduced", "at most\n * 2^27 records",
+                   "leaves G, the counters, the\n * rows and the records as they were before the call",
+                   "The largest fold whose rows are kept has 2^22", "however the stream is cut",
+                   "Not built: deletions, combine, serialization, multi-GPU groups, parallelism above 1"):
+        assert phrase in text, phrase
+
+
+def test_null_handles_and_pointers_are_rejected(gs):
+    L = gs.lib()
+    n = ctypes.c_size_t(7)
+    w = (ctypes.c_uint64 * 10)()
+    p = ctypes.c_void_p()
+    calls = (
+        lambda: L.gs_tristream_create(None, 0, 0, 16),
+        lambda: L.gs_tristream_reset(None),
+        lambda: L.gs_tristream_fold(None, None, None, 0),
+        lambda: L.gs_tristream_fold_device(None, None, None, 0, 1),
+        lambda: L.gs_tristream_rows(None, None, None, 0, ctypes.byref(n)),
+        lambda: L.gs_tristream_rows_device(None, None, None, 0, ctypes.byref(n)),
+        lambda: L.gs_tristream_records(None, None, None, None, 0, ctypes.byref(n)),
+        lambda: L.gs_tristream_records_device(None, None, None, None, 0, ctypes.byref(n)),
+        lambda: L.gs_tristream_size(None, w),
+        lambda: L.gs_tristream_count(None, w),
+        lambda: L.gs_tristream_counts(None, None, None, 0, ctypes.byref(n)),
+        lambda: L.gs_tristream_counts_device(None, None, None, 0, ctypes.byref(n)),
+        lambda: L.gs_tristream_sync(None),
+        lambda: L.gs_tristream_get_stream(None, ctypes.byref(p)),
+        lambda: L.gs_tristream_wait_stream(None, None),
+        lambda: L.gs_testing_tristream_stats(None, w),
+        lambda: L.gs_testing_tristream_tune(None, 0, 1),
+    )
+    for c in calls:
+        assert c() == gs.GS_ERR_INVALID
+        assert b"null" in L.gs_last_error()
+    assert L.gs_tristream_destroy(None) == gs.GS_OK
+    assert n.value == 7
+    # argument errors that need no device: an unknown mode, a hint past the pair limit
+    h = ctypes.c_void_p()
+    assert L.gs_tristream_create(ctypes.byref(h), 0, 2, 16) == gs.GS_ERR_INVALID and not h.value
+    assert b"repeats" in L.gs_last_error()
+    assert L.gs_tristream_create(ctypes.byref(h), 0, -1, 16) == gs.GS_ERR_INVALID
+    assert L.gs_tristream_create(ctypes.byref(h), 0, 0, 1 << 31) == gs.GS_ERR_CAPACITY and not h.value
+
+
+def test_python_class_has_the_methods(gs):
+    for m in ("close", "reset", "sync", "wait_stream", "fold", "fold_device", "rows", "rows_device", "records",
+              "records_device", "count", "local_counts", "local_counts_device", "size", "stats", "phases", "tune",
+              "__enter__", "__exit__"):
+        assert callable(getattr(gs.TriangleStream, m)), m
+    assert isinstance(gs.TriangleStream.stream, property)
+    assert issubclass(gs.TriangleStream, gs._ResetHandle)
+    assert "__del__" not in vars(gs.TriangleStream) and "close" not in vars(gs.TriangleStream)
+    import inspect
+    sig = inspect.signature(gs.TriangleStream.__init__)
+    assert [(k, v.default) for k, v in sig.parameters.items()][1:] == [("repeats", "count"), ("edge_hint", 0),
+                                                                      ("device", 0)]
+
+
+def test_tristream_constants_match_the_headers(gs):
+    csrc = os.path.join(ROOT, "gelly-streaming_amd", "csrc")
+    with open(os.path.join(csrc, "gs_tristream_seq.hpp")) as f:
+        seq = f.read()
+    with open(os.path.join(csrc, "gs_tristream.hpp")) as f:
+        hpp = f.read()
+    assert gs.TRISTREAM_TILE == int(re.search(r"constexpr uint32_t TRISTREAM_TILE = (\d+);", hpp).group(1))
+    assert gs.TRISTREAM_LANES == int(re.search(r"constexpr uint32_t TRISTREAM_LANES = (\d+);", hpp).group(1))
+    assert "constexpr uint32_t kTsShortRow = 4 * TRISTREAM_LANES;" in hpp and gs.TRISTREAM_SHORT_ROW == 4 * gs.TRISTREAM_LANES
+    assert gs.TRISTREAM_MAX_TOTAL == int(re.search(r"constexpr uint64_t kTsMaxTotal = (0x[0-9A-F]+)ull;", seq).group(1), 16)
+    assert gs.TRISTREAM_MAX_FOLD == 1 << int(re.search(r"constexpr uint64_t kTsMaxFold = 1ull << (\d+);", seq).group(1))
+    assert gs.TRISTREAM_MAX_RECORDS == 1 << int(re.search(r"constexpr uint64_t kTsMaxRecords = 1ull << (\d+);", seq).group(1))
+    assert gs.TRISTREAM_MAX_RECORDS <= (1 << 31) - 1
+    assert re.search(r"enum TsRepeats : int \{ kTsCount = 0, kTsIgnore = 1, kTsModes = 2 \};", seq)
+    assert gs.TRISTREAM_REPEATS == {"count": 0, "ignore": 1}
+    with open(os.path.join(ROOT, "include", "gs_testing.h")) as f:
+        assert "(product and maximum: 2^27)" in f.read()
+    with open(os.path.join(ROOT, "gelly-streaming_amd", "Makefile")) as f:
+        mk = f.read()
+    for name in ("csrc/gs_tristream.hpp", "csrc/gs_tristream_seq.hpp", "gs_tristream_k.o", "gs_tristream.o"):
+        assert name in mk, name
+    with open(os.path.join(ROOT, "gelly-streaming_amd", "host", "Makefile")) as f:
+        mk = f.read()
+    for name in ("bin/test_tristream", "bin/exact_triangle_count"):
+        assert name in mk, name
+
+
+def test_the_pins_file_has_its_shape():
+    with open(os.path.join(ROOT, "tests", "golden", "tristream_pins.json")) as f:
+        pins = json.load(f)
+    assert set(pins) == {"_comment", "test_intersection", "test_counts", "builtin_stream", "derived"}
+    cases = pins["test_intersection"]["cases"]
+    assert len(cases) == 2 and all(len(c["expected_tuples"]) == 5 for c in cases)
+    assert all(re.search(r"TriangleCountTest\.java:\d+", c["cite"]) for c in cases)
+    assert len(pins["test_counts"]["inputs"]) == len(pins["test_counts"]["running_sums"]) == 5
+    assert len(pins["builtin_stream"]["edges"]) == 9
+    assert pins["derived"]["tuples"][-1] == [-1, 4]
