@@ -52,7 +52,7 @@ EXPORTED_SYMBOLS = (
     "gs_combine", "gs_sync", "gs_num_vertices", "gs_find", "gs_export_labels", "gs_export_labels_device",
     "gs_bip_status", "gs_export_colouring", "gs_serialize", "gs_deserialize", "gs_set_delta_tracking",
     "gs_take_delta_records", "gs_fold_take_device", "gs_delta_stage", "gs_fold_records_device", "gs_fold_exchange_device",
-    "gs_get_stream", "gs_set_pipelining", "gs_set_hot_index", "gs_hot_index_stats", "gs_set_profiling", "gs_kernel_stats", "gs_table_capacity", "gs_counters", "gs_debug_counters",
+    "gs_get_stream", "gs_set_pipelining", "gs_set_hot_index", "gs_hot_index_stats", "gs_testing_hot_tune", "gs_testing_hot_keys", "gs_set_profiling", "gs_kernel_stats", "gs_table_capacity", "gs_counters", "gs_debug_counters",
     "gs_gen_rmat", "gs_gen_er", "gs_gen_bip",
     "gs_parse_edges_device", "gs_fold_text", "gs_parse_set_profiling", "gs_parse_profile", "gs_parse_release",
     "gs_group_unique_id", "gs_group_create", "gs_group_fold_device", "gs_group_finish", "gs_group_stats",
@@ -294,6 +294,10 @@ def lib():
     L.gs_set_pipelining.argtypes = [_vp, ctypes.c_int]
     L.gs_set_hot_index.argtypes = [_vp, ctypes.c_int, _u64, ctypes.c_uint32]
     L.gs_hot_index_stats.argtypes = [_vp, ctypes.POINTER(_u64)]
+    if hasattr(L, "gs_testing_hot_tune"):  # (an A/B's GS_LIB_VARIANT library of the parent commit has neither)
+        L.gs_testing_hot_tune.argtypes = [_vp, ctypes.c_int, ctypes.c_int64]
+        L.gs_testing_hot_keys.argtypes = [_vp, ctypes.POINTER(_i64), _u64]
+        L.gs_testing_hot_keys.restype = _i64
     L.gs_kernel_stats.argtypes = [_vp, ctypes.c_int, ctypes.POINTER(_u64), ctypes.POINTER(ctypes.c_double)]
     L.gs_table_capacity.argtypes = [_vp, ctypes.POINTER(_u64)]
     L.gs_counters.argtypes = [_vp, ctypes.POINTER(_u64)]
@@ -537,6 +541,29 @@ def testing_set(knob, value):
 
 def testing_get(knob):
     return lib().gs_testing_get(TESTING_KNOBS[knob])
+
+
+def testing_hot_tune(summary, rows=None, sketch_log2=None, sample_folds=None):
+    """gs_testing_hot_tune, per handle of a "cc" Summary: the rows of the hot index build's
+    sketch (1 or 2), its counters per row and id (log2), the folds counted for one build (1, 2
+    or 4). A value < 0 restores the library's. Drops a live index."""
+    for what, v in enumerate((rows, sketch_log2, sample_folds)):
+        if v is not None:
+            _check(lib().gs_testing_hot_tune(summary._h, what, int(v)))
+
+
+def testing_hot_keys(summary):
+    """gs_testing_hot_keys: the keys the live hot index of a "cc" Summary holds (an int64 array,
+    in bucket order)."""
+    import numpy as np
+    n = lib().gs_testing_hot_keys(summary._h, None, 0)
+    if n < 0:
+        _check(int(n))
+    out = (_i64 * max(int(n), 1))()
+    m = lib().gs_testing_hot_keys(summary._h, out, int(n))
+    if m < 0:
+        _check(int(m))
+    return np.frombuffer(out, dtype=np.int64, count=int(min(n, m))).copy()
 
 
 class testing:

@@ -165,8 +165,8 @@ void reset_capacity_tracking(gs_summary* h, uint64_t nv) {
 // Defaults from the grid on the flagship step (profiles/hot_buckets_grid.txt): 2^17 ids in 2^16
 // buckets (1 MiB, inside every XCD's L2; 2 MiB is slower), a refresh every 16 folds, the whole
 // 2^20-edge batch as a build's sample. A table below 256 MiB probes fast enough without an index.
-// The three are compile-time switches so that tools/hot_grid.py can run the grid again (one
-// library per setting) when the fold or the build changes.
+// These, and the build's counts below, are compile-time switches so that tools/hot_grid.py can
+// run the grid again (one library per setting) when the fold or the build changes.
 #ifndef GS_HOT_LOG2
 #define GS_HOT_LOG2 17
 #endif
@@ -176,6 +176,22 @@ void reset_capacity_tracking(gs_summary* h, uint64_t nv) {
 #ifndef GS_HOT_SAMPLE_LOG2
 #define GS_HOT_SAMPLE_LOG2 20
 #endif
+// The build's counts (profiles/hot_ways_grid.txt): the sketch's rows (1 or 2) and counters per
+// row and id (log2), and the folds whose endpoints are counted for one build (1, 2 or 4: the
+// build's own fold and the ones before it). One row of 64 counters per id and two folds: a
+// second row of the same total size measures the same, four folds measure slower.
+#ifndef GS_HOT_SKETCH_ROWS
+#define GS_HOT_SKETCH_ROWS 1
+#endif
+#ifndef GS_HOT_SKETCH_LOG2
+#define GS_HOT_SKETCH_LOG2 6
+#endif
+#ifndef GS_HOT_SAMPLE_FOLDS
+#define GS_HOT_SAMPLE_FOLDS 2
+#endif
+static_assert(GS_HOT_SKETCH_ROWS == 1 || GS_HOT_SKETCH_ROWS == 2, "GS_HOT_SKETCH_ROWS");
+static_assert(GS_HOT_SKETCH_LOG2 >= 0 && GS_HOT_SKETCH_LOG2 <= 6, "GS_HOT_SKETCH_LOG2");
+static_assert(GS_HOT_SAMPLE_FOLDS == 1 || GS_HOT_SAMPLE_FOLDS == 2 || GS_HOT_SAMPLE_FOLDS == 4, "GS_HOT_SAMPLE_FOLDS");
 constexpr int kHotLog2 = GS_HOT_LOG2;
 constexpr int kHotMaxLog2 = 20;
 constexpr uint64_t kHotFirstEdges = 1ull << 26;
@@ -184,6 +200,16 @@ constexpr uint32_t kHotRefreshEvery = GS_HOT_REFRESH_EVERY;  // the default rule
 constexpr uint32_t kHotRefreshPerBuild = 16;  // a forced index: refreshes every / 16 folds apart
 constexpr uint64_t kHotMinTableBytes = 256ull << 20;
 constexpr size_t kHotSampleEdges = 1u << GS_HOT_SAMPLE_LOG2;  // of the sampled micro-batch
+
+gs::HotTune hot_tune(const gs_summary* h) {
+  return gs::HotTune{h->hot_rows ? h->hot_rows : GS_HOT_SKETCH_ROWS,
+                     h->hot_sketch_log2 >= 0 ? h->hot_sketch_log2 : GS_HOT_SKETCH_LOG2};
+}
+// Folds counted for one build: what gs_testing_hot_tune set, else GS_HOT_SAMPLE_FOLDS by the
+// default rule and 1 for a forced index (whose caller names the fold a build follows).
+uint32_t hot_sample_folds(const gs_summary* h) {
+  return h->hot_sample_folds ? h->hot_sample_folds : (h->hot_cfg ? 1u : (uint32_t)GS_HOT_SAMPLE_FOLDS);
+}
 
 // log2 ids of the index this summary's plain folds use as it is set up now (0: none)
 int hot_log2(const gs_summary* h) {
@@ -205,6 +231,7 @@ void hot_drop(gs_summary* h) {
   h->hot_edges = 0;
   h->hot_folds = 0;
   h->hot_folds_r = 0;
+  h->hot_counted = 0;  // a partly counted sketch is discarded
 }
 
 // Before a fold that may use the index: a finished build is adopted. The folds queued so far
@@ -225,7 +252,12 @@ int hot_before_fold(gs_summary* h) {
 }
 
 // After a fold of c edges queued on st (hl = hot_log2(h) > 0): when a build is due it is queued
-// behind that fold, on its stream, from its edges, into the buffer no fold reads. No fold waits
+// behind that fold, on its stream, from its edges, into the buffer no fold reads. With k =
+// hot_sample_folds > 1 the first k - 1 folds from which a build is due only add their endpoint
+// counts to the sketch, each behind its own fold on its own stream (the first of them zeroes the
+// scratch before, and the others wait for that), and the k-th fold's stream waits for their
+// events and builds: counts of k folds, candidates from the last (a caller's older buffers may
+// be gone by then). No fold waits
 // for it: the folds go on with the live buffer (or none) until hot_before_fold sees it done.
 // Between two builds a refresh finds the root above the live index's ancestor again -- every
 // kHotRefreshEvery folds by the default rule, every 1/16 of the builds' distance for a forced
@@ -249,17 +281,35 @@ int hot_after_fold(gs_summary* h, const int64_t* src, const int64_t* dst, size_t
     GS_LAUNCH(gs::launch_hot_refresh(h->table(), h->hot_buf[h->hot_live], hl, st));
     return GS_OK;
   }
+  const gs::HotTune tune = hot_tune(h);
   if (h->hot_alloc_log2 != hl) {  // first use (gs_set_hot_index freed the buffers of another size)
     h->hot_alloc_log2 = 0;
     for (auto& b : h->hot_buf) GS_HIP(b.alloc(gs::hot_buckets(hl) + 1));  // the buckets and their header
-    GS_HIP(h->hot_scratch.alloc(gs::hot_scratch_words(hl)));
+    GS_HIP(h->hot_scratch.alloc(gs::hot_scratch_words(hl, tune)));
     if (!h->hot_built) {
       GS_HIP(h->hot_built.create());
+      GS_HIP(h->hot_zeroed.create());
+      for (Event& e : h->hot_count_ev) GS_HIP(e.create());
       for (auto& r : h->hot_read)
         for (Event& e : r) GS_HIP(e.create());
     }
     h->hot_alloc_log2 = hl;
   }
+  const uint32_t n = (uint32_t)std::min(c, kHotSampleEdges);
+  if (h->hot_counted == 0) {  // (the last build is done: hot_building < 0 above)
+    GS_LAUNCH(gs::launch_hot_zero(hl, tune, h->hot_scratch, st));
+    GS_HIP(hipEventRecord(h->hot_zeroed, st));
+  } else {
+    GS_HIP(hipStreamWaitEvent(st, h->hot_zeroed, 0));
+  }
+  if (h->hot_counted + 1 < hot_sample_folds(h)) {  // one of the k - 1 folds that are only counted
+    GS_LAUNCH(gs::launch_hot_count(src, dst, n, (uint32_t)stride, hl, tune, h->hot_scratch, st));
+    GS_HIP(hipEventRecord(h->hot_count_ev[h->hot_counted], st));
+    h->hot_counted++;
+    return GS_OK;
+  }
+  for (uint32_t i = 0; i < h->hot_counted; ++i) GS_HIP(hipStreamWaitEvent(st, h->hot_count_ev[i], 0));
+  h->hot_counted = 0;
   const int b = h->hot_live < 0 ? 0 : h->hot_live ^ 1;
   if (h->hot_read_on[b]) {
     for (int i = 0; i <= gs_summary::kLanes; ++i)
@@ -268,8 +318,7 @@ int hot_after_fold(gs_summary* h, const int64_t* src, const int64_t* dst, size_t
   }
   h->hot_folds = 0;  // (counted whether or not the launch is accepted)
   h->hot_builds++;
-  GS_LAUNCH(gs::launch_hot_build(h->table(), src, dst, (uint32_t)std::min(c, kHotSampleEdges), (uint32_t)stride,
-                                 h->hot_buf[b], hl, h->hot_scratch, st));
+  GS_LAUNCH(gs::launch_hot_build(h->table(), src, dst, n, (uint32_t)stride, h->hot_buf[b], hl, tune, h->hot_scratch, st));
   GS_HIP(hipEventRecord(h->hot_built, st));
   h->hot_building = b;
   h->hot_folds_r = 0;
@@ -2065,6 +2114,50 @@ int gs_hot_index_stats(gs_handle h, uint64_t* out4) {
     for (const gs::HotBucket& x : e) out4[1] += (x.key[0] != gs::kEmpty) + (x.key[1] != gs::kEmpty);
   }
   return GS_OK;
+}
+
+int gs_testing_hot_tune(void* hv, int what, int64_t value) {
+  gs_handle h = static_cast<gs_handle>(hv);
+  if (int rc = check_any(h)) return rc;
+  if (h->kind != GS_KIND_CC) return fail(GS_ERR_INVALID, "the hot index serves connected-components summaries only");
+  if (what < 0 || what > 2) return fail(GS_ERR_INVALID, "hot tune: what is 0, 1 or 2");
+  if (value >= 0) {
+    if (what == 0 && value != 1 && value != 2) return fail(GS_ERR_INVALID, "hot tune: 1 or 2 sketch rows");
+    if (what == 1 && value > 6) return fail(GS_ERR_INVALID, "hot tune: at most 2^6 counters per id");
+    if (what == 2 && value != 1 && value != 2 && value != 4) return fail(GS_ERR_INVALID, "hot tune: 1, 2 or 4 sample folds");
+  }
+  DeviceGuard g(h->device);
+  if (int rc = join_lanes(h)) return rc;
+  GS_HIP(hipStreamSynchronize(h->stream));  // nothing reads, counts into or builds a buffer any more
+  hot_drop(h);
+  h->hot_alloc_log2 = 0;  // (the scratch's size follows the sketch's)
+  for (auto& b : h->hot_buf) b.reset();
+  h->hot_scratch.reset();
+  if (what == 0) h->hot_rows = value < 0 ? 0 : (int)value;
+  if (what == 1) h->hot_sketch_log2 = value < 0 ? -1 : (int)value;
+  if (what == 2) h->hot_sample_folds = value < 0 ? 0u : (uint32_t)value;
+  return GS_OK;
+}
+
+int64_t gs_testing_hot_keys(void* hv, int64_t* out, uint64_t cap) {
+  gs_handle h = static_cast<gs_handle>(hv);
+  if (int rc = check_any(h)) return rc;
+  if (!out && cap) return fail(GS_ERR_INVALID, "out is null");
+  DeviceGuard g(h->device);
+  if (int rc = join_lanes(h)) return rc;
+  GS_HIP(hipStreamSynchronize(h->stream));  // a queued build is done
+  if (int rc = hot_before_fold(h)) return rc;
+  if (h->hot_live < 0) return 0;
+  std::vector<gs::HotBucket> e(gs::hot_buckets(h->hot_alloc_log2));
+  GS_HIP(hipMemcpy(e.data(), h->hot_buf[h->hot_live], e.size() * sizeof(gs::HotBucket), hipMemcpyDeviceToHost));
+  uint64_t n = 0;
+  for (const gs::HotBucket& x : e)
+    for (int64_t k : x.key)
+      if (k != gs::kEmpty) {
+        if (n < cap) out[n] = k;
+        ++n;
+      }
+  return (int64_t)n;
 }
 
 int gs_table_capacity(gs_handle h, uint64_t* slots) {

@@ -3,9 +3,12 @@
 // gs_capi.cpp).
 //
 // A build reads the first n edges of one micro-batch, on the stream that has just folded it:
-//   count  : endpoint occurrences into a one-row sketch (16 counters per id the index can hold,
-//            addressed by a hash of the id: no keys, no probing; a collision only overstates a
-//            count);
+//   count  : endpoint occurrences into a sketch of one or two rows (per row 2^sketch_log2
+//            counters per id the index can hold, addressed by a row's own hash of the id: no
+//            keys, no probing; a collision only overstates a count, and an id's count is the
+//            smaller of its rows' counters). The count passes of up to three earlier folds may
+//            have added their occurrences to the same sketch (launch_hot_count behind each of
+//            those folds; candidates still come from the build's own fold only);
 //   select : per bucket the two highest ranks {count, tag} among its ids, in one pass: a 64-bit
 //            max takes the winner, and whatever loses to it or is displaced by it goes into a
 //            second max, which so ends as the highest rank below the winner's;
@@ -30,7 +33,6 @@ namespace gs {
 
 namespace {
 
-constexpr int kHotSketchLog2 = 4;  // sketch counters per id (log2)
 constexpr uint32_t kHotBS = 256;
 constexpr uint32_t kVoteCells = 1024;  // hashed vote counters
 // Every 8th block of k_hot_root votes: places are hash positions, so any blocks are a uniform
@@ -40,8 +42,19 @@ constexpr uint32_t kVoteCells = 1024;  // hashed vote counters
 constexpr uint32_t kVoteEvery = 8;
 constexpr int kVoteRounds = 8;         // distinct roots a wave votes for at most
 
-__device__ __forceinline__ uint32_t sketch_pos(int64_t key, int log2_ids) {
-  return (uint32_t)(((uint64_t)key * 0xC2B2AE3D27D4EB4Full) >> (64 - kHotSketchLog2 - log2_ids));
+// The sketch: `rows` rows of 2^bits counters (bits = sketch_log2 + log2 ids <= 31).
+struct HotSketch {
+  uint32_t* c;
+  int rows, bits;
+};
+__device__ __forceinline__ uint32_t sketch_pos(int64_t key, int row, int bits) {
+  const uint64_t mul = row ? 0xA24BAED4963EE407ull : 0xC2B2AE3D27D4EB4Full;  // two odd constants: independent rows
+  return ((uint32_t)row << bits) + (uint32_t)(((uint64_t)key * mul) >> (64 - bits));
+}
+__device__ __forceinline__ uint32_t sketch_count(const HotSketch& k, int64_t key) {
+  uint32_t c = k.c[sketch_pos(key, 0, k.bits)];
+  if (k.rows > 1) c = min(c, k.c[sketch_pos(key, 1, k.bits)]);
+  return c;
 }
 __device__ __forceinline__ unsigned long long hot_rank(uint32_t count, int64_t key) {
   return ((unsigned long long)count << 32) | (uint32_t)(((uint64_t)key * 0x9E3779B97F4A7C15ull) >> 32);
@@ -79,15 +92,16 @@ struct HotScratch {
   unsigned long long* vote;   // {votes << 32 | root} of the root with the most votes so far
   uint32_t* cells;            // [kVoteCells] votes by hashed root
   uint32_t* slot1;            // [ids] place 2 * bucket + {0, 1}: the claimed slot + 1 (0: none)
-  uint32_t* sketch;           // [ids << kHotSketchLog2]
+  HotSketch sketch;           // [rows << (sketch_log2 + log2 ids)]
   int64_t* keys;              // [ids] the place's key (where slot1 != 0)
   uint32_t* root;             // [ids] the place's root (where slot1 != 0)
 };
-__host__ __device__ inline uint64_t scratch_zeroed_words(int log2_ids) {
+inline uint64_t scratch_zeroed_words(int log2_ids, const HotTune& tune) {
   const uint64_t ids = 1ull << log2_ids;
-  return ids /* best1, best2 */ + 1 + kVoteCells / 2 + (ids + 1) / 2 + ((ids << kHotSketchLog2) >> 1);
+  return ids /* best1, best2 */ + 1 + kVoteCells / 2 + (ids + 1) / 2 +
+         (((uint64_t)tune.rows << (tune.sketch_log2 + log2_ids)) + 1) / 2;
 }
-inline HotScratch scratch_of(unsigned long long* w, int log2_ids) {
+inline HotScratch scratch_of(unsigned long long* w, int log2_ids, const HotTune& tune) {
   const uint64_t ids = 1ull << log2_ids, buckets = ids >> 1;
   HotScratch s;
   s.best1 = w;
@@ -95,8 +109,8 @@ inline HotScratch scratch_of(unsigned long long* w, int log2_ids) {
   s.vote = s.best2 + buckets;
   s.cells = reinterpret_cast<uint32_t*>(s.vote + 1);
   s.slot1 = s.cells + kVoteCells;
-  s.sketch = s.slot1 + ids;
-  s.keys = reinterpret_cast<int64_t*>(w + scratch_zeroed_words(log2_ids));
+  s.sketch = HotSketch{s.slot1 + ids, tune.rows, tune.sketch_log2 + log2_ids};
+  s.keys = reinterpret_cast<int64_t*>(w + scratch_zeroed_words(log2_ids, tune));
   s.root = reinterpret_cast<uint32_t*>(s.keys + ids);
   return s;
 }
@@ -110,7 +124,7 @@ __device__ __forceinline__ bool sample_key(const HotSample& s, int j, int64_t& k
   return key != kEmpty;
 }
 
-__global__ __launch_bounds__(kHotBS) void k_hot_count(HotSample s, uint32_t* sketch, int log2_ids) {
+__global__ __launch_bounds__(kHotBS) void k_hot_count(HotSample s, HotSketch sketch) {
   __shared__ uint32_t elect[kHotBS / 64][128], dups[kHotBS / 64][64];
   const uint32_t wv = threadIdx.x >> 6;
 #pragma unroll
@@ -118,7 +132,8 @@ __global__ __launch_bounds__(kHotBS) void k_hot_count(HotSample s, uint32_t* ske
     int64_t key;
     uint32_t cnt;
     const bool has = sample_key(s, j, key);
-    if (wave_combine(key, has, elect[wv], dups[wv], cnt)) atomicAdd(&sketch[sketch_pos(key, log2_ids)], cnt);
+    if (!wave_combine(key, has, elect[wv], dups[wv], cnt)) continue;
+    for (int row = 0; row < sketch.rows; ++row) atomicAdd(&sketch.c[sketch_pos(key, row, sketch.bits)], cnt);
   }
 }
 
@@ -131,7 +146,7 @@ __global__ __launch_bounds__(kHotBS) void k_hot_select(HotSample s, HotScratch x
     uint32_t cnt;
     const bool has = sample_key(s, j, key);
     if (!wave_combine(key, has, elect[wv], dups[wv], cnt)) continue;
-    const unsigned long long r = hot_rank(x.sketch[sketch_pos(key, log2_ids)], key);
+    const unsigned long long r = hot_rank(sketch_count(x.sketch, key), key);
     const uint32_t p = hot_pos(key, 65 - log2_ids);
     // (the plain reads may be stale, that is lower: a stale read only costs an atomic)
     const unsigned long long seen = x.best1[p];
@@ -155,7 +170,7 @@ __global__ __launch_bounds__(kHotBS) void k_hot_claim(Table t, HotSample s, HotS
     uint32_t cnt;
     const bool has = sample_key(s, j, key);
     if (!wave_combine(key, has, elect[wv], dups[wv], cnt)) continue;
-    const unsigned long long r = hot_rank(x.sketch[sketch_pos(key, log2_ids)], key);  // >= 2^32: the id was counted
+    const unsigned long long r = hot_rank(sketch_count(x.sketch, key), key);  // >= 2^32: the id was counted
     const uint32_t p = hot_pos(key, 65 - log2_ids);
     const bool second = x.best1[p] != r;
     unsigned long long* b = (second ? x.best2 : x.best1) + p;
@@ -232,19 +247,30 @@ __global__ __launch_bounds__(64) void k_hot_refresh(Table t, HotHeader* h) {
 
 }  // namespace
 
-uint64_t hot_scratch_words(int log2_ids) {
+uint64_t hot_scratch_words(int log2_ids, const HotTune& tune) {
   const uint64_t ids = 1ull << log2_ids;
-  return scratch_zeroed_words(log2_ids) + ids + (ids + 1) / 2;  // + keys, root
+  return scratch_zeroed_words(log2_ids, tune) + ids + (ids + 1) / 2;  // + keys, root
+}
+
+void launch_hot_zero(int log2_ids, const HotTune& tune, unsigned long long* scratch, hipStream_t st) {
+  (void)hipMemsetAsync(scratch, 0, scratch_zeroed_words(log2_ids, tune) * 8, st);
+}
+
+void launch_hot_count(const int64_t* src, const int64_t* dst, uint32_t n, uint32_t stride, int log2_ids,
+                      const HotTune& tune, unsigned long long* scratch, hipStream_t st) {
+  if (!n) return;
+  const HotScratch x = scratch_of(scratch, log2_ids, tune);
+  const HotSample s{src, dst, n, stride};
+  hipLaunchKernelGGL(k_hot_count, dim3((n + kHotBS - 1) / kHotBS), dim3(kHotBS), 0, st, s, x.sketch);
 }
 
 void launch_hot_build(const Table& t, const int64_t* src, const int64_t* dst, uint32_t n, uint32_t stride,
-                      HotBucket* out, int log2_ids, unsigned long long* scratch, hipStream_t st) {
+                      HotBucket* out, int log2_ids, const HotTune& tune, unsigned long long* scratch, hipStream_t st) {
   const uint32_t ids = 1u << log2_ids, buckets = (uint32_t)hot_buckets(log2_ids);
-  const HotScratch x = scratch_of(scratch, log2_ids);
-  (void)hipMemsetAsync(scratch, 0, scratch_zeroed_words(log2_ids) * 8, st);
+  const HotScratch x = scratch_of(scratch, log2_ids, tune);
   const HotSample s{src, dst, n, stride};
   const dim3 g((n + kHotBS - 1) / kHotBS), b(kHotBS);
-  hipLaunchKernelGGL(k_hot_count, g, b, 0, st, s, x.sketch, log2_ids);
+  hipLaunchKernelGGL(k_hot_count, g, b, 0, st, s, x.sketch);
   hipLaunchKernelGGL(k_hot_select, g, b, 0, st, s, x, log2_ids);
   hipLaunchKernelGGL(k_hot_claim, g, b, 0, st, t, s, x, log2_ids);
   hipLaunchKernelGGL(k_hot_root, dim3((ids + kHotBS - 1) / kHotBS), b, 0, st, t, x, ids);

@@ -393,6 +393,13 @@ struct gs_summary : gsi::StreamOwner {
   uint32_t hot_folds_r = 0;    //   ... since the last build or refresh was
   uint64_t hot_builds = 0;     // builds queued since create
   uint64_t hot_refreshes = 0;  // refreshes queued since create
+  // the build's counts: the sketch (0 / < 0: the library's defaults) and the folds counted for
+  // one build (0: the default; gs_testing_hot_tune), and the folds counted so far for the next
+  int hot_rows = 0, hot_sketch_log2 = -1;
+  uint32_t hot_sample_folds = 0;
+  uint32_t hot_counted = 0;
+  gsi::Event hot_zeroed;       // the scratch is zeroed: ahead of every count pass
+  gsi::Event hot_count_ev[3];  // behind the count passes of the folds before the build's
   // side stream (a multi-GPU group's apply stream): folds of remote rows run there,
   // overlapping this rank's own folds; every reader joins it (join_lanes), the
   // handle's own folds do not (union commutes). Views: the group owns both and takes them

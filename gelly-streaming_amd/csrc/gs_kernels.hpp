@@ -107,11 +107,21 @@ void launch_find_batch(const Table& t, const int64_t* v, uint64_t n, int64_t* la
 
 // hot index build (gs_hot_k.hip): an index of at most 2^log2 ids (2^(log2 - 1) buckets and the
 // header behind them: hot_buckets(log2) + 1 elements of `out`) from the first n edges of a
-// micro-batch; scratch holds hot_scratch_words(log2) words
+// micro-batch; scratch holds hot_scratch_words(log2, tune) words. The sketch is zeroed
+// (launch_hot_zero), earlier folds may add their endpoint counts to it (launch_hot_count, each
+// ordered behind the zeroing), and launch_hot_build, ordered behind all of them, counts its own
+// batch, takes its candidates from it and writes `out`.
+struct HotTune {
+  int rows;         // sketch rows, 1 or 2: an id's count is the smallest of its rows' counters
+  int sketch_log2;  // counters per row and per id the index can hold (log2)
+};
 inline uint64_t hot_buckets(int log2_ids) { return 1ull << (log2_ids - 1); }
-uint64_t hot_scratch_words(int log2_ids);
+uint64_t hot_scratch_words(int log2_ids, const HotTune& tune);
+void launch_hot_zero(int log2_ids, const HotTune& tune, unsigned long long* scratch, hipStream_t st);
+void launch_hot_count(const int64_t* src, const int64_t* dst, uint32_t n, uint32_t stride, int log2_ids,
+                      const HotTune& tune, unsigned long long* scratch, hipStream_t st);
 void launch_hot_build(const Table& t, const int64_t* src, const int64_t* dst, uint32_t n, uint32_t stride,
-                      HotBucket* out, int log2_ids, unsigned long long* scratch, hipStream_t st);
+                      HotBucket* out, int log2_ids, const HotTune& tune, unsigned long long* scratch, hipStream_t st);
 // the header's G2 found again from its G (one wave)
 void launch_hot_refresh(const Table& t, HotBucket* live, int log2_ids, hipStream_t st);
 

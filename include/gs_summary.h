@@ -157,9 +157,11 @@ int gs_set_pipelining(gs_handle h, int depth);
  * deserialized.
  * By default it is on for GS_KIND_CC summaries whose table has at least 256 MiB, in plain
  * host and device folds (no delta or change tracking, no window takes, no window server, no
- * exchange group): 2^17 ids (2^16 buckets, 1 MiB), first built after 2^26 edges since the
+ * exchange group): 2^17 ids (2^16 buckets, 1 MiB), first due after 2^26 edges since the
  * reset, then every 2048 folds, with a refresh every 16 folds (one wave: the root above the
- * index's ancestor found again, one word stored into the live header). (The library reads
+ * index's ancestor found again, one word stored into the live header). By the default rule a
+ * build ranks ids by their occurrences in two folds, the one at which it is due and the next,
+ * which it follows and takes its candidates from; a forced index counts one fold. (The library reads
  * no environment variable: the Python binding turns the default off for summaries created
  * while GS_HOT_INDEX=0 is set, for A/B runs.)
  *   log2_entries < 0  : off;

@@ -201,6 +201,20 @@ int gs_testing_tristream_stats(void* d, uint64_t* out);
  * Returns GS_OK or GS_ERR_INVALID. */
 int gs_testing_tristream_tune(void* d, int what, int64_t value);
 
+/* Per-handle controls of the hot index's build (`h` is a gs_handle of a connected-components
+ * summary; not knobs of gs_testing_set): what = 0 the sketch's rows (1 or 2), what = 1 the
+ * sketch's counters per row and per id the index can hold, as a log2 (0..6), what = 2 the folds
+ * counted for one build (1, 2 or 4: the build comes behind the last of them and takes its
+ * candidates from it; a forced index counts 1 unless this says otherwise). A value < 0 restores
+ * the library's value. The call waits for the handle's work and drops a live index and a partly
+ * counted sketch. Returns GS_OK or GS_ERR_INVALID. */
+int gs_testing_hot_tune(void* h, int what, int64_t value);
+
+/* The keys the live hot index of `h` holds, in bucket order: up to `cap` of them into `out`.
+ * Waits for the handle's work (a queued build is done and adopted). Returns their number
+ * (which may exceed cap; 0 without a live index) or a negative GS_ERR_* code. */
+int64_t gs_testing_hot_keys(void* h, int64_t* out, uint64_t cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,7 +12,8 @@
 // Last, A against M1 with entries {key, slot, anc} and against K2, buckets of two keys under one
 // shared ancestor (2^16 and 2^17 buckets), under the pipelined fold's conditions: three probe
 // kernels in flight on three streams (profiles/hot_index_calib.txt). A second argument skips
-// everything before that last part.
+// everything before that last part. K5 (profiles/hot_ways_calib.txt): 32-B buckets of five 51-bit
+// places (calib_hot_pack.hpp), two 16-B loads per endpoint, 2^15 buckets: the same 1 MiB as K2's 2^16.
 // Build: hipcc -O3 --offload-arch=gfx950 -Iinclude tools/calib_hot.hip
 //          -Lgelly-streaming_amd/lib -lgs_summary -Wl,-rpath,$PWD/gelly-streaming_amd/lib -o tools/bin/calib_hot
 #include <hip/hip_runtime.h>
@@ -23,6 +24,7 @@
 #include <algorithm>
 #include <vector>
 #include "gs_gen.h"
+#include "calib_hot_pack.hpp"
 
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e)); return 1; } } while (0)
 constexpr int64_t kEmpty = INT64_MIN;
@@ -334,6 +336,36 @@ __global__ __launch_bounds__(256) void k_probe_k2(const uint4* tab, uint32_t mas
   if (((pu >> 1) ^ (pv >> 1)) == 0x12345671u) sink[0] = pu;
 }
 
+// K5: the bucket's two 16-B loads go out together with the other endpoint's; the rest as K2.
+__device__ __forceinline__ gs::HotBucket ld_bucket(const gs::HotBucket* p) {
+  const uint4 lo = reinterpret_cast<const uint4*>(p)[0], hi = reinterpret_cast<const uint4*>(p)[1];
+  gs::HotBucket b;
+  b.w[0] = ((uint64_t)lo.y << 32) | lo.x;
+  b.w[1] = ((uint64_t)lo.w << 32) | lo.z;
+  b.w[2] = ((uint64_t)hi.y << 32) | hi.x;
+  b.w[3] = ((uint64_t)hi.w << 32) | hi.z;
+  return b;
+}
+__global__ __launch_bounds__(256) void k_probe_k5(const uint4* tab, uint32_t mask, int sh, const gs::HotBucket* hot, int q,
+                                                  uint32_t g, const int64_t* src, const int64_t* dst, uint32_t n,
+                                                  uint32_t* sink) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int64_t ku = __builtin_nontemporal_load(src + i), kv = __builtin_nontemporal_load(dst + i);
+  const uint64_t pu0 = gs::hot_product(ku), pv0 = gs::hot_product(kv);
+  const gs::HotBucket a = ld_bucket(hot + gs::hot_bucket_of(pu0, q)), b = ld_bucket(hot + gs::hot_bucket_of(pv0, q));
+  const bool hu = gs::hot_match(a, true, ku, pu0), hv = gs::hot_match(b, true, kv, pv0);
+  if (hu & hv) return;
+  const uint32_t mu = hmain(ku, sh), mv = hmain(kv, sh);
+  uint4 x{}, y{};
+  uint32_t pu = g, pv = g;
+  if (!hu) x = tab[mu];
+  if (!hv) y = tab[mv];
+  if (!hu) pu = probe_main<false>(tab, mask, sh, ku, mu, x);
+  if (!hv) pv = probe_main<false>(tab, mask, sh, kv, mv, y);
+  if (((pu >> 1) ^ (pv >> 1)) == 0x12345671u) sink[0] = pu;
+}
+
 int main(int argc, char** argv) {
   setvbuf(stdout, nullptr, _IONBF, 0);
   const int logs = 27, scale = 26;
@@ -481,17 +513,48 @@ int main(int argc, char** argv) {
   // batches, as the 3-deep pipelined step runs them. A = main only, M1 = direct-mapped index of
   // {key, slot, anc} entries first. The variants alternate within every repetition; a repetition is
   // kRounds passes over the NB batches, timed on the host from the first launch to a device synchronise.
-  constexpr int kStreams = 3, kReps = 7, kRounds = 8, kVar = 5;
+  constexpr int kStreams = 3, kReps = 7, kRounds = 8, kVar = 6;
   hipStream_t st[kStreams];
   for (int i = 0; i < kStreams; ++i) CK(hipStreamCreateWithFlags(&st[i], hipStreamNonBlocking));
-  uint4* hotv[kVar] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  const int logv[kVar] = {0, 15, 16, 16, 17};  // entries (M1) or buckets (K2)
-  const char* namev[kVar] = {"A  main only", "M1 index 2^15", "M1 index 2^16", "K2 2^16 buckets", "K2 2^17 buckets"};
+  uint4* hotv[kVar] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  const int logv[kVar] = {0, 15, 16, 16, 17, 15};  // entries (M1) or buckets (K2, K5)
+  const char* namev[kVar] = {"A  main only", "M1 index 2^15", "M1 index 2^16", "K2 2^16 buckets", "K2 2^17 buckets", "K5 2^15 buckets"};
   unsigned long long* best2;
   CK(hipMalloc(&best2, (1ull << 20) * 8));
   printf("3 streams, %d x %u batches per repetition, %d repetitions, variants alternated\n", kRounds, NB, kReps);
   for (int v = 1; v < kVar; ++v) {
     const uint64_t H = 1ull << logv[v];
+    if (v == 5) {  // K5, built on the host: per bucket the five highest ranks among the ids seen at least twice
+      struct Cand {
+        uint32_t b;
+        unsigned long long r;
+        uint64_t stored;
+      };
+      std::vector<uint4> hc(cslots);
+      CK(hipMemcpy(hc.data(), cnt, cslots * 16, hipMemcpyDeviceToHost));
+      std::vector<Cand> cs;
+      for (const uint4& e : hc) {
+        const int64_t key = (int64_t)(((uint64_t)e.y << 32) | e.x);
+        const unsigned long long c = ((unsigned long long)e.w << 32) | e.z;
+        if (key == kEmpty || c < 2) continue;
+        const uint64_t m = gs::hot_product(key);
+        if (!gs::hot_stored(m)) continue;
+        cs.push_back({gs::hot_bucket_of(m, logv[v]), (c << 32) | (uint32_t)(((uint64_t)key * 0x9E3779B97F4A7C15ull) >> 32),
+                      gs::hot_stored(m)});
+      }
+      std::sort(cs.begin(), cs.end(), [](const Cand& x, const Cand& y) { return x.b != y.b ? x.b < y.b : x.r > y.r; });
+      std::vector<gs::HotBucket> hb(H);
+      for (auto& b : hb) gs::hot_clear(b, true);
+      unsigned long long held = 0;
+      for (size_t i = 0, j = 0; i < cs.size(); i = j)
+        for (j = i; j < cs.size() && cs[j].b == cs[i].b; ++j)
+          if (j - i < (size_t)gs::kHotMaxPlaces) gs::hot_set(hb[cs[i].b], (int)(j - i), true, cs[j].stored), ++held;
+      CK(hipMalloc(&hotv[v], H * 32));
+      CK(hipMemcpy(hotv[v], hb.data(), H * 32, hipMemcpyHostToDevice));
+      printf("K5 2^%d buckets (%llu KiB): %zu candidates seen twice or more, %llu keys held\n", logv[v],
+             (unsigned long long)(H * 32 >> 10), cs.size(), held);
+      continue;
+    }
     const bool k2 = v >= 3;
     uint64_t T = 63, acc = 0;
     for (int c = 63; c >= 2; --c) {
@@ -532,6 +595,7 @@ int main(int argc, char** argv) {
           const int64_t* d = dst + (size_t)b * B;
           hipStream_t q = st[(r * NB + b) % kStreams];
           if (v == 0) k_probe_ix<false><<<B / 256, 256, 0, q>>>(tab, (uint32_t)(slots - 1), sh, nullptr, 0, s, d, B, sink);
+          else if (v == 5) k_probe_k5<<<B / 256, 256, 0, q>>>(tab, (uint32_t)(slots - 1), sh, reinterpret_cast<const gs::HotBucket*>(hotv[v]), logv[v], 7u, s, d, B, sink);
           else if (v >= 3) k_probe_k2<<<B / 256, 256, 0, q>>>(tab, (uint32_t)(slots - 1), sh, hotv[v], 64 - logv[v], 7u, s, d, B, sink);
           else k_probe_ix<true><<<B / 256, 256, 0, q>>>(tab, (uint32_t)(slots - 1), sh, hotv[v], 64 - logv[v], s, d, B, sink);
         }
@@ -550,6 +614,9 @@ int main(int argc, char** argv) {
     for (int rep = 0; rep < kReps; ++rep) printf(" %6.2f", us[v][rep]);
     printf("  median %6.2f  min %6.2f  max %6.2f  spread %5.2f\n", med[v], s[0], s[kReps - 1], spread[v]);
   }
+  printf("  K5 2^15 buckets vs K2 2^16 buckets: %+.2f us/batch (%+.1f %%), 3 x the larger spread = %.2f -> %s\n", med[5] - med[3],
+         100.0 * (med[5] - med[3]) / med[3], 3 * std::max(spread[3], spread[5]),
+         med[3] - med[5] > 3 * std::max(spread[3], spread[5]) ? "FASTER" : "not faster");
   for (int v = 1; v < kVar; ++v)
     printf("  %s vs A: %+.2f us/batch (%+.1f %%), 3 x A's spread = %.2f -> %s\n", namev[v], med[v] - med[0],
            100.0 * (med[v] - med[0]) / med[0], 3 * spread[0], med[0] - med[v] > 3 * spread[0] ? "FASTER" : "not faster");
