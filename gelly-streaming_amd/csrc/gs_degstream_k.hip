@@ -11,7 +11,8 @@
 //   k_ds_rec_count / k_ds_rec_write   : the records of every occurrence, compacted in arrival order
 //   k_ds_live_count / k_ds_live_write : the live entries of a state array, compacted in index order
 // The maps, their composition, the segmented combine and the record rule are
-// gs_degstream_seq.hpp's; the tile count and the rank inside a tile are gs_scan.hpp's.
+// gs_degstream_seq.hpp's; the tile count, the rank inside a tile and the block-wide segmented
+// scan are gs_scan.hpp's.
 //
 // Concurrency. No atomics carry data: the only atomics are the error flag, the maximum and the
 // crossed-tile counter, read by the host after the fold. k_ds_seg_apply reads state[key] (the
@@ -38,42 +39,6 @@ namespace gs {
 namespace {
 
 __device__ __forceinline__ void raise_err(unsigned long long* ctl) { atomicOr(ctl + DS_ERR, 1ull); }
-
-__device__ __forceinline__ DsSeg seg_shfl_up(const DsSeg& x, int o) {
-  DsSeg y;
-  y.a = __shfl_up((long long)x.a, o, 64);
-  y.b = __shfl_up((long long)x.b, o, 64);
-  y.head = __shfl_up(x.head, o, 64);
-  return y;
-}
-
-// The combination of `mine` over the threads of the workgroup before this one (threads in
-// order), and *total = over all of them. wagg: BS / 64 DsSeg of LDS; holds a barrier after every
-// thread's earlier loads; the caller separates two calls on the same words with a barrier.
-template <uint32_t BS>
-__device__ __forceinline__ DsSeg block_seg_excl(DsSeg mine, DsSeg* wagg, DsSeg* total) {
-  static_assert(BS % 64 == 0, "whole waves");
-  const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
-  DsSeg inc = mine;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const DsSeg y = seg_shfl_up(inc, o);
-    if ((int)lane >= o) inc = ds_seg_combine(y, inc);
-  }
-  if (lane == 63) wagg[wid] = inc;
-  DsSeg excl = seg_shfl_up(inc, 1);
-  if (lane == 0) excl = ds_seg_identity();
-  __syncthreads();
-  DsSeg base = ds_seg_identity(), all = ds_seg_identity();
-#pragma unroll
-  for (uint32_t q = 0; q < BS / 64; ++q) {
-    const DsSeg w = wagg[q];
-    if (q < wid) base = ds_seg_combine(base, w);
-    all = ds_seg_combine(all, w);
-  }
-  *total = all;
-  return ds_seg_combine(base, excl);
-}
 
 __global__ __launch_bounds__(kDsBS) void k_ds_keys(const int64_t* __restrict__ src, const int64_t* __restrict__ dst,
                                                   const uint8_t* __restrict__ del, uint64_t occs, uint64_t stride,
@@ -159,7 +124,7 @@ __global__ __launch_bounds__(kDsBS) void k_ds_seg_reduce(const unsigned long lon
   DsMine m;
   load_mine(skey, spay, sgn, n, j0, m);
   DsSeg total;
-  (void)block_seg_excl<kDsBS>(reduce_mine(m, clamp != 0), wagg, &total);
+  (void)block_seg_excl<kDsBS, DsSegOps>(reduce_mine(m, clamp != 0), wagg, &total);
   if (threadIdx.x == 0) {
     agg[blockIdx.x] = total;
     if (blockIdx.x > 0 && !(m.head & 1u)) atomicAdd(ctl + DS_CROSSED, 1ull);
@@ -174,7 +139,7 @@ __global__ __launch_bounds__(kDsBS) void k_ds_seg_carry(const DsSeg* __restrict_
     const uint64_t t = t0 + threadIdx.x;
     const DsSeg mine = t < tiles ? agg[t] : ds_seg_identity();
     DsSeg total;
-    const DsSeg excl = block_seg_excl<kDsBS>(mine, wagg, &total);
+    const DsSeg excl = block_seg_excl<kDsBS, DsSegOps>(mine, wagg, &total);
     if (t < tiles) carry[t] = ds_seg_combine(run, excl);
     run = ds_seg_combine(run, total);
     __syncthreads();  // wagg is written again
@@ -208,7 +173,7 @@ __global__ __launch_bounds__(kDsBS) void k_ds_seg_apply(const unsigned long long
   if (bad) raise_err(ctl);
   if (threadIdx.x == 0) late_idx[blockIdx.x] = kDsNoLate;
   DsSeg total;
-  DsSeg in = block_seg_excl<kDsBS>(reduce_mine(m, clamp != 0), wagg, &total);  // (barrier: seeds loaded, late_idx set)
+  DsSeg in = block_seg_excl<kDsBS, DsSegOps>(reduce_mine(m, clamp != 0), wagg, &total);  // (barrier: seeds loaded, late_idx set)
   const DsSeg cin = carry[blockIdx.x];
   uint32_t top = 0;
 #pragma unroll

@@ -85,6 +85,21 @@ GS_DS_HD DsSeg ds_seg_combine(const DsSeg& first, const DsSeg& then) {
 GS_DS_HD int64_t ds_seg_before(const DsSeg& before, bool head, int64_t seed) {
   return head ? seed : ds_apply(DsPair{before.a, before.b}, seed);
 }
+#if defined(__HIPCC__)
+// what gs_scan.hpp's block_seg_excl needs of a DsSeg
+struct DsSegOps {
+  using Seg = DsSeg;
+  static __device__ __forceinline__ DsSeg identity() { return ds_seg_identity(); }
+  static __device__ __forceinline__ DsSeg combine(const DsSeg& a, const DsSeg& b) { return ds_seg_combine(a, b); }
+  static __device__ __forceinline__ DsSeg shfl_up(const DsSeg& x, int o) {
+    DsSeg y;
+    y.a = __shfl_up((long long)x.a, o, 64);
+    y.b = __shfl_up((long long)x.b, o, 64);
+    y.head = __shfl_up(x.head, o, 64);
+    return y;
+  }
+};
+#endif
 
 // ---- rule 2
 GS_DS_HD uint32_t ds_record_count(uint32_t old_d, uint32_t new_d, int c) {

@@ -8,7 +8,11 @@
 // points all of them have (sync, get_stream, wait_stream, the null check, the truncation error).
 // Every device array a handle owns is a DevBuf (gs_devbuf.hpp), every event, stream and pinned
 // host block an Event, Stream or HostBuf (gs_own.hpp): deleting the handle releases them. Groups
-// of DevBufs that share a capacity grow through grow_group (gs_grow.hpp).
+// of DevBufs that share a capacity grow through grow_group (gs_grow.hpp). All of it is linked into
+// one library, so every summary owns one prefix for its names in namespace gs, in its lower,
+// camel and upper case spellings (ts_, kTs, Ts, TS_): degree, tri, slice, dist, sp, mt, ts (the
+// sampling triangle estimate), ds (the degree streams), trs (the triangle streams); a new summary
+// takes a new one (tests/test_one_definition.py).
 #pragma once
 #include <hip/hip_runtime.h>
 

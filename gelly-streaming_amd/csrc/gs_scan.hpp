@@ -1,8 +1,9 @@
 // gs_scan.hpp -- the device primitives of the flag / scan / compact idiom (gfx950): a kernel
 // flags its elements and counts them per tile (block_count_to), launch_tile_scan (gs_sort.hpp)
 // turns the tile counts into tile bases, and a second kernel ranks every kept element inside its
-// tile (block_excl_scan) and writes the kept rows in order. Device functions only: a kernel in a
-// header would be compiled into every code object that includes it.
+// tile (block_excl_scan) and writes the kept rows in order. block_seg_excl is the same block scan
+// over a summary's own segmented element (slices, degree streams, triangle streams). Device
+// functions only: a kernel in a header would be compiled into every code object that includes it.
 //
 // Every thread of the workgroup calls these (they hold barriers), from uniform control flow, in
 // a workgroup of whole waves. How a kernel loads its flags and turns (tile base, rank) into an
@@ -54,6 +55,38 @@ __device__ __forceinline__ void block_count_to(uint32_t cnt, uint32_t* total_lds
   if ((threadIdx.x & 63u) == 0 && cnt) atomicAdd(total_lds, cnt);
   __syncthreads();
   if (threadIdx.x == 0) *out = *total_lds;
+}
+
+// The segmented form, over any associative combine. Ops supplies the element type Seg,
+// identity(), combine(first, then) and shfl_up(x, o), the wave shuffle of a Seg field by field.
+// Returns the combination of `mine` over the threads of the workgroup before this one (threads in
+// order), and *total = over all of them. wagg: BS / 64 Seg of LDS; holds a barrier after every
+// thread's earlier loads; the caller separates two calls on the same words with a barrier.
+template <uint32_t BS, class Ops>
+__device__ __forceinline__ typename Ops::Seg block_seg_excl(typename Ops::Seg mine, typename Ops::Seg* wagg,
+                                                            typename Ops::Seg* total) {
+  static_assert(BS % 64 == 0, "whole waves");
+  using Seg = typename Ops::Seg;
+  const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
+  Seg inc = mine;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const Seg y = Ops::shfl_up(inc, o);
+    if ((int)lane >= o) inc = Ops::combine(y, inc);
+  }
+  if (lane == 63) wagg[wid] = inc;
+  Seg excl = Ops::shfl_up(inc, 1);
+  if (lane == 0) excl = Ops::identity();
+  __syncthreads();
+  Seg base = Ops::identity(), all = Ops::identity();
+#pragma unroll
+  for (uint32_t q = 0; q < BS / 64; ++q) {
+    const Seg w = wagg[q];
+    if (q < wid) base = Ops::combine(base, w);
+    all = Ops::combine(all, w);
+  }
+  *total = all;
+  return Ops::combine(base, excl);
 }
 
 }  // namespace gs

@@ -16,7 +16,7 @@
 //   k_slice_count / k_slice_gather / k_slice_stats : the COUNT op, the neighbourhood export,
 //                    the diagnostics
 // The segmented-combine operator and all tile / carry index arithmetic are gs_slice_seg.hpp's;
-// the tile count and the rank inside a tile are gs_scan.hpp's.
+// the tile count, the rank inside a tile and the block-wide segmented scan are gs_scan.hpp's.
 //
 // What bounds every loop:
 //   * per-element kernels handle one element per thread, its index tested against the count;
@@ -34,40 +34,6 @@
 
 namespace gs {
 namespace {
-
-__device__ __forceinline__ SegPair seg_shfl_up(const SegPair& p, int o) {
-  SegPair r;
-  r.heads = __shfl_up(p.heads, o, 64);
-  r.val = (int64_t)__shfl_up((long long)p.val, o, 64);
-  return r;
-}
-
-// The stretch before this thread's inside its workgroup (threads in order), and the
-// workgroup's whole stretch. wtot: one SegPair per wave in LDS; the caller separates two calls
-// with a barrier.
-template <int OP, uint32_t BS>
-__device__ __forceinline__ SegPair block_seg_excl(const SegPair& agg, SegPair* wtot, SegPair* total) {
-  const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
-  SegPair inc = agg;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const SegPair y = seg_shfl_up(inc, o);
-    if ((int)lane >= o) inc = seg_combine<OP>(y, inc);
-  }
-  SegPair ex = seg_shfl_up(inc, 1);
-  if (lane == 0) ex = seg_identity<OP>();
-  if (lane == 63) wtot[wid] = inc;
-  __syncthreads();
-  SegPair before = seg_identity<OP>(), all = seg_identity<OP>();
-#pragma unroll
-  for (uint32_t q = 0; q < BS / 64; ++q) {
-    const SegPair w = wtot[q];
-    if (q < wid) before = seg_combine<OP>(before, w);
-    all = seg_combine<OP>(all, w);
-  }
-  *total = all;
-  return seg_combine<OP>(before, ex);
-}
 
 __global__ __launch_bounds__(kSliceBS) void k_slice_expand(const int64_t* src, const int64_t* dst, const int64_t* val,
                                                            uint64_t n, uint64_t stride, int dir, int copy,
@@ -177,7 +143,7 @@ __global__ __launch_bounds__(kSliceBS) void k_slice_reduce(const uint8_t* __rest
     }
   }
   SegPair total;
-  const SegPair before = block_seg_excl<OP, kSliceBS>(run, wtot, &total);
+  const SegPair before = block_seg_excl<kSliceBS, SliceSegOps<OP>>(run, wtot, &total);
   const uint64_t base = tbase[t];
 #pragma unroll
   for (uint32_t k = 0; k < kSlicePer; ++k) {
@@ -215,7 +181,7 @@ __global__ __launch_bounds__(kSliceBS) void k_slice_carry(const uint32_t* __rest
       a.val = trail[t];
     }
     SegPair total;
-    const SegPair ex = block_seg_excl<OP, kSliceBS>(a, wtot, &total);
+    const SegPair ex = block_seg_excl<kSliceBS, SliceSegOps<OP>>(a, wtot, &total);
     if (t < nt) carry[t] = seg_combine<OP>(run, ex).val;
     run = seg_combine<OP>(run, total);
     __syncthreads();

@@ -75,6 +75,22 @@ GS_SLICE_HD void seg_push(SegPair& run, bool head, int64_t v) {
   }
 }
 
+#if defined(__HIPCC__)
+// what gs_scan.hpp's block_seg_excl needs of a SegPair
+template <int OP>
+struct SliceSegOps {
+  using Seg = SegPair;
+  static __device__ __forceinline__ SegPair identity() { return seg_identity<OP>(); }
+  static __device__ __forceinline__ SegPair combine(const SegPair& a, const SegPair& b) { return seg_combine<OP>(a, b); }
+  static __device__ __forceinline__ SegPair shfl_up(const SegPair& p, int o) {
+    SegPair r;
+    r.heads = __shfl_up(p.heads, o, 64);
+    r.val = (int64_t)__shfl_up((long long)p.val, o, 64);
+    return r;
+  }
+};
+#endif
+
 // ---- entries of a window of n edges
 GS_SLICE_HD uint64_t slice_entries(uint64_t n, int dir) { return dir == kSliceAll ? 2 * n : n; }
 // the edge an entry (a sort payload) came from

@@ -1,8 +1,8 @@
 // gs_tristream.cpp -- the triangle streams behind include/gs_summary.h's gs_tristream_* section:
 // every record example/ExactTriangleCount.java emits, exact in arrival order wherever the stream
 // is cut into folds. State layout and kernels are described in gs_tristream.hpp /
-// gs_tristream_k.hip, the rules and the exactness argument in gs_tristream_seq.hpp (ts_fold_seq,
-// ts_fold_parts) and DESIGN.md section 6j.
+// gs_tristream_k.hip, the rules and the exactness argument in gs_tristream_seq.hpp (trs_fold_seq,
+// trs_fold_parts) and DESIGN.md section 6j.
 //
 // A fold of n arrivals: growth of the vertex table is decided first from host-known totals; the
 // distinct streams' vertex phase gives every new id its rank; the arrivals are canonised and
@@ -27,8 +27,8 @@
 using namespace gsi;
 
 struct gs_tristream_s : StreamOwner, VertexTable {  // (the vertex table and the vertices in rank order)
-  int mode = gs::kTsCount;
-  DevBuf<unsigned long long> ctl;   // gs::TsCtl words
+  int mode = gs::kTrsCount;
+  DevBuf<unsigned long long> ctl;   // gs::TrsCtl words
   DevBuf<unsigned long long> dctl;  // gs::DistCtl words of the vertex phase
   DevBuf<int64_t> counter;          // [dist_vid_cap(vcap)] t of every rank
   // adjacency: two buffers, the merge of a fold reads one and writes the other
@@ -45,8 +45,8 @@ struct gs_tristream_s : StreamOwner, VertexTable {  // (the vertex table and the
   DevBuf<int64_t> lo, hi, nx, ny, rx, ry;
   DevBuf<uint32_t> nf, rf, blk, cnt, roff;
   DevBuf<uint8_t> flags, is_new;
-  DevBuf<gs::TsRowInfo> info;
-  DevBuf<gs::TsSeg> a_agg, a_carry;
+  DevBuf<gs::TrsRowInfo> info;
+  DevBuf<gs::TrsSeg> a_agg, a_carry;
   // the rows and records of the last fold, and the record scan's scratch
   uint64_t w_cap = 0;
   DevBuf<uint32_t> row_closed;
@@ -54,7 +54,7 @@ struct gs_tristream_s : StreamOwner, VertexTable {  // (the vertex table and the
   uint64_t r_cap = 0;
   DevBuf<uint32_t> r_arr, r_delta;
   DevBuf<int64_t> r_v, r_key, r_cnt;
-  DevBuf<gs::TsSeg> agg, carry;
+  DevBuf<gs::TrsSeg> agg, carry;
   SortScratch sort;
   // device staging of a host fold
   uint64_t h_cap = 0;
@@ -74,11 +74,11 @@ struct gs_tristream_s : StreamOwner, VertexTable {  // (the vertex table and the
   bool kept = true;  // false after a fold the library cut into pieces
   // gs_testing_tristream_tune (profile, record limit) and the last profiled fold's phases
   bool profile = false;
-  uint64_t max_records = gs::kTsMaxRecords;
+  uint64_t max_records = gs::kTrsMaxRecords;
   uint64_t phase_us[6] = {0, 0, 0, 0, 0, 0};
 
-  gs::TsAdj adj(int side, uint64_t n) const {
-    gs::TsAdj a;
+  gs::TrsAdj adj(int side, uint64_t n) const {
+    gs::TrsAdj a;
     a.x = ax[side];
     a.y = ay[side];
     a.first = af[side];
@@ -89,9 +89,9 @@ struct gs_tristream_s : StreamOwner, VertexTable {  // (the vertex table and the
 
 namespace {
 
-// Adjacency entries are row indices of 32 bits (TsRowInfo).
-constexpr uint64_t kTsMaxEntries = 0xFFFFFFFFull;
-constexpr uint64_t kTsMinEdges = 32;
+// Adjacency entries are row indices of 32 bits (TrsRowInfo).
+constexpr uint64_t kTrsMaxEntries = 0xFFFFFFFFull;
+constexpr uint64_t kTrsMinEdges = 32;
 
 constexpr const char* kWhat = "tristream";  // check_handle: "null tristream handle"
 
@@ -111,7 +111,7 @@ int grow_vertices(gs_tristream_s* d, uint64_t cap) {
 }
 
 int ensure_adj(gs_tristream_s* d, int side, uint64_t need) {
-  GS_HIP(grow_group(d->stream, d->acap[side], need, std::min<uint64_t>(kTsMaxEntries, need + need / 2),
+  GS_HIP(grow_group(d->stream, d->acap[side], need, std::min<uint64_t>(kTrsMaxEntries, need + need / 2),
                     [&](uint64_t c) { return alloc_each(c, d->ax[side], d->ay[side], d->af[side]); }));
   return GS_OK;
 }
@@ -119,7 +119,7 @@ int ensure_adj(gs_tristream_s* d, int side, uint64_t need) {
 int ensure_scratch(gs_tristream_s* d, uint64_t n) {
   const auto alloc_scratch = [&](uint64_t c) {
     const uint64_t vtiles = gs::dist_tiles(2 * c, gs::DISTINCT_TILE);
-    const uint64_t tiles = gs::ts_tiles(c, gs::TRISTREAM_TILE) + 1;
+    const uint64_t tiles = gs::trs_tiles(c, gs::TRISTREAM_TILE) + 1;
     hipError_t e = alloc_each(2 * c, d->vslot, d->entry);
     if (e == hipSuccess) e = d->vflags.alloc(vtiles * gs::DISTINCT_TILE);
     if (e == hipSuccess) e = d->tbase.alloc(vtiles + 1);
@@ -130,12 +130,12 @@ int ensure_scratch(gs_tristream_s* d, uint64_t n) {
     if (e == hipSuccess) e = alloc_each(tiles, d->a_agg, d->a_carry);
     return e;
   };
-  GS_HIP(grow_group(d->stream, d->n_cap, n, std::min<uint64_t>(gs::kTsMaxFold, n + n / 4), alloc_scratch));
+  GS_HIP(grow_group(d->stream, d->n_cap, n, std::min<uint64_t>(gs::kTrsMaxFold, n + n / 4), alloc_scratch));
   return GS_OK;
 }
 
 int ensure_rows(gs_tristream_s* d, uint64_t rows) {
-  GS_HIP(grow_group(d->stream, d->w_cap, rows, std::min<uint64_t>(gs::kTsMaxFold, rows + rows / 4),
+  GS_HIP(grow_group(d->stream, d->w_cap, rows, std::min<uint64_t>(gs::kTrsMaxFold, rows + rows / 4),
                     [&](uint64_t c) { return alloc_each(c, d->row_closed, d->row_total); }));
   return GS_OK;
 }
@@ -143,13 +143,13 @@ int ensure_rows(gs_tristream_s* d, uint64_t rows) {
 int ensure_records(gs_tristream_s* d, uint64_t rows) {
   GS_HIP(grow_group(d->stream, d->r_cap, rows, rows + rows / 4, [&](uint64_t c) {
     const hipError_t e = alloc_each(c, d->r_arr, d->r_delta, d->r_v, d->r_key, d->r_cnt);
-    return e != hipSuccess ? e : alloc_each(gs::ts_tiles(c, gs::TRISTREAM_TILE) + 1, d->agg, d->carry);
+    return e != hipSuccess ? e : alloc_each(gs::trs_tiles(c, gs::TRISTREAM_TILE) + 1, d->agg, d->carry);
   }));
   return GS_OK;
 }
 
 int ensure_head_tiles(gs_tristream_s* d, uint64_t positions) {
-  const uint64_t tiles = gs::ts_tiles(positions, gs::TRISTREAM_TILE) + 1;
+  const uint64_t tiles = gs::trs_tiles(positions, gs::TRISTREAM_TILE) + 1;
   GS_HIP(grow_group(d->stream, d->x_tiles, tiles, tiles + tiles / 4, [&](uint64_t c) { return d->x_blk.alloc(c); }));
   return GS_OK;
 }
@@ -163,13 +163,13 @@ void forget_last(gs_tristream_s* d) {
 int fold_guard(gs_tristream_s* d, const void* src, const void* dst, size_t n) {
   if (int rc = check_handle(d, kWhat)) return rc;
   if (n && (!src || !dst)) return fail(GS_ERR_INVALID, "null edge arrays");
-  if ((uint64_t)n > gs::kTsMaxTotal || d->total + n > gs::kTsMaxTotal)
+  if ((uint64_t)n > gs::kTrsMaxTotal || d->total + n > gs::kTrsMaxTotal)
     return fail(GS_ERR_CAPACITY, "tristream fold: " + std::to_string(d->total) + " + " + std::to_string(n) +
                                      " arrivals pass 2^31 - 1 since the last reset");
-  if (2 * (d->edges + (uint64_t)n) > kTsMaxEntries)
+  if (2 * (d->edges + (uint64_t)n) > kTrsMaxEntries)
     return fail(GS_ERR_CAPACITY, "tristream adjacency: " + std::to_string(d->edges) + " + " + std::to_string(n) +
                                      " pairs could pass 2^32 - 1 entries");
-  const uint64_t piece = std::min<uint64_t>(n, gs::kTsMaxFold);
+  const uint64_t piece = std::min<uint64_t>(n, gs::kTrsMaxFold);
   const uint64_t need_v = d->nv + gs::dist_worst_vertices(n);
   if (need_v > gs::kDistMaxVertices ||
       (gs::dist_must_grow(d->nv, gs::dist_worst_vertices(piece), d->vcap) &&
@@ -193,7 +193,7 @@ int sort_keys(gs_tristream_s* d, const int64_t* key, uint64_t n, uint64_t bound,
   return GS_OK;
 }
 
-// 0 < n <= kTsMaxFold device arrivals on d->stream
+// 0 < n <= kTrsMaxFold device arrivals on d->stream
 int fold_piece(gs_tristream_s* d, const int64_t* src, const int64_t* dst, uint64_t n, uint64_t stride) {
   hipStream_t st = d->stream;
   const uint64_t t0 = d->total;
@@ -207,8 +207,8 @@ int fold_piece(gs_tristream_s* d, const int64_t* src, const int64_t* dst, uint64
   PhaseTimer timer(st, d->profile, d->phase_us, 6);
   timer.mark(0);
   GS_HIP(hipMemsetAsync(d->dctl, 0, gs::DIST_CTL_WORDS * 8, st));
-  static_assert(gs::TS_ERR == 0, "the error word outlives a fold: every wait reads it");
-  GS_HIP(hipMemsetAsync(d->ctl + 1, 0, (gs::TS_CTL_WORDS - 1) * 8, st));
+  static_assert(gs::TRS_ERR == 0, "the error word outlives a fold: every wait reads it");
+  GS_HIP(hipMemsetAsync(d->ctl + 1, 0, (gs::TRS_CTL_WORDS - 1) * 8, st));
   // 1. ranks for every endpoint; canonical pairs
   GS_LAUNCH(gs::launch_dist_vertices(src, dst, n, stride, vt, d->vslot, d->vflags, d->tbase, d->nv, d->vid, ranks,
                                      d->entry, d->dctl, st));
@@ -221,18 +221,18 @@ int fold_piece(gs_tristream_s* d, const int64_t* src, const int64_t* dst, uint64
   old.y = d->ay[d->cur];
   old.n = d->entries;
   GS_LAUNCH(gs::launch_tri_flag_new(cur.pay, d->lo, d->hi, n, old, d->flags, d->blk, st));
-  GS_LAUNCH(gs::launch_tile_scan(d->blk, gs::tri_blocks(n), d->ctl + gs::TS_NEW, st));
-  GS_LAUNCH(gs::launch_ts_compact_new(cur.pay, d->lo, d->hi, n, d->flags, d->blk, t0, d->nx, d->ny, d->nf, d->is_new,
-                                      d->n_cap, st));
+  GS_LAUNCH(gs::launch_tile_scan(d->blk, gs::tri_blocks(n), d->ctl + gs::TRS_NEW, st));
+  GS_LAUNCH(gs::launch_trs_compact_new(cur.pay, d->lo, d->hi, n, d->flags, d->blk, t0, d->nx, d->ny, d->nf, d->is_new,
+                                       d->n_cap, st));
   // the first wait: the new pairs, the new ids
-  unsigned long long c[gs::TS_CTL_WORDS], v[gs::DIST_CTL_WORDS];
+  unsigned long long c[gs::TRS_CTL_WORDS], v[gs::DIST_CTL_WORDS];
   GS_HIP(hipMemcpyAsync(c, d->ctl, sizeof(c), hipMemcpyDeviceToHost, st));
   GS_HIP(hipMemcpyAsync(v, d->dctl, sizeof(v), hipMemcpyDeviceToHost, st));
   timer.mark(1);
   GS_HIP(hipStreamSynchronize(st));
   if (v[gs::DIST_OVERFLOW]) return fail(GS_ERR_HIP, "tristream fold: the vertex table overflowed (the handle's state is undefined)");
-  if (c[gs::TS_ERR]) return fail(GS_ERR_HIP, "tristream fold: an index out of range (the handle's state is undefined)");
-  const uint64_t m = c[gs::TS_NEW];
+  if (c[gs::TRS_ERR]) return fail(GS_ERR_HIP, "tristream fold: an index out of range (the handle's state is undefined)");
+  const uint64_t m = c[gs::TRS_NEW];
   if (v[gs::DIST_NEW_V] > 2 * n || m > n) return fail(GS_ERR_HIP, "tristream fold: counts out of range");
   d->nv += v[gs::DIST_NEW_V];  // (the table holds them whatever becomes of the fold; their counters are 0)
   // 3. the stamped merge into the other buffer
@@ -243,72 +243,72 @@ int fold_piece(gs_tristream_s* d, const int64_t* src, const int64_t* dst, uint64
     if (int rc = ensure_adj(d, other, merged)) return rc;
     if (int rc = ensure_head_tiles(d, merged)) return rc;
     if (int rc = sort_keys(d, d->ny, m, 0, &cur)) return rc;
-    GS_LAUNCH(gs::launch_ts_reverse(cur.pay, d->nx, d->ny, d->nf, m, d->rx, d->ry, d->rf, st));
-    gs::TsAdjOut out;
+    GS_LAUNCH(gs::launch_trs_reverse(cur.pay, d->nx, d->ny, d->nf, m, d->rx, d->ry, d->rf, st));
+    gs::TrsAdjOut out;
     out.x = d->ax[other];
     out.y = d->ay[other];
     out.first = d->af[other];
     out.cap = d->acap[other];
-    GS_LAUNCH(gs::launch_ts_merge(d->adj(d->cur, d->entries), d->nx, d->ny, d->nf, d->rx, d->ry, d->rf, m, out, st));
-    GS_LAUNCH(gs::launch_ts_head_count(d->ax[other], merged, d->x_blk, st));
-    GS_LAUNCH(gs::launch_tile_scan(d->x_blk, gs::ts_tiles(merged, gs::TRISTREAM_TILE), d->ctl + gs::TS_HEADS, st));
+    GS_LAUNCH(gs::launch_trs_merge(d->adj(d->cur, d->entries), d->nx, d->ny, d->nf, d->rx, d->ry, d->rf, m, out, st));
+    GS_LAUNCH(gs::launch_trs_head_count(d->ax[other], merged, d->x_blk, st));
+    GS_LAUNCH(gs::launch_tile_scan(d->x_blk, gs::trs_tiles(merged, gs::TRISTREAM_TILE), d->ctl + gs::TRS_HEADS, st));
     side = other;
   }
-  const gs::TsAdj M = d->adj(side, merged);
+  const gs::TrsAdj M = d->adj(side, merged);
   timer.mark(2);
   // 4. rows and the count pass; the reduce half of the scan over the arrivals
-  GS_LAUNCH(gs::launch_ts_rows(M, d->lo, d->hi, d->mode == gs::kTsIgnore ? d->is_new.get() : nullptr, n, d->info,
-                               d->ctl, st));
-  GS_LAUNCH(gs::launch_ts_count(M, d->info, n, t0, d->cnt, d->ctl, st));
-  GS_LAUNCH(gs::launch_ts_arr_reduce(d->cnt, n, d->a_agg, d->a_carry, d->ctl, st));
+  GS_LAUNCH(gs::launch_trs_rows(M, d->lo, d->hi, d->mode == gs::kTrsIgnore ? d->is_new.get() : nullptr, n, d->info,
+                                d->ctl, st));
+  GS_LAUNCH(gs::launch_trs_count(M, d->info, n, t0, d->cnt, d->ctl, st));
+  GS_LAUNCH(gs::launch_trs_arr_reduce(d->cnt, n, d->a_agg, d->a_carry, d->ctl, st));
   // the second wait: the record count
   GS_HIP(hipMemcpyAsync(c, d->ctl, sizeof(c), hipMemcpyDeviceToHost, st));
   timer.mark(3);
   GS_HIP(hipStreamSynchronize(st));
-  if (c[gs::TS_ERR]) return fail(GS_ERR_HIP, "tristream fold: an index out of range (the handle's state is undefined)");
-  const uint64_t closed = c[gs::TS_CLOSED], recs = c[gs::TS_RECORDS];
+  if (c[gs::TRS_ERR]) return fail(GS_ERR_HIP, "tristream fold: an index out of range (the handle's state is undefined)");
+  const uint64_t closed = c[gs::TRS_CLOSED], recs = c[gs::TRS_RECORDS];
   if (recs > d->max_records)
     return fail(GS_ERR_CAPACITY, "tristream fold: " + std::to_string(recs) + " records pass the limit of " +
                                      std::to_string(d->max_records) + " per fold (fold smaller pieces: the stream is the same)");
-  if (m && c[gs::TS_HEADS] > merged) return fail(GS_ERR_HIP, "tristream fold: counts out of range");
+  if (m && c[gs::TRS_HEADS] > merged) return fail(GS_ERR_HIP, "tristream fold: counts out of range");
   if (int rc = ensure_rows(d, n)) return rc;
   if (recs) {
     if (int rc = ensure_records(d, recs)) return rc;
     if (int rc = sort_scratch_ensure(d->sort, recs, st)) return rc;
   }
   // 5. from here on the fold is visible: rows and offsets, 6. the ordered write
-  GS_LAUNCH(gs::launch_ts_arr_apply(d->cnt, n, d->a_carry, d->triangles, d->row_closed, d->row_total, d->roff, st));
+  GS_LAUNCH(gs::launch_trs_arr_apply(d->cnt, n, d->a_carry, d->triangles, d->row_closed, d->row_total, d->roff, st));
   if (recs)
-    GS_LAUNCH(gs::launch_ts_write(M, d->info, d->lo, d->hi, d->cnt, d->roff, n, t0, d->r_arr, d->r_v, d->r_delta, recs,
-                                  d->ctl, st));
+    GS_LAUNCH(gs::launch_trs_write(M, d->info, d->lo, d->hi, d->cnt, d->roff, n, t0, d->r_arr, d->r_v, d->r_delta, recs,
+                                   d->ctl, st));
   timer.mark(4);
   if (recs) {
     // 7. ranks, the stable sort by rank, the seeded segmented sum, the counters
     GS_LAUNCH(gs::launch_dist_rank(vt, d->r_v, recs, d->r_key, nullptr, st));
     if (int rc = sort_keys(d, d->r_key, recs, d->nv, &cur)) return rc;
     timer.mark(5);
-    GS_LAUNCH(gs::launch_ts_seg_pass(cur.key, cur.pay, d->r_delta, recs, d->counter, ranks, d->agg, d->carry, d->r_cnt,
-                                     d->ctl, st));
+    GS_LAUNCH(gs::launch_trs_seg_pass(cur.key, cur.pay, d->r_delta, recs, d->counter, ranks, d->agg, d->carry, d->r_cnt,
+                                      d->ctl, st));
     timer.mark(6);
   }
   if (m) {
     d->cur = other;
     d->entries = merged;
     d->edges += m;
-    d->vertices = c[gs::TS_HEADS];
+    d->vertices = c[gs::TRS_HEADS];
   }
   d->total += n;
   d->triangles += (int64_t)closed;
   d->last_n = n;
   d->last_rec = recs;
   d->last_new = m;
-  d->last_tiles = gs::ts_tiles(recs, gs::TRISTREAM_TILE);
+  d->last_tiles = gs::trs_tiles(recs, gs::TRISTREAM_TILE);
   d->kept = true;
   timer.finish();
   return GS_OK;
 }
 
-// the whole fold, cut into pieces of at most kTsMaxFold arrivals; host: the arrays are HOST arrays
+// the whole fold, cut into pieces of at most kTrsMaxFold arrivals; host: the arrays are HOST arrays
 int fold_all(gs_tristream_s* d, const int64_t* src, const int64_t* dst, size_t n, uint64_t stride, bool host) {
   if (n == 0) {
     forget_last(d);
@@ -316,11 +316,11 @@ int fold_all(gs_tristream_s* d, const int64_t* src, const int64_t* dst, size_t n
   }
   DeviceGuard g(d->device);
   uint64_t sum[3] = {0, 0, 0};
-  for (uint64_t at = 0; at < n; at += gs::kTsMaxFold) {
-    const uint64_t len = std::min<uint64_t>(gs::kTsMaxFold, n - at);
+  for (uint64_t at = 0; at < n; at += gs::kTrsMaxFold) {
+    const uint64_t len = std::min<uint64_t>(gs::kTrsMaxFold, n - at);
     const int64_t *ps = src + at * stride, *pd = dst + at * stride;
     if (host) {
-      GS_HIP(grow_group(d->stream, d->h_cap, len, std::min<uint64_t>(gs::kTsMaxFold, len + len / 4),
+      GS_HIP(grow_group(d->stream, d->h_cap, len, std::min<uint64_t>(gs::kTrsMaxFold, len + len / 4),
                         [&](uint64_t c) { return d->stage.alloc(2 * c); }));
       int64_t* s0 = d->stage;
       GS_HIP(hipMemcpyAsync(s0, ps, len * 8, hipMemcpyHostToDevice, d->stream));
@@ -336,7 +336,7 @@ int fold_all(gs_tristream_s* d, const int64_t* src, const int64_t* dst, size_t n
     sum[1] += d->last_rec;
     sum[2] += d->last_new;
   }
-  if (n > gs::kTsMaxFold) {
+  if (n > gs::kTrsMaxFold) {
     d->last_n = sum[0];
     d->last_rec = sum[1];
     d->last_new = sum[2];
@@ -396,14 +396,14 @@ int counts_impl(gs_tristream_s* d, int64_t* vertex, int64_t* count, size_t cap, 
   GS_HIP(grow_group(st, d->v_cap, heads, heads + heads / 4, [&](uint64_t c) { return alloc_each(c, d->hv, d->hrank); }));
   const int64_t* x = d->ax[d->cur];
   const uint64_t ranks = gs::dist_vid_cap(d->vcap);
-  GS_LAUNCH(gs::launch_ts_head_count(x, d->entries, d->x_blk, st));
-  GS_LAUNCH(gs::launch_tile_scan(d->x_blk, gs::ts_tiles(d->entries, gs::TRISTREAM_TILE), d->ctl + gs::TS_LIVE, st));
-  GS_LAUNCH(gs::launch_ts_head_write(x, d->entries, d->x_blk, d->hv, heads, st));
+  GS_LAUNCH(gs::launch_trs_head_count(x, d->entries, d->x_blk, st));
+  GS_LAUNCH(gs::launch_tile_scan(d->x_blk, gs::trs_tiles(d->entries, gs::TRISTREAM_TILE), d->ctl + gs::TRS_LIVE, st));
+  GS_LAUNCH(gs::launch_trs_head_write(x, d->entries, d->x_blk, d->hv, heads, st));
   GS_LAUNCH(gs::launch_dist_rank(d->vtable(), d->hv, heads, d->hrank, nullptr, st));
-  GS_LAUNCH(gs::launch_ts_live_count(d->hrank, heads, d->counter, ranks, d->x_blk, st));
-  GS_LAUNCH(gs::launch_tile_scan(d->x_blk, gs::ts_tiles(heads, gs::TRISTREAM_TILE), d->ctl + gs::TS_LIVE, st));
+  GS_LAUNCH(gs::launch_trs_live_count(d->hrank, heads, d->counter, ranks, d->x_blk, st));
+  GS_LAUNCH(gs::launch_tile_scan(d->x_blk, gs::trs_tiles(heads, gs::TRISTREAM_TILE), d->ctl + gs::TRS_LIVE, st));
   unsigned long long rows = 0;
-  GS_HIP(hipMemcpyAsync(&rows, d->ctl + gs::TS_LIVE, 8, hipMemcpyDeviceToHost, st));
+  GS_HIP(hipMemcpyAsync(&rows, d->ctl + gs::TRS_LIVE, 8, hipMemcpyDeviceToHost, st));
   GS_HIP(hipStreamSynchronize(st));
   if (rows > heads) return fail(GS_ERR_HIP, "tristream counts: counts out of range");
   *n = rows;
@@ -415,7 +415,7 @@ int counts_impl(gs_tristream_s* d, int64_t* vertex, int64_t* count, size_t cap, 
     da = vertex ? d->o_a.get() : nullptr;
     db = count ? d->o_b.get() : nullptr;
   }
-  GS_LAUNCH(gs::launch_ts_live_write(d->hv, d->hrank, heads, d->counter, ranks, d->x_blk, da, db, rows, st));
+  GS_LAUNCH(gs::launch_trs_live_write(d->hv, d->hrank, heads, d->counter, ranks, d->x_blk, da, db, rows, st));
   if (to_host) {
     if (vertex) GS_HIP(hipMemcpyAsync(vertex, da, rows * 8, hipMemcpyDeviceToHost, st));
     if (count) GS_HIP(hipMemcpyAsync(count, db, rows * 8, hipMemcpyDeviceToHost, st));
@@ -433,17 +433,17 @@ int gs_tristream_destroy(gs_tristream d) { return owner_destroy(d); }
 int gs_tristream_create(gs_tristream* out, int device, int repeats_mode, uint64_t edge_hint) {
   if (!out) return fail(GS_ERR_INVALID, "out is null");
   *out = nullptr;
-  if (repeats_mode < 0 || repeats_mode >= gs::kTsModes) return fail(GS_ERR_INVALID, "tristream create: unknown repeats mode");
-  if (2 * edge_hint > kTsMaxEntries || gs::dist_slots_for(2 * edge_hint) > gs::kDistMaxSlots)
+  if (repeats_mode < 0 || repeats_mode >= gs::kTrsModes) return fail(GS_ERR_INVALID, "tristream create: unknown repeats mode");
+  if (2 * edge_hint > kTrsMaxEntries || gs::dist_slots_for(2 * edge_hint) > gs::kDistMaxSlots)
     return fail(GS_ERR_CAPACITY, "tristream create: the hint passes 2^31 - 1 pairs");
   if (int rc = check_device_index(device)) return rc;
   return owner_create(out, device, [&](gs_tristream_s* d) -> int {
     d->mode = repeats_mode;
-    GS_HIP(d->ctl.alloc(gs::TS_CTL_WORDS));
-    GS_HIP(hipMemsetAsync(d->ctl, 0, gs::TS_CTL_WORDS * 8, d->stream));
+    GS_HIP(d->ctl.alloc(gs::TRS_CTL_WORDS));
+    GS_HIP(hipMemsetAsync(d->ctl, 0, gs::TRS_CTL_WORDS * 8, d->stream));
     GS_HIP(d->dctl.alloc(gs::DIST_CTL_WORDS));
     GS_HIP(hipMemsetAsync(d->dctl, 0, gs::DIST_CTL_WORDS * 8, d->stream));
-    const uint64_t e = std::max<uint64_t>(edge_hint, kTsMinEdges);
+    const uint64_t e = std::max<uint64_t>(edge_hint, kTrsMinEdges);
     if (int rc = ensure_adj(d, 0, 2 * e)) return rc;
     return grow_vertices(d, gs::dist_slots_for(e));
   });
@@ -454,7 +454,7 @@ int gs_tristream_reset(gs_tristream d) {
   DeviceGuard g(d->device);
   GS_LAUNCH(gs::launch_dist_init(d->vtable(), d->stream));
   GS_HIP(hipMemsetAsync(d->counter, 0, gs::dist_vid_cap(d->vcap) * 8, d->stream));
-  GS_HIP(hipMemsetAsync(d->ctl, 0, gs::TS_CTL_WORDS * 8, d->stream));
+  GS_HIP(hipMemsetAsync(d->ctl, 0, gs::TRS_CTL_WORDS * 8, d->stream));
   d->nv = d->vertices = d->edges = d->total = d->entries = 0;
   d->triangles = 0;
   forget_last(d);
@@ -505,7 +505,7 @@ int gs_tristream_count(gs_tristream d, uint64_t* out) {
   if (!out) return fail(GS_ERR_INVALID, "out is null");
   DeviceGuard g(d->device);
   unsigned long long err = 0;
-  GS_HIP(hipMemcpyAsync(&err, d->ctl + gs::TS_ERR, 8, hipMemcpyDeviceToHost, d->stream));
+  GS_HIP(hipMemcpyAsync(&err, d->ctl + gs::TRS_ERR, 8, hipMemcpyDeviceToHost, d->stream));
   GS_HIP(hipStreamSynchronize(d->stream));
   if (err) return fail(GS_ERR_HIP, "tristream: an index out of range in the last fold (the handle's state is undefined)");
   out[0] = (uint64_t)d->triangles;
@@ -533,14 +533,14 @@ int gs_testing_tristream_stats(void* handle, uint64_t* out) {
   if (int rc = check_handle(d, kWhat)) return rc;
   if (!out) return fail(GS_ERR_INVALID, "out is null");
   DeviceGuard g(d->device);
-  unsigned long long c[gs::TS_CTL_WORDS];
+  unsigned long long c[gs::TRS_CTL_WORDS];
   GS_HIP(hipMemcpyAsync(c, d->ctl, sizeof(c), hipMemcpyDeviceToHost, d->stream));
   GS_HIP(hipStreamSynchronize(d->stream));
   const bool any = d->last_n != 0;
   out[0] = d->last_tiles;
-  out[1] = any ? c[gs::TS_CROSSED] : 0;
-  out[2] = any ? c[gs::TS_HOT] : 0;
-  out[3] = any ? c[gs::TS_STEPS] : 0;
+  out[1] = any ? c[gs::TRS_CROSSED] : 0;
+  out[2] = any ? c[gs::TRS_HOT] : 0;
+  out[3] = any ? c[gs::TRS_STEPS] : 0;
   for (int i = 0; i < 6; ++i) out[4 + i] = d->phase_us[i];
   return GS_OK;
 }
@@ -553,8 +553,8 @@ int gs_testing_tristream_tune(void* handle, int what, int64_t value) {
     return GS_OK;
   }
   if (what == 1) {
-    if (value > (int64_t)gs::kTsMaxRecords) return fail(GS_ERR_INVALID, "tristream tune: the record limit is at most 2^27");
-    d->max_records = value > 0 ? (uint64_t)value : gs::kTsMaxRecords;
+    if (value > (int64_t)gs::kTrsMaxRecords) return fail(GS_ERR_INVALID, "tristream tune: the record limit is at most 2^27");
+    d->max_records = value > 0 ? (uint64_t)value : gs::kTrsMaxRecords;
     return GS_OK;
   }
   return fail(GS_ERR_INVALID, "tristream tune: unknown control");

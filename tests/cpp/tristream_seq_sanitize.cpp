@@ -1,9 +1,9 @@
 // tristream_seq_sanitize.cpp -- the triangle streams' rules header (csrc/gs_tristream_seq.hpp) in a
 // stand-alone host program, built with -fsanitize=address,undefined by tests/test_tristream_seq.py:
-//   * ts_fold_seq against a literal restatement of the reference's three operators
+//   * trs_fold_seq against a literal restatement of the reference's three operators
 //     (buildNeighborhood(false) + ProjectCanonicalEdges, IntersectNeighborhoods,
 //     SumAndEmitCounters of example/ExactTriangleCount.java) made of std::map and std::set;
-//   * ts_fold_parts, the kernels' decomposition, against ts_fold_seq at every tile size 1..9 and
+//   * trs_fold_parts, the kernels' decomposition, against trs_fold_seq at every tile size 1..9 and
 //     every two-way cut of streams of up to 40 arrivals, in both repeat modes;
 //   * the pins (tests/golden/tristream_pins.json, handed over as text: argv[1]);
 //   * the int64 extremes, the empty fold, a fold of loops only, the record limit.
@@ -74,7 +74,7 @@ struct Reference {
 };
 
 // the definition's rows and records as the reference's tuple sequence
-std::vector<Tuple> as_tuples(const std::vector<gs::TsRow>& rows, const std::vector<gs::TsRec>& recs) {
+std::vector<Tuple> as_tuples(const std::vector<gs::TrsRow>& rows, const std::vector<gs::TrsRec>& recs) {
   std::vector<Tuple> out;
   size_t r = 0;
   for (size_t a = 0; a < rows.size(); ++a) {
@@ -109,22 +109,22 @@ void check_reference() {
     Reference ref;
     std::vector<Tuple> want;
     for (size_t i = 0; i < s.size(); ++i) ref.edge(s[i], d[i], &want);
-    gs::TsState st;
-    std::vector<gs::TsRow> rows;
-    std::vector<gs::TsRec> recs;
+    gs::TrsState st;
+    std::vector<gs::TrsRow> rows;
+    std::vector<gs::TrsRec> recs;
     // in folds of 7: the arrival index restarts with every fold
     std::vector<Tuple> got;
     for (size_t at = 0; at < s.size(); at += 7) {
       rows.clear();
       recs.clear();
-      gs::ts_fold_seq(st, s.data() + at, d.data() + at, std::min<size_t>(7, s.size() - at), gs::kTsCount, &rows, &recs);
+      gs::trs_fold_seq(st, s.data() + at, d.data() + at, std::min<size_t>(7, s.size() - at), gs::kTrsCount, &rows, &recs);
       const std::vector<Tuple> t = as_tuples(rows, recs);
       got.insert(got.end(), t.begin(), t.end());
     }
     CHECK(got == want);
     CHECK(st.arrivals == s.size());
   }
-  puts("ok ts_fold_seq == the reference's operators (count mode, loop-free)");
+  puts("ok trs_fold_seq == the reference's operators (count mode, loop-free)");
 }
 
 void check_parts() {
@@ -133,23 +133,23 @@ void check_parts() {
     const size_t n = round < 4 ? (size_t)round : 8 + (size_t)(rng() % 33);  // up to 40
     std::vector<int64_t> s, d;
     random_stream(n, 4 + round % 6, true, &s, &d);
-    for (int mode = 0; mode < gs::kTsModes; ++mode) {
-      gs::TsState whole;
-      std::vector<gs::TsRow> wr;
-      std::vector<gs::TsRec> wc;
-      gs::ts_fold_seq(whole, s.data(), d.data(), n, mode, &wr, &wc);
+    for (int mode = 0; mode < gs::kTrsModes; ++mode) {
+      gs::TrsState whole;
+      std::vector<gs::TrsRow> wr;
+      std::vector<gs::TrsRec> wc;
+      gs::trs_fold_seq(whole, s.data(), d.data(), n, mode, &wr, &wc);
       for (uint32_t tile = 1; tile <= 9; ++tile)
         for (size_t cut = 0; cut <= n; ++cut) {
-          gs::TsState st;
-          std::vector<gs::TsRow> r1, r2;
-          std::vector<gs::TsRec> c1, c2;
-          const uint64_t x1 = gs::ts_fold_parts(st, s.data(), d.data(), cut, mode, tile, ~0ull >> 1, &r1, &c1);
-          const uint64_t x2 = gs::ts_fold_parts(st, s.data() + cut, d.data() + cut, n - cut, mode, tile, ~0ull >> 1, &r2, &c2);
+          gs::TrsState st;
+          std::vector<gs::TrsRow> r1, r2;
+          std::vector<gs::TrsRec> c1, c2;
+          const uint64_t x1 = gs::trs_fold_parts(st, s.data(), d.data(), cut, mode, tile, ~0ull >> 1, &r1, &c1);
+          const uint64_t x2 = gs::trs_fold_parts(st, s.data() + cut, d.data() + cut, n - cut, mode, tile, ~0ull >> 1, &r2, &c2);
           CHECK(x1 != ~0ull && x2 != ~0ull);
           crossed_any += x1 + x2;
           ++runs;
           // the second fold's arrival indices follow the cut
-          for (gs::TsRec& r : c2) r.arrival += (uint32_t)cut;
+          for (gs::TrsRec& r : c2) r.arrival += (uint32_t)cut;
           r1.insert(r1.end(), r2.begin(), r2.end());
           c1.insert(c1.end(), c2.begin(), c2.end());
           CHECK(r1 == wr);
@@ -159,21 +159,21 @@ void check_parts() {
     }
   }
   CHECK(crossed_any > 0);  // segments did cross tiles
-  printf("ok ts_fold_parts == ts_fold_seq (%llu runs, tiles 1..9, every cut, both modes)\n", (unsigned long long)runs);
+  printf("ok trs_fold_parts == trs_fold_seq (%llu runs, tiles 1..9, every cut, both modes)\n", (unsigned long long)runs);
 }
 
 void check_modes_and_limits() {
   // a repeated closing edge: counted again under `count`, nothing under `ignore`
   const int64_t s[] = {1, 2, 1, 1, 3, 3}, d[] = {2, 3, 3, 3, 1, 3};
-  for (int mode = 0; mode < gs::kTsModes; ++mode) {
-    gs::TsState st;
-    std::vector<gs::TsRow> rows;
-    std::vector<gs::TsRec> recs;
-    gs::ts_fold_seq(st, s, d, 6, mode, &rows, &recs);
+  for (int mode = 0; mode < gs::kTrsModes; ++mode) {
+    gs::TrsState st;
+    std::vector<gs::TrsRow> rows;
+    std::vector<gs::TrsRec> recs;
+    gs::trs_fold_seq(st, s, d, 6, mode, &rows, &recs);
     CHECK(rows.size() == 6 && rows[2].closed == 1 && rows[5].closed == 0);
-    CHECK(rows[3].closed == (mode == gs::kTsCount ? 1u : 0u) && rows[4].closed == rows[3].closed);
-    CHECK(st.total == (mode == gs::kTsCount ? 3 : 1));
-    CHECK(recs.size() == (mode == gs::kTsCount ? 9u : 3u));
+    CHECK(rows[3].closed == (mode == gs::kTrsCount ? 1u : 0u) && rows[4].closed == rows[3].closed);
+    CHECK(st.total == (mode == gs::kTrsCount ? 3 : 1));
+    CHECK(recs.size() == (mode == gs::kTrsCount ? 9u : 3u));
     CHECK(st.first.size() == 3 && st.arrivals == 6);
   }
   // the int64 extremes and -1 as vertices; the order of w is signed
@@ -181,49 +181,49 @@ void check_modes_and_limits() {
   const int64_t es[] = {lo, hi, -1, 7, lo, 7, hi}, ed[] = {7, 7, 7, 0, hi, hi, 0};
   // pairs: lo-7, hi-7, -1-7, 7-0, then lo-hi closes w = 7; 7-hi is a repeat; hi-0 closes w = 7
   for (uint32_t tile = 1; tile <= 3; ++tile) {
-    gs::TsState a, b;
-    std::vector<gs::TsRow> ra, rb;
-    std::vector<gs::TsRec> ca, cb;
-    gs::ts_fold_seq(a, es, ed, 7, gs::kTsCount, &ra, &ca);
-    CHECK(gs::ts_fold_parts(b, es, ed, 7, gs::kTsCount, tile, 1000, &rb, &cb) != ~0ull);
+    gs::TrsState a, b;
+    std::vector<gs::TrsRow> ra, rb;
+    std::vector<gs::TrsRec> ca, cb;
+    gs::trs_fold_seq(a, es, ed, 7, gs::kTrsCount, &ra, &ca);
+    CHECK(gs::trs_fold_parts(b, es, ed, 7, gs::kTrsCount, tile, 1000, &rb, &cb) != ~0ull);
     CHECK(ra == rb && ca == cb && a == b);
     CHECK(ra[4].closed == 1 && ca.size() >= 3 && ca[0].vertex == 7 && ca[1].vertex == lo && ca[2].vertex == hi);
   }
   {
     // two common neighbours -1 and 5 of lo and hi: -1 first
     const int64_t s2[] = {lo, lo, hi, hi, lo}, d2[] = {5, -1, 5, -1, hi};
-    gs::TsState a;
-    std::vector<gs::TsRow> ra;
-    std::vector<gs::TsRec> ca;
-    gs::ts_fold_seq(a, s2, d2, 5, gs::kTsCount, &ra, &ca);
+    gs::TrsState a;
+    std::vector<gs::TrsRow> ra;
+    std::vector<gs::TrsRec> ca;
+    gs::trs_fold_seq(a, s2, d2, 5, gs::kTrsCount, &ra, &ca);
     CHECK(ca.size() == 4 && ca[0].vertex == -1 && ca[1].vertex == 5 && ca[2].vertex == lo && ca[3].vertex == hi);
     CHECK(ca[2].count == 2 && ca[3].count == 2 && a.total == 2);
   }
   // the empty fold and a fold of loops only
   {
-    gs::TsState a, b;
-    std::vector<gs::TsRow> ra, rb;
-    std::vector<gs::TsRec> ca, cb;
-    gs::ts_fold_seq(a, nullptr, nullptr, 0, gs::kTsCount, &ra, &ca);
-    CHECK(gs::ts_fold_parts(b, nullptr, nullptr, 0, gs::kTsCount, 4, 10, &rb, &cb) == 0);
+    gs::TrsState a, b;
+    std::vector<gs::TrsRow> ra, rb;
+    std::vector<gs::TrsRec> ca, cb;
+    gs::trs_fold_seq(a, nullptr, nullptr, 0, gs::kTrsCount, &ra, &ca);
+    CHECK(gs::trs_fold_parts(b, nullptr, nullptr, 0, gs::kTrsCount, 4, 10, &rb, &cb) == 0);
     CHECK(ra.empty() && rb.empty() && a == b && a.arrivals == 0);
     const int64_t l[] = {3, 3, 9};
-    gs::ts_fold_seq(a, l, l, 3, gs::kTsCount, &ra, &ca);
-    CHECK(gs::ts_fold_parts(b, l, l, 3, gs::kTsCount, 2, 10, &rb, &cb) == 0);
+    gs::trs_fold_seq(a, l, l, 3, gs::kTrsCount, &ra, &ca);
+    CHECK(gs::trs_fold_parts(b, l, l, 3, gs::kTrsCount, 2, 10, &rb, &cb) == 0);
     CHECK(ra.size() == 3 && ra == rb && ca.empty() && cb.empty() && a == b && a.arrivals == 3 && a.first.empty());
   }
   // the record limit: nothing changes, and the two halves give the same stream
   {
     const int64_t s3[] = {1, 2, 1, 4, 4, 1}, d3[] = {2, 3, 3, 1, 2, 2};
-    gs::TsState a, b;
-    std::vector<gs::TsRow> ra, rb;
-    std::vector<gs::TsRec> ca, cb;
-    gs::ts_fold_seq(a, s3, d3, 6, gs::kTsCount, &ra, &ca);
+    gs::TrsState a, b;
+    std::vector<gs::TrsRow> ra, rb;
+    std::vector<gs::TrsRec> ca, cb;
+    gs::trs_fold_seq(a, s3, d3, 6, gs::kTrsCount, &ra, &ca);
     CHECK(ca.size() > 7);
-    CHECK(gs::ts_fold_parts(b, s3, d3, 6, gs::kTsCount, 4, 7, &rb, &cb) == ~0ull);
-    CHECK(rb.empty() && cb.empty() && b == gs::TsState());
-    CHECK(gs::ts_fold_parts(b, s3, d3, 3, gs::kTsCount, 4, 7, &rb, &cb) != ~0ull);
-    CHECK(gs::ts_fold_parts(b, s3 + 3, d3 + 3, 3, gs::kTsCount, 4, 7, &rb, &cb) != ~0ull);
+    CHECK(gs::trs_fold_parts(b, s3, d3, 6, gs::kTrsCount, 4, 7, &rb, &cb) == ~0ull);
+    CHECK(rb.empty() && cb.empty() && b == gs::TrsState());
+    CHECK(gs::trs_fold_parts(b, s3, d3, 3, gs::kTrsCount, 4, 7, &rb, &cb) != ~0ull);
+    CHECK(gs::trs_fold_parts(b, s3 + 3, d3 + 3, 3, gs::kTrsCount, 4, 7, &rb, &cb) != ~0ull);
     CHECK(rb == ra && a == b && cb.size() == ca.size());
   }
   puts("ok modes, extremes, empty and loop folds, the record limit");
@@ -251,18 +251,18 @@ std::map<std::string, std::vector<std::vector<int64_t>>> read_pins(const char* p
   return out;
 }
 
-void run_stream(const std::vector<std::vector<int64_t>>& edges, std::vector<gs::TsRow>* rows, std::vector<gs::TsRec>* recs,
+void run_stream(const std::vector<std::vector<int64_t>>& edges, std::vector<gs::TrsRow>* rows, std::vector<gs::TrsRec>* recs,
                 bool parts) {
   std::vector<int64_t> s, d;
   for (const auto& e : edges) {
     s.push_back(e.at(0));
     d.push_back(e.at(1));
   }
-  gs::TsState st;
+  gs::TrsState st;
   if (parts)
-    CHECK(gs::ts_fold_parts(st, s.data(), d.data(), s.size(), gs::kTsCount, 3, 1000, rows, recs) != ~0ull);
+    CHECK(gs::trs_fold_parts(st, s.data(), d.data(), s.size(), gs::kTrsCount, 3, 1000, rows, recs) != ~0ull);
   else
-    gs::ts_fold_seq(st, s.data(), d.data(), s.size(), gs::kTsCount, rows, recs);
+    gs::trs_fold_seq(st, s.data(), d.data(), s.size(), gs::kTrsCount, rows, recs);
 }
 
 void check_pins(const char* path) {
@@ -271,8 +271,8 @@ void check_pins(const char* path) {
   for (int parts = 0; parts < 2; ++parts) {
     for (int k = 0; k < 2; ++k) {
       const std::string id = std::to_string(k);
-      std::vector<gs::TsRow> rows;
-      std::vector<gs::TsRec> recs;
+      std::vector<gs::TrsRow> rows;
+      std::vector<gs::TrsRec> recs;
       run_stream(pins["stream_" + id], &rows, &recs, parts != 0);
       const auto& want = pins["records_" + id];
       CHECK(recs.size() == want.size());
@@ -287,8 +287,8 @@ void check_pins(const char* path) {
       for (const auto& t : pins["tuples_" + id]) b.insert(Tuple(t.at(0), t.at(1)));
       CHECK(a == b);
     }
-    std::vector<gs::TsRow> rows;
-    std::vector<gs::TsRec> recs;
+    std::vector<gs::TrsRow> rows;
+    std::vector<gs::TrsRec> recs;
     run_stream(pins["builtin"], &rows, &recs, parts != 0);
     std::vector<Tuple> want;
     for (const auto& t : pins["derived_tuples"]) want.push_back(Tuple(t.at(0), t.at(1)));

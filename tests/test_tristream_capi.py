@@ -103,12 +103,12 @@ def test_tristream_constants_match_the_headers(gs):
         hpp = f.read()
     assert gs.TRISTREAM_TILE == int(re.search(r"constexpr uint32_t TRISTREAM_TILE = (\d+);", hpp).group(1))
     assert gs.TRISTREAM_LANES == int(re.search(r"constexpr uint32_t TRISTREAM_LANES = (\d+);", hpp).group(1))
-    assert "constexpr uint32_t kTsShortRow = 4 * TRISTREAM_LANES;" in hpp and gs.TRISTREAM_SHORT_ROW == 4 * gs.TRISTREAM_LANES
-    assert gs.TRISTREAM_MAX_TOTAL == int(re.search(r"constexpr uint64_t kTsMaxTotal = (0x[0-9A-F]+)ull;", seq).group(1), 16)
-    assert gs.TRISTREAM_MAX_FOLD == 1 << int(re.search(r"constexpr uint64_t kTsMaxFold = 1ull << (\d+);", seq).group(1))
-    assert gs.TRISTREAM_MAX_RECORDS == 1 << int(re.search(r"constexpr uint64_t kTsMaxRecords = 1ull << (\d+);", seq).group(1))
+    assert "constexpr uint32_t kTrsShortRow = 4 * TRISTREAM_LANES;" in hpp and gs.TRISTREAM_SHORT_ROW == 4 * gs.TRISTREAM_LANES
+    assert gs.TRISTREAM_MAX_TOTAL == int(re.search(r"constexpr uint64_t kTrsMaxTotal = (0x[0-9A-F]+)ull;", seq).group(1), 16)
+    assert gs.TRISTREAM_MAX_FOLD == 1 << int(re.search(r"constexpr uint64_t kTrsMaxFold = 1ull << (\d+);", seq).group(1))
+    assert gs.TRISTREAM_MAX_RECORDS == 1 << int(re.search(r"constexpr uint64_t kTrsMaxRecords = 1ull << (\d+);", seq).group(1))
     assert gs.TRISTREAM_MAX_RECORDS <= (1 << 31) - 1
-    assert re.search(r"enum TsRepeats : int \{ kTsCount = 0, kTsIgnore = 1, kTsModes = 2 \};", seq)
+    assert re.search(r"enum TrsRepeats : int \{ kTrsCount = 0, kTrsIgnore = 1, kTrsModes = 2 \};", seq)
     assert gs.TRISTREAM_REPEATS == {"count": 0, "ignore": 1}
     with open(os.path.join(ROOT, "include", "gs_testing.h")) as f:
         assert "(product and maximum: 2^27)" in f.read()

@@ -1,8 +1,8 @@
 """CPU: the triangle streams' rules header (csrc/gs_tristream_seq.hpp: the stamp test, the record
-layout, the segmented combine, the sequential definition ts_fold_seq and the kernels'
-decomposition ts_fold_parts) in a stand-alone program built with the address and
-undefined-behaviour sanitizers (tests/cpp/tristream_seq_sanitize.cpp): ts_fold_seq against a
-literal restatement of the reference's three operators, ts_fold_parts against ts_fold_seq at every
+layout, the segmented combine, the sequential definition trs_fold_seq and the kernels'
+decomposition trs_fold_parts) in a stand-alone program built with the address and
+undefined-behaviour sanitizers (tests/cpp/tristream_seq_sanitize.cpp): trs_fold_seq against a
+literal restatement of the reference's three operators, trs_fold_parts against trs_fold_seq at every
 tile size and every cut, and the pins of tests/golden/tristream_pins.json. The header is the one
 the kernels include."""
 import json
@@ -91,23 +91,23 @@ def test_kernels_and_host_include_the_checked_header():
         text = f.read()
     assert '#include "gs_tristream.hpp"' in text and '#include "gs_scan.hpp"' in text
     assert '#include "gs_triangle_rows.hpp"' in text
-    for fn in ("ts_seg_combine(", "ts_seg_element(", "ts_seg_after(", "ts_seg_identity(", "ts_hit(", "ts_pick_rows(",
-               "ts_arrival_no(", "ts_record_count(", "ts_record_delta(", "ts_tiles(", "tri_merge_pos(", "tri_row(",
+    for fn in ("trs_seg_combine(", "trs_seg_element(", "trs_seg_after(", "trs_seg_identity(", "trs_hit(", "trs_pick_rows(",
+               "trs_arrival_no(", "trs_record_count(", "trs_record_delta(", "trs_tiles(", "tri_merge_pos(", "tri_row(",
                "block_excl_scan<", "block_count_to<", "__ballot(", "__popcll("):
         assert fn in text, fn
     with open(os.path.join(CSRC, "gs_tristream.cpp")) as f:
         host = f.read()
     assert '#include "gs_tristream.hpp"' in host and '#include "gs_vtable.hpp"' in host
-    for fn in ("kTsMaxTotal", "kTsMaxFold", "kTsMaxRecords", "launch_dist_vertices(", "launch_dist_rank(",
+    for fn in ("kTrsMaxTotal", "kTrsMaxFold", "kTrsMaxRecords", "launch_dist_vertices(", "launch_dist_rank(",
                "launch_tri_canon(", "launch_tri_flag_new(", "launch_tile_scan(", "sort_by_pair(", "sort_run(",
                "launch_sort_digits_one(", "grow_group(", "check_handle(", "GS_LAUNCH(", ": StreamOwner, VertexTable"):
         assert fn in host, fn
     # the definition and the decomposition are made of the same rules
     with open(os.path.join(CSRC, "gs_tristream_seq.hpp")) as f:
         seq = f.read()
-    for fn in ("ts_canon(", "ts_stamp_ok(", "ts_arrival_no(", "ts_record_count(", "ts_seg_combine(", "ts_hit("):
+    for fn in ("trs_canon(", "trs_stamp_ok(", "trs_arrival_no(", "trs_record_count(", "trs_seg_combine(", "trs_hit("):
         assert seq.count(fn) >= 2, fn
-    assert "inline void ts_fold_seq(" in seq and "inline uint64_t ts_fold_parts(" in seq
+    assert "inline void trs_fold_seq(" in seq and "inline uint64_t trs_fold_parts(" in seq
     # no second open-addressing insert, no inline assembly
     assert "atomicCAS" not in text and "atomicCAS" not in host and "asm" not in text
     # no workgroup waits on another: no spin, no grid-wide barrier

@@ -1,5 +1,5 @@
 // tristream_seq_bench.cpp -- the sequential baseline of tools/tristream_bench.py: the definition of
-// the triangle streams' fold (csrc/gs_tristream_seq.hpp, ts_fold_seq: ordered maps, one arrival
+// the triangle streams' fold (csrc/gs_tristream_seq.hpp, trs_fold_seq: ordered maps, one arrival
 // after the other) on one core. Reads n arrivals (n int64 sources, then targets) from a binary
 // file, folds them in order in batches of `batch` arrivals, mode `count`, into one state, dropping
 // each batch's rows and records once it is folded, and prints one JSON line with the seconds of
@@ -26,9 +26,9 @@ int main(int argc, char** argv) {
     return 2;
   }
   std::fclose(f);
-  gs::TsState st;
-  std::vector<gs::TsRow> rows;
-  std::vector<gs::TsRec> recs;
+  gs::TrsState st;
+  std::vector<gs::TrsRow> rows;
+  std::vector<gs::TrsRec> recs;
   unsigned long long records = 0;
   double sec = 0;
   for (size_t at = 0; at < n; at += batch) {
@@ -36,7 +36,7 @@ int main(int argc, char** argv) {
     rows.clear();
     recs.clear();
     const auto t0 = std::chrono::steady_clock::now();
-    gs::ts_fold_seq(st, src.data() + at, dst.data() + at, len, gs::kTsCount, &rows, &recs);
+    gs::trs_fold_seq(st, src.data() + at, dst.data() + at, len, gs::kTrsCount, &rows, &recs);
     sec += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     records += recs.size();
   }
