@@ -50,16 +50,13 @@ struct gs_degstream_s : StreamOwner, VertexTable {  // (the vertex table and the
   DevBuf<uint32_t> late_idx, late_val;
   SortScratch sort;
   // device staging of a host fold
-  uint64_t h_cap = 0;
-  DevBuf<int64_t> stage;  // [2][h_cap]
-  DevBuf<uint8_t> stage_del;
+  FoldStage stage;  // (src, dst) and the deletion bytes
   // state exports: tile counts, staging of the host-array form
   uint64_t x_tiles = 0;
   DevBuf<uint32_t> x_blk;
-  uint64_t o_cap = 0;
-  DevBuf<int64_t> o_a, o_b;
-  // host-known totals
-  uint64_t nv = 0, total = 0, max_degree = 0;
+  OutStage out;  // two columns
+  // host-known totals (nv: VertexTable)
+  uint64_t total = 0, max_degree = 0;
   uint64_t last_nv = 0, last_occ = 0, last_rec = 0;
   bool kept = true;  // false after a fold the library cut into pieces
   uint64_t last_tiles = 0, growths = 0;
@@ -73,19 +70,7 @@ namespace {
 constexpr const char* kWhat = "degstream";  // check_handle: "null degstream handle"
 
 // The vertex table grows (VertexTable::grow) and the degrees with it, inside the same wait.
-int grow_vertices(gs_degstream_s* d, uint64_t cap) {
-  DevBuf<uint32_t> deg;
-  const uint64_t ranks = gs::dist_vid_cap(cap);
-  const int rc = d->grow(cap, d->nv, d->dctl, d->stream, [&](bool rebuild) -> int {
-    GS_HIP(deg.alloc(ranks));
-    GS_HIP(hipMemsetAsync(deg, 0, ranks * 4, d->stream));
-    if (rebuild && d->nv) GS_HIP(hipMemcpyAsync(deg, d->degree, d->nv * 4, hipMemcpyDeviceToDevice, d->stream));
-    return GS_OK;
-  });
-  if (rc) return rc;
-  d->degree.swap(deg);
-  return GS_OK;
-}
+int grow_vertices(gs_degstream_s* d, uint64_t cap) { return d->grow_ranked(cap, d->dctl, d->stream, d->degree); }
 
 // count[] holds degrees 0 .. max_degree; the old counts move over
 int grow_counts(gs_degstream_s* d, uint64_t max_degree) {
@@ -132,12 +117,6 @@ int ensure_records(gs_degstream_s* d, uint64_t rows) {
   return GS_OK;
 }
 
-int ensure_staging(gs_degstream_s* d, uint64_t rows) {
-  GS_HIP(grow_group(d->stream, d->o_cap, rows, rows + rows / 4,
-                    [&](uint64_t c) { return alloc_each(c, d->o_a, d->o_b); }));
-  return GS_OK;
-}
-
 void forget_last(gs_degstream_s* d) {
   d->last_nv = d->last_occ = d->last_rec = d->last_tiles = 0;
   d->kept = true;
@@ -151,28 +130,7 @@ int fold_guard(gs_degstream_s* d, const void* src, const void* dst, size_t n) {
   if ((uint64_t)n > gs::kDsMaxTotal || d->total + occs > gs::kDsMaxTotal)
     return fail(GS_ERR_CAPACITY, "degstream fold: " + std::to_string(d->total) + " + " + std::to_string(occs) +
                                      " endpoint occurrences pass 2^31 - 1 since the last reset");
-  const uint64_t piece = std::min<uint64_t>(n, gs::kDsMaxFold);
-  const uint64_t need_v = d->nv + gs::dist_worst_vertices(n);
-  if (need_v > gs::kDistMaxVertices ||
-      (gs::dist_must_grow(d->nv, gs::dist_worst_vertices(piece), d->vcap) &&
-       gs::dist_slots_for(d->nv + gs::dist_worst_vertices(piece)) > gs::kDistMaxSlots))
-    return fail(GS_ERR_CAPACITY, "degstream fold: the fold may pass 2^31 vertex table slots");
-  return GS_OK;
-}
-
-// the stable radix sort of n keys below `bound` (key[i] of row i): the digits above the bits of
-// bound - 1 are equal in all keys and skipped
-int sort_keys(gs_degstream_s* d, const int64_t* key, uint64_t n, uint64_t bound, gs::SortSrc* cur) {
-  uint32_t* const sctl = d->sort.ctl;
-  GS_HIP(hipMemsetAsync(sctl, 0, gs::kSortCtlWords * 4, d->stream));
-  GS_LAUNCH(gs::launch_sort_digits_one(key, n, sctl, d->stream));
-  bool skip[gs::kSortPasses];
-  for (int p = 0; p < (int)gs::kSortPasses; ++p) skip[p] = p > 0 && (bound >> (8 * p)) == 0;
-  *cur = gs::SortSrc();  // (pay null: payload i of row i is i)
-  int side = 0;
-  if (int rc = sort_run(d->sort, key, n, sctl, skip, cur, &side, d->stream)) return rc;
-  if (!cur->key || !cur->pay) return fail(GS_ERR_HIP, "degstream fold: the sort ran no pass");
-  return GS_OK;
+  return d->fold_guard_vertices(n, std::min<uint64_t>(n, gs::kDsMaxFold), kWhat);
 }
 
 // 0 < n <= kDsMaxFold device edges on d->stream
@@ -180,8 +138,7 @@ int fold_piece(gs_degstream_s* d, const int64_t* src, const int64_t* dst, const 
                uint64_t stride) {
   hipStream_t st = d->stream;
   const uint64_t occs = gs::ds_occurrences(n, d->dir);
-  if (gs::dist_must_grow(d->nv, gs::dist_worst_vertices(n), d->vcap))
-    if (int rc = grow_vertices(d, gs::dist_slots_for(d->nv + gs::dist_worst_vertices(n)))) return rc;
+  if (int rc = d->ensure_for(n, [&](uint64_t slots) { return grow_vertices(d, slots); })) return rc;
   if (int rc = ensure_scratch(d, n)) return rc;
   if (int rc = ensure_tiles(d, occs)) return rc;
   if (int rc = sort_scratch_ensure(d->sort, occs, st)) return rc;
@@ -202,8 +159,13 @@ int fold_piece(gs_degstream_s* d, const int64_t* src, const int64_t* dst, const 
   GS_LAUNCH(gs::launch_ds_keys(src, dst, del, n, stride, d->dir, vt, d->vslot, ranks, d->key, d->sgn, d->row_v, d->ctl,
                                st));
   timer.mark(1);
+  // every key is a rank below the bound, every record key a degree below its own: the digits
+  // above a bound's bits are skipped (neither bound is 0, which would skip none: n > 0 gives
+  // dist_worst_vertices(n) > 0, and max_degree + 1 > 0)
   gs::SortSrc cur;
-  if (int rc = sort_keys(d, d->key, occs, d->nv + gs::dist_worst_vertices(n), &cur)) return rc;
+  bool skip[gs::kSortPasses];
+  sort_skip_above(d->nv + gs::dist_worst_vertices(n), skip);
+  if (int rc = sort_by_key(d->sort, d->key, occs, skip, &cur, st, "degstream fold")) return rc;
   timer.mark(2);
   GS_LAUNCH(gs::launch_ds_seg_pass(cur.key, cur.pay, d->sgn, occs, true, d->degree, ranks, d->agg, d->carry,
                                    d->late_idx, d->late_val, d->row_old, d->row_new, d->ctl, d->ctl + gs::DS_MAX, st));
@@ -239,7 +201,8 @@ int fold_piece(gs_degstream_s* d, const int64_t* src, const int64_t* dst, const 
   if (int rc = sort_scratch_ensure(d->sort, recs, st)) return rc;
   GS_LAUNCH(gs::launch_ds_rec_write(d->row_old, d->row_new, d->sgn, occs, d->tbase, d->r_occ, d->r_key, d->r_deg,
                                     d->r_delta, recs, d->ctl, st));
-  if (int rc = sort_keys(d, d->r_key, recs, d->max_degree + 1, &cur)) return rc;
+  sort_skip_above(d->max_degree + 1, skip);
+  if (int rc = sort_by_key(d->sort, d->r_key, recs, skip, &cur, st, "degstream fold")) return rc;
   timer.mark(4);
   GS_LAUNCH(gs::launch_ds_seg_pass(cur.key, cur.pay, d->r_delta, recs, false, d->count, d->count_cap, d->agg, d->carry,
                                    d->late_idx, d->late_val, nullptr, d->r_cnt, d->ctl, nullptr, st));
@@ -257,22 +220,10 @@ int fold_all(gs_degstream_s* d, const int64_t* src, const int64_t* dst, const ui
   uint64_t sum[3] = {0, 0, 0};
   for (uint64_t at = 0; at < n; at += gs::kDsMaxFold) {
     const uint64_t len = std::min<uint64_t>(gs::kDsMaxFold, n - at);
-    const int64_t *ps = src + at * stride, *pd = dst + at * stride;
+    const int64_t* col[2] = {src + at * stride, dst + at * stride};
     const uint8_t* pe = del ? del + at : nullptr;
-    if (host) {
-      GS_HIP(grow_group(d->stream, d->h_cap, len, std::min<uint64_t>(gs::kDsMaxFold, len + len / 4), [&](uint64_t c) {
-        const hipError_t e = d->stage.alloc(2 * c);
-        return e != hipSuccess ? e : d->stage_del.alloc(c);
-      }));
-      int64_t* s0 = d->stage;
-      GS_HIP(hipMemcpyAsync(s0, ps, len * 8, hipMemcpyHostToDevice, d->stream));
-      GS_HIP(hipMemcpyAsync(s0 + d->h_cap, pd, len * 8, hipMemcpyHostToDevice, d->stream));
-      if (pe) GS_HIP(hipMemcpyAsync(d->stage_del, pe, len, hipMemcpyHostToDevice, d->stream));
-      ps = s0;
-      pd = s0 + d->h_cap;
-      pe = pe ? d->stage_del.get() : nullptr;
-    }
-    if (int rc = fold_piece(d, ps, pd, pe, len, host ? 1 : stride)) return rc;
+    if (host) GS_HIP(d->stage.put(d->stream, len, gs::kDsMaxFold, col, &pe));
+    if (int rc = fold_piece(d, col[0], col[1], pe, len, host ? 1 : stride)) return rc;
     sum[0] += d->last_nv;
     sum[1] += d->last_occ;
     sum[2] += d->last_rec;
@@ -301,11 +252,11 @@ int rows_impl(gs_degstream_s* d, int64_t* vertex, uint32_t* old_d, uint32_t* new
   *n = rows;
   if (cap < rows) return truncated(cap, rows);
   if (rows == 0) return GS_OK;
-  const hipMemcpyKind kind = to_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-  if (vertex) GS_HIP(hipMemcpyAsync(vertex, d->row_v, rows * 8, kind, d->stream));
-  if (old_d) GS_HIP(hipMemcpyAsync(old_d, d->row_old, rows * 4, kind, d->stream));
-  if (new_d) GS_HIP(hipMemcpyAsync(new_d, d->row_new, rows * 4, kind, d->stream));
-  if (to_host) GS_HIP(hipStreamSynchronize(d->stream));
+  const ColumnCopy copy(d->stream, to_host);
+  GS_HIP(copy.col(vertex, d->row_v.get(), rows));
+  GS_HIP(copy.col(old_d, d->row_old.get(), rows));
+  GS_HIP(copy.col(new_d, d->row_new.get(), rows));
+  GS_HIP(copy.done());
   return GS_OK;
 }
 
@@ -317,11 +268,11 @@ int records_impl(gs_degstream_s* d, uint32_t* occ, uint32_t* degree, uint32_t* c
   *n = rows;
   if (cap < rows) return truncated(cap, rows);
   if (rows == 0) return GS_OK;
-  const hipMemcpyKind kind = to_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-  if (occ) GS_HIP(hipMemcpyAsync(occ, d->r_occ, rows * 4, kind, d->stream));
-  if (degree) GS_HIP(hipMemcpyAsync(degree, d->r_deg, rows * 4, kind, d->stream));
-  if (count) GS_HIP(hipMemcpyAsync(count, d->r_cnt, rows * 4, kind, d->stream));
-  if (to_host) GS_HIP(hipStreamSynchronize(d->stream));
+  const ColumnCopy copy(d->stream, to_host);
+  GS_HIP(copy.col(occ, d->r_occ.get(), rows));
+  GS_HIP(copy.col(degree, d->r_deg.get(), rows));
+  GS_HIP(copy.col(count, d->r_cnt.get(), rows));
+  GS_HIP(copy.done());
   return GS_OK;
 }
 
@@ -342,18 +293,10 @@ int live_impl(gs_degstream_s* d, const uint32_t* state, uint64_t entries, const 
   *n = rows;
   if (cap < rows) return truncated(cap, rows);
   if (rows == 0) return GS_OK;
-  int64_t *da = id_out, *db = value_out;
-  if (to_host) {
-    if (int rc = ensure_staging(d, rows)) return rc;
-    da = id_out ? d->o_a.get() : nullptr;
-    db = value_out ? d->o_b.get() : nullptr;
-  }
-  GS_LAUNCH(gs::launch_ds_live_write(state, entries, d->x_blk, ids, da, db, rows, st));
-  if (to_host) {
-    if (id_out) GS_HIP(hipMemcpyAsync(id_out, da, rows * 8, hipMemcpyDeviceToHost, st));
-    if (value_out) GS_HIP(hipMemcpyAsync(value_out, db, rows * 8, hipMemcpyDeviceToHost, st));
-    GS_HIP(hipStreamSynchronize(st));
-  }
+  if (to_host) GS_HIP(d->out.ensure(2, rows, st));
+  GS_LAUNCH(gs::launch_ds_live_write(state, entries, d->x_blk, ids, d->out.dev(0, id_out, to_host),
+                                     d->out.dev(1, value_out, to_host), rows, st));
+  if (to_host) GS_HIP(d->out.finish(st, rows, id_out, value_out));
   return GS_OK;
 }
 

@@ -33,21 +33,16 @@ struct gs_distinct_s : StreamOwner, VertexTable {  // (the vertex table and the 
   DevBuf<uint32_t> newv_entry;  // [2 n] entries of the new vertices
   DevBuf<uint32_t> newe_index;  // [n] indices of the kept edges
   // device staging of a host fold
-  uint64_t h_cap = 0;
-  DevBuf<int64_t> hsrc;
-  DevBuf<int64_t> hdst;
-  // host-known totals
-  uint64_t nv = 0, ne = 0, folded = 0;
+  FoldStage stage;  // (src, dst)
+  // host-known totals (nv: VertexTable)
+  uint64_t ne = 0, folded = 0;
   uint64_t last_n = 0, last_nv = 0, last_ne = 0;
   // edge export: compacted (stamp, key) rows, the sort's scratch, staging of the host-array forms
   SortScratch sort;
   uint64_t x_cap = 0;
   DevBuf<int64_t> x_stamp;
   DevBuf<unsigned long long> x_key;
-  uint64_t o_cap = 0;
-  DevBuf<int64_t> o_a;
-  DevBuf<int64_t> o_b;
-  DevBuf<unsigned long long> o_c;
+  OutStage out;  // three columns
   // diagnostics (gs_testing_distinct_stats)
   uint64_t v_rebuilds = 0, e_rebuilds = 0, last_probe = 0, last_tiles = 0;
   uint64_t phase_us[5] = {0, 0, 0, 0, 0};  // of the last profiled fold (gs_testing_distinct_phases)
@@ -70,7 +65,7 @@ constexpr const char* kWhat = "distinct";  // check_handle: "null distinct handl
 
 int grow_vertices(gs_distinct_s* d, uint64_t cap) {
   const bool rebuild = d->vtab;
-  if (int rc = d->grow(cap, d->nv, d->ctl, d->stream, [](bool) { return GS_OK; })) return rc;
+  if (int rc = d->grow(cap, d->ctl, d->stream, [](bool) { return GS_OK; })) return rc;
   if (rebuild) ++d->v_rebuilds;
   return GS_OK;
 }
@@ -103,12 +98,6 @@ int ensure_scratch(gs_distinct_s* d, uint64_t n) {
   return GS_OK;
 }
 
-int ensure_staging(gs_distinct_s* d, uint64_t rows) {
-  GS_HIP(grow_group(d->stream, d->o_cap, rows, rows + rows / 4,
-                    [&](uint64_t c) { return alloc_each(c, d->o_a, d->o_b, d->o_c); }));
-  return GS_OK;
-}
-
 void forget_last(gs_distinct_s* d) {
   d->last_n = d->last_nv = d->last_ne = d->last_probe = d->last_tiles = d->last_atomics = 0;
   for (uint64_t& us : d->phase_us) us = 0;
@@ -134,8 +123,7 @@ int fold_impl(gs_distinct_s* d, const int64_t* src, const int64_t* dst, uint64_t
   forget_last(d);
   static_assert(gs::DIST_PROBE == 3 && gs::DIST_ATOMICS == 5, "the fold's words are among the first six");
   GS_HIP(hipMemsetAsync(d->ctl, 0, 6 * 8, d->stream));
-  if (gs::dist_must_grow(d->nv, gs::dist_worst_vertices(n), d->vcap))
-    if (int rc = grow_vertices(d, gs::dist_slots_for(d->nv + gs::dist_worst_vertices(n)))) return rc;
+  if (int rc = d->ensure_for(n, [&](uint64_t slots) { return grow_vertices(d, slots); })) return rc;
   if (gs::dist_must_grow(d->ne, gs::dist_worst_edges(n), d->ecap))
     if (int rc = grow_edges(d, gs::dist_slots_for(d->ne + gs::dist_worst_edges(n)))) return rc;
   if (int rc = ensure_scratch(d, n)) return rc;
@@ -177,23 +165,13 @@ int new_edges_impl(gs_distinct_s* d, uint32_t* index, int64_t* src, int64_t* dst
   *n = ne;
   if (cap < ne) return truncated(cap, ne);
   if (ne == 0) return GS_OK;
-  const hipMemcpyKind kind = to_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-  int64_t *ds = src, *dd = dst;
-  if (to_host && (src || dst)) {
-    if (int rc = ensure_staging(d, ne)) return rc;
-    ds = src ? d->o_a.get() : nullptr;
-    dd = dst ? d->o_b.get() : nullptr;
+  if (to_host && (src || dst)) GS_HIP(d->out.ensure(3, ne, d->stream));
+  if (src || dst) {
+    GS_LAUNCH(gs::launch_dist_new_edges(d->newe_index, ne, d->eslot, d->last_n, d->etable(), d->vid, d->nv,
+                                        d->out.dev(0, src, to_host), d->out.dev(1, dst, to_host), d->stream));
   }
-  if (ds || dd) {
-    GS_LAUNCH(gs::launch_dist_new_edges(d->newe_index, ne, d->eslot, d->last_n, d->etable(), d->vid, d->nv, ds, dd,
-                                        d->stream));
-  }
-  if (index) GS_HIP(hipMemcpyAsync(index, d->newe_index, ne * 4, kind, d->stream));
-  if (to_host) {
-    if (src) GS_HIP(hipMemcpyAsync(src, ds, ne * 8, hipMemcpyDeviceToHost, d->stream));
-    if (dst) GS_HIP(hipMemcpyAsync(dst, dd, ne * 8, hipMemcpyDeviceToHost, d->stream));
-    GS_HIP(hipStreamSynchronize(d->stream));
-  }
+  GS_HIP(ColumnCopy(d->stream, to_host).col(index, d->newe_index.get(), ne));
+  if (to_host) GS_HIP(d->out.finish(d->stream, ne, src, dst));
   return GS_OK;
 }
 
@@ -205,11 +183,10 @@ int new_vertices_impl(gs_distinct_s* d, int64_t* v, uint32_t* entry, size_t cap,
   *n = k;
   if (cap < k) return truncated(cap, k);
   if (k == 0) return GS_OK;
-  const hipMemcpyKind kind = to_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-  // the new vertices are the tail of the vertex list
-  if (v) GS_HIP(hipMemcpyAsync(v, d->vid + (d->nv - k), k * 8, kind, d->stream));
-  if (entry) GS_HIP(hipMemcpyAsync(entry, d->newv_entry, k * 4, kind, d->stream));
-  if (to_host) GS_HIP(hipStreamSynchronize(d->stream));
+  const ColumnCopy copy(d->stream, to_host);
+  GS_HIP(copy.col(v, d->vid + (d->nv - k), k));  // the new vertices are the tail of the vertex list
+  GS_HIP(copy.col(entry, d->newv_entry.get(), k));
+  GS_HIP(copy.done());
   return GS_OK;
 }
 
@@ -221,8 +198,9 @@ int vertices_impl(gs_distinct_s* d, int64_t* v, size_t cap, size_t* n, bool to_h
   if (cap < d->nv) return truncated(cap, d->nv);
   if (d->nv == 0) return GS_OK;
   if (!v) return fail(GS_ERR_INVALID, "null arrays");
-  GS_HIP(hipMemcpyAsync(v, d->vid, d->nv * 8, to_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, d->stream));
-  if (to_host) GS_HIP(hipStreamSynchronize(d->stream));
+  const ColumnCopy copy(d->stream, to_host);
+  GS_HIP(copy.col(v, d->vid.get(), d->nv));
+  GS_HIP(copy.done());
   return GS_OK;
 }
 
@@ -237,35 +215,19 @@ int edges_impl(gs_distinct_s* d, int64_t* src, int64_t* dst, uint64_t* first, si
   GS_HIP(grow_group(d->stream, d->x_cap, ne, ne + ne / 4,
                     [&](uint64_t c) { return alloc_each(c, d->x_stamp, d->x_key); }));
   if (int rc = sort_scratch_ensure(d->sort, ne, d->stream)) return rc;
-  int64_t *ds = src, *dd = dst;
-  unsigned long long* df = reinterpret_cast<unsigned long long*>(first);
-  if (to_host) {
-    if (int rc = ensure_staging(d, ne)) return rc;
-    ds = src ? d->o_a.get() : nullptr;
-    dd = dst ? d->o_b.get() : nullptr;
-    df = first ? d->o_c.get() : nullptr;
-  }
+  if (to_host) GS_HIP(d->out.ensure(3, ne, d->stream));
   // scan the table, compact, sort by stamp, decode through the vertex list
   GS_HIP(hipMemsetAsync(d->ctl + gs::DIST_EXPORT, 0, 8, d->stream));
   GS_LAUNCH(gs::launch_dist_export(d->etable(), d->x_stamp, d->x_key, ne, d->ctl, d->stream));
-  uint32_t* const sctl = d->sort.ctl;
-  GS_HIP(hipMemsetAsync(sctl, 0, gs::kSortCtlWords * 4, d->stream));
-  // rows 0..7: the digit histograms of one key column
-  GS_LAUNCH(gs::launch_sort_digits_one(d->x_stamp, ne, sctl, d->stream));
-  // every stamp is below 2 * folded: the digits above its bits are equal in all keys
+  // every stamp is below 2 * folded (not 0: there are edges): the digits above its bits are equal in all keys
   bool skip[gs::kSortPasses];
-  for (int p = 0; p < (int)gs::kSortPasses; ++p) skip[p] = p > 0 && 8 * p < 64 && ((2 * d->folded) >> (8 * p)) == 0;
-  gs::SortSrc cur;  // (pay null: payload i of row i is i)
-  int side = 0;
-  if (int rc = sort_run(d->sort, d->x_stamp, ne, sctl, skip, &cur, &side, d->stream)) return rc;
-  if (!cur.key || !cur.pay) return fail(GS_ERR_HIP, "distinct edges: the sort ran no pass");
-  GS_LAUNCH(gs::launch_dist_decode(cur.key, cur.pay, d->x_key, ne, d->vid, d->nv, ds, dd, df, d->stream));
-  if (to_host) {
-    if (src) GS_HIP(hipMemcpyAsync(src, ds, ne * 8, hipMemcpyDeviceToHost, d->stream));
-    if (dst) GS_HIP(hipMemcpyAsync(dst, dd, ne * 8, hipMemcpyDeviceToHost, d->stream));
-    if (first) GS_HIP(hipMemcpyAsync(first, df, ne * 8, hipMemcpyDeviceToHost, d->stream));
-    GS_HIP(hipStreamSynchronize(d->stream));
-  }
+  sort_skip_above(2 * d->folded, skip);
+  gs::SortSrc cur;
+  if (int rc = sort_by_key(d->sort, d->x_stamp, ne, skip, &cur, d->stream, "distinct edges")) return rc;
+  GS_LAUNCH(gs::launch_dist_decode(cur.key, cur.pay, d->x_key, ne, d->vid, d->nv, d->out.dev(0, src, to_host),
+                                   d->out.dev(1, dst, to_host),
+                                   d->out.dev(2, reinterpret_cast<unsigned long long*>(first), to_host), d->stream));
+  if (to_host) GS_HIP(d->out.finish(d->stream, ne, src, dst, first));
   return GS_OK;
 }
 
@@ -320,11 +282,10 @@ int gs_distinct_fold(gs_distinct d, const int64_t* src, const int64_t* dst, size
     return GS_OK;
   }
   DeviceGuard g(d->device);
-  GS_HIP(grow_group(d->stream, d->h_cap, n, n + n / 4, [&](uint64_t c) { return alloc_each(c, d->hsrc, d->hdst); }));
-  GS_HIP(hipMemcpyAsync(d->hsrc, src, n * 8, hipMemcpyHostToDevice, d->stream));
-  GS_HIP(hipMemcpyAsync(d->hdst, dst, n * 8, hipMemcpyHostToDevice, d->stream));
+  const int64_t* col[2] = {src, dst};
+  GS_HIP(d->stage.put(d->stream, n, UINT64_MAX, col));  // (one piece: fold_guard bounds n, nothing clamps the growth)
   // (fold_impl waits for the stream before it returns: the host arrays are free then)
-  return fold_impl(d, d->hsrc, d->hdst, n, 1);
+  return fold_impl(d, col[0], col[1], n, 1);
 }
 
 int gs_distinct_size(gs_distinct d, uint64_t* vertices, uint64_t* edges, uint64_t* folded, uint64_t* new_vertices,

@@ -8,7 +8,11 @@
 // points all of them have (sync, get_stream, wait_stream, the null check, the truncation error).
 // Every device array a handle owns is a DevBuf (gs_devbuf.hpp), every event, stream and pinned
 // host block an Event, Stream or HostBuf (gs_own.hpp): deleting the handle releases them. Groups
-// of DevBufs that share a capacity grow through grow_group (gs_grow.hpp). All of it is linked into
+// of DevBufs that share a capacity grow through grow_group (gs_grow.hpp); the host-array form of an
+// export and the staging of a host fold go through gs_hostio.hpp (ColumnCopy, OutStage,
+// FoldStage); a one-column sort is sort_by_key, a two-column one sort_by_pair (gs_sort.hpp); the
+// vertex table of the streams that rank their vertices, its fold guard and its growth are
+// VertexTable (gs_vtable.hpp). All of it is linked into
 // one library, so every summary owns one prefix for its names in namespace gs, in its lower,
 // camel and upper case spellings (ts_, kTs, Ts, TS_): degree, tri, slice, dist, sp, mt, ts (the
 // sampling triangle estimate), ds (the degree streams), trs (the triangle streams); a new summary
@@ -21,6 +25,7 @@
 
 #include "gs_devbuf.hpp"
 #include "gs_grow.hpp"
+#include "gs_hostio.hpp"
 #include "gs_ingest.hpp"
 #include "gs_kernels.hpp"
 #include "gs_own.hpp"

@@ -37,8 +37,7 @@ struct gs_matching_s : StreamOwner, VertexTable {  // (the vertex table and the 
   DevBuf<gs::MtRec> rec;
   DevBuf<uint32_t> list[2];
   // device staging of a host fold
-  uint64_t h_cap = 0;
-  DevBuf<int64_t> stage;  // [3][h_cap]
+  FoldStage stage;  // (src, dst, val)
   // the last fold's events
   uint64_t ev_cap = 0, ev_rows = 0;
   bool ev_kept = true;  // false after a fold the library cut into pieces
@@ -50,14 +49,12 @@ struct gs_matching_s : StreamOwner, VertexTable {  // (the vertex table and the 
   uint64_t x_cap = 0;
   DevBuf<int64_t> x_stamp;
   DevBuf<uint32_t> x_rank;
-  uint64_t o_cap = 0;
-  DevBuf<int64_t> o_a, o_b, o_c;
-  DevBuf<unsigned long long> o_d;
+  OutStage out;  // four columns
   // mate probe
   uint64_t q_cap = 0;
   DevBuf<int64_t> q_rank;
-  // host-known totals
-  uint64_t nv = 0, folded = 0, edges = 0;
+  // host-known totals (nv: VertexTable)
+  uint64_t folded = 0, edges = 0;
   int64_t weight = 0;
   bool safe = true;
   // gs_testing_matching_tune (< 0: product) and gs_testing_matching_stats
@@ -73,7 +70,7 @@ constexpr const char* kWhat = "matching";  // check_handle: "null matching handl
 int grow_vertices(gs_matching_s* m, uint64_t cap) {
   DevBuf<gs::MtVertex> st;
   const uint64_t ranks = gs::dist_vid_cap(cap);
-  const int rc = m->grow(cap, m->nv, m->dctl, m->stream, [&](bool rebuild) -> int {
+  const int rc = m->grow(cap, m->dctl, m->stream, [&](bool rebuild) -> int {
     GS_HIP(st.alloc(ranks));
     GS_LAUNCH(gs::launch_mt_init(st, rebuild ? m->nv : 0, ranks, m->stream));
     if (rebuild && m->nv)
@@ -106,21 +103,9 @@ int ensure_events(gs_matching_s* m, uint64_t rows) {
   return GS_OK;
 }
 
-int ensure_staging(gs_matching_s* m, uint64_t rows) {
-  GS_HIP(grow_group(m->stream, m->o_cap, rows, rows + rows / 4,
-                    [&](uint64_t c) { return alloc_each(c, m->o_a, m->o_b, m->o_c, m->o_d); }));
-  return GS_OK;
-}
-
 int fold_guard(gs_matching_s* m, const void* src, const void* dst, const void* val, size_t n) {
   if (n && (!src || !dst || !val)) return fail(GS_ERR_INVALID, "null edge arrays");
-  const uint64_t piece = std::min<uint64_t>(n, gs::kMtMaxFold);
-  const uint64_t need_v = m->nv + gs::dist_worst_vertices(n);
-  if (need_v > gs::kDistMaxVertices ||
-      (gs::dist_must_grow(m->nv, gs::dist_worst_vertices(piece), m->vcap) &&
-       gs::dist_slots_for(m->nv + gs::dist_worst_vertices(piece)) > gs::kDistMaxSlots))
-    return fail(GS_ERR_CAPACITY, "matching fold: the fold may pass 2^31 vertex table slots");
-  return GS_OK;
+  return m->fold_guard_vertices(n, std::min<uint64_t>(n, gs::kMtMaxFold), kWhat);
 }
 
 // 0 < n <= kMtMaxFold device arrivals on m->stream; on return m->acc[i] is the accepted byte of
@@ -128,8 +113,7 @@ int fold_guard(gs_matching_s* m, const void* src, const void* dst, const void* v
 int fold_piece(gs_matching_s* m, const int64_t* src, const int64_t* dst, const int64_t* val, uint64_t n,
                uint64_t stride) {
   hipStream_t st = m->stream;
-  if (gs::dist_must_grow(m->nv, gs::dist_worst_vertices(n), m->vcap))
-    if (int rc = grow_vertices(m, gs::dist_slots_for(m->nv + gs::dist_worst_vertices(n)))) return rc;
+  if (int rc = m->ensure_for(n, [&](uint64_t slots) { return grow_vertices(m, slots); })) return rc;
   if (int rc = ensure_scratch(m, n)) return rc;
   const gs::DistVTable vt = m->vtable();
   const uint64_t ranks = gs::dist_vid_cap(m->vcap);
@@ -222,19 +206,9 @@ int fold_all(gs_matching_s* m, const int64_t* src, const int64_t* dst, const int
   uint64_t sum[5] = {0, 0, 0, 0, 0};
   for (uint64_t at = 0; at < n; at += gs::kMtMaxFold) {
     const uint64_t len = std::min<uint64_t>(gs::kMtMaxFold, n - at);
-    const int64_t *ps = src + at * stride, *pd = dst + at * stride, *pv = val + at * stride;
-    if (host) {
-      GS_HIP(grow_group(m->stream, m->h_cap, len, std::min<uint64_t>(gs::kMtMaxFold, len + len / 4),
-                        [&](uint64_t c) { return m->stage.alloc(3 * c); }));
-      int64_t* s0 = m->stage;
-      GS_HIP(hipMemcpyAsync(s0, ps, len * 8, hipMemcpyHostToDevice, m->stream));
-      GS_HIP(hipMemcpyAsync(s0 + m->h_cap, pd, len * 8, hipMemcpyHostToDevice, m->stream));
-      GS_HIP(hipMemcpyAsync(s0 + 2 * m->h_cap, pv, len * 8, hipMemcpyHostToDevice, m->stream));
-      ps = s0;
-      pd = s0 + m->h_cap;
-      pv = s0 + 2 * m->h_cap;
-    }
-    if (int rc = fold_piece(m, ps, pd, pv, len, host ? 1 : stride)) return rc;
+    const int64_t* col[3] = {src + at * stride, dst + at * stride, val + at * stride};
+    if (host) GS_HIP(m->stage.put(m->stream, len, gs::kMtMaxFold, col));
+    if (int rc = fold_piece(m, col[0], col[1], col[2], len, host ? 1 : stride)) return rc;
     if (accepted)
       GS_HIP(hipMemcpyAsync(accepted + at, m->acc, len, host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
                             m->stream));
@@ -259,13 +233,13 @@ int events_impl(gs_matching_s* m, uint32_t* arrival, uint8_t* type, int64_t* src
   *n = rows;
   if (cap < rows) return truncated(cap, rows);
   if (rows == 0) return GS_OK;
-  const hipMemcpyKind kind = to_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-  if (arrival) GS_HIP(hipMemcpyAsync(arrival, m->ev_arrival, rows * 4, kind, m->stream));
-  if (type) GS_HIP(hipMemcpyAsync(type, m->ev_type, rows, kind, m->stream));
-  if (src) GS_HIP(hipMemcpyAsync(src, m->ev_src, rows * 8, kind, m->stream));
-  if (dst) GS_HIP(hipMemcpyAsync(dst, m->ev_dst, rows * 8, kind, m->stream));
-  if (val) GS_HIP(hipMemcpyAsync(val, m->ev_val, rows * 8, kind, m->stream));
-  if (to_host) GS_HIP(hipStreamSynchronize(m->stream));
+  const ColumnCopy copy(m->stream, to_host);
+  GS_HIP(copy.col(arrival, m->ev_arrival.get(), rows));
+  GS_HIP(copy.col(type, m->ev_type.get(), rows));
+  GS_HIP(copy.col(src, m->ev_src.get(), rows));
+  GS_HIP(copy.col(dst, m->ev_dst.get(), rows));
+  GS_HIP(copy.col(val, m->ev_val.get(), rows));
+  GS_HIP(copy.done());
   return GS_OK;
 }
 
@@ -282,35 +256,18 @@ int export_impl(gs_matching_s* m, int64_t* src, int64_t* dst, int64_t* val, uint
   GS_HIP(grow_group(m->stream, m->x_cap, ne, ne + ne / 4,
                     [&](uint64_t c) { return alloc_each(c, m->x_stamp, m->x_rank); }));
   if (int rc = sort_scratch_ensure(m->sort, ne, m->stream)) return rc;
-  int64_t *ds = src, *dd = dst, *dv = val;
-  unsigned long long* df = reinterpret_cast<unsigned long long*>(first);
-  if (to_host) {
-    if (int rc = ensure_staging(m, ne)) return rc;
-    ds = src ? m->o_a.get() : nullptr;
-    dd = dst ? m->o_b.get() : nullptr;
-    dv = val ? m->o_c.get() : nullptr;
-    df = first ? m->o_d.get() : nullptr;
-  }
+  if (to_host) GS_HIP(m->out.ensure(4, ne, m->stream));
   GS_HIP(hipMemsetAsync(m->ctl + gs::MT_EXPORT, 0, 8, m->stream));
   GS_LAUNCH(gs::launch_mt_export(m->st, m->nv, m->x_stamp, m->x_rank, ne, m->ctl, m->stream));
-  uint32_t* const sctl = m->sort.ctl;
-  GS_HIP(hipMemsetAsync(sctl, 0, gs::kSortCtlWords * 4, m->stream));
-  GS_LAUNCH(gs::launch_sort_digits_one(m->x_stamp, ne, sctl, m->stream));
-  // every stamp is below folded: the digits above its bits are equal in all keys
+  // every stamp is below folded (not 0: M has edges): the digits above its bits are equal in all keys
   bool skip[gs::kSortPasses];
-  for (int p = 0; p < (int)gs::kSortPasses; ++p) skip[p] = p > 0 && (m->folded >> (8 * p)) == 0;
-  gs::SortSrc cur;  // (pay null: payload i of row i is i)
-  int side = 0;
-  if (int rc = sort_run(m->sort, m->x_stamp, ne, sctl, skip, &cur, &side, m->stream)) return rc;
-  if (!cur.key || !cur.pay) return fail(GS_ERR_HIP, "matching export: the sort ran no pass");
-  GS_LAUNCH(gs::launch_mt_decode(cur.key, cur.pay, m->x_rank, ne, m->st, m->vid, m->nv, ds, dd, dv, df, m->stream));
-  if (to_host) {
-    if (src) GS_HIP(hipMemcpyAsync(src, ds, ne * 8, hipMemcpyDeviceToHost, m->stream));
-    if (dst) GS_HIP(hipMemcpyAsync(dst, dd, ne * 8, hipMemcpyDeviceToHost, m->stream));
-    if (val) GS_HIP(hipMemcpyAsync(val, dv, ne * 8, hipMemcpyDeviceToHost, m->stream));
-    if (first) GS_HIP(hipMemcpyAsync(first, df, ne * 8, hipMemcpyDeviceToHost, m->stream));
-    GS_HIP(hipStreamSynchronize(m->stream));
-  }
+  sort_skip_above(m->folded, skip);
+  gs::SortSrc cur;
+  if (int rc = sort_by_key(m->sort, m->x_stamp, ne, skip, &cur, m->stream, "matching export")) return rc;
+  GS_LAUNCH(gs::launch_mt_decode(cur.key, cur.pay, m->x_rank, ne, m->st, m->vid, m->nv, m->out.dev(0, src, to_host),
+                                 m->out.dev(1, dst, to_host), m->out.dev(2, val, to_host),
+                                 m->out.dev(3, reinterpret_cast<unsigned long long*>(first), to_host), m->stream));
+  if (to_host) GS_HIP(m->out.finish(m->stream, ne, src, dst, val, first));
   return GS_OK;
 }
 

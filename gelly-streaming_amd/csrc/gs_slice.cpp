@@ -43,9 +43,7 @@ struct gs_slices_s : StreamOwner {
   const unsigned long long* skey = nullptr;  // the sorted pairs (in the sort's scratch)
   const uint32_t* spay = nullptr;
   // device staging of the host-array forms
-  uint64_t o_cap = 0;
-  DevBuf<int64_t> o_a;
-  DevBuf<int64_t> o_b;
+  OutStage out;  // two columns
   // diagnostics (gs_testing_slice_stats)
   uint64_t reduce_tiles = 0;
   uint64_t phase_us[5] = {0, 0, 0, 0, 0};  // expand, sort, heads, reduce, gather of the last profiled calls
@@ -74,12 +72,6 @@ int ensure_window(gs_slices_s* s, uint64_t n, uint64_t entries) {
   GS_HIP(grow_group(s->stream, s->e_cap, entries, std::min<uint64_t>(kSliceMaxEntries, entries + entries / 4),
                     alloc_entries));
   return sort_scratch_ensure(s->sort, entries, s->stream);
-}
-
-int ensure_staging(gs_slices_s* s, uint64_t rows) {
-  GS_HIP(grow_group(s->stream, s->o_cap, rows, rows + rows / 4,
-                    [&](uint64_t c) { return alloc_each(c, s->o_a, s->o_b); }));
-  return GS_OK;
 }
 
 // a call's timer over `phases` words of s->phase_us from word `first` on
@@ -114,13 +106,8 @@ int window_impl(gs_slices_s* s, const int64_t* src, const int64_t* dst, const in
   timer.mark(PH_EXPAND);
   GS_LAUNCH(gs::launch_slice_expand(src, dst, val, n, stride, dir, s->esrc, s->edst, s->eval, s->kid, s->stream));
   timer.mark(PH_SORT);
-  uint32_t* const sctl = s->sort.ctl;
-  GS_HIP(hipMemsetAsync(sctl, 0, gs::kSortCtlWords * 4, s->stream));
-  GS_LAUNCH(gs::launch_sort_digits_one(s->kid, entries, sctl, s->stream));  // rows 0..7: the keys
-  gs::SortSrc cur;  // (pay null: payload i of entry i is i)
-  int side = 0;
-  if (int rc = sort_run(s->sort, s->kid, entries, sctl, nullptr, &cur, &side, s->stream)) return rc;
-  if (!cur.key || !cur.pay) return fail(GS_ERR_HIP, "slice window: the sort ran no pass");
+  gs::SortSrc cur;
+  if (int rc = sort_by_key(s->sort, s->kid, entries, nullptr, &cur, s->stream, "slice window")) return rc;
   timer.mark(PH_HEADS);
   GS_LAUNCH(gs::launch_slice_heads(cur.key, entries, s->flags, s->tbase, s->ctl, s->vtx, s->off, s->e_cap, s->stream));
   // the window's one host synchronisation: the vertex count
@@ -150,11 +137,8 @@ int reduce_impl(gs_slices_s* s, int op, int64_t* v, int64_t* out, size_t cap, si
   if (cap < s->nv) return truncated(cap, s->nv);
   if (s->nv == 0) return GS_OK;
   if (!v || !out) return fail(GS_ERR_INVALID, "null arrays");
-  int64_t* dout = out;
-  if (to_host) {
-    if (int rc = ensure_staging(s, s->nv)) return rc;
-    dout = s->o_a;
-  }
+  if (to_host) GS_HIP(s->out.ensure(2, s->nv, s->stream));
+  int64_t* const dout = s->out.dev(0, out, to_host);
   PhaseTimer timer = phase_timer(s, PH_REDUCE, 1);
   timer.mark(0);
   if (op == GS_SLICE_COUNT) {
@@ -166,11 +150,8 @@ int reduce_impl(gs_slices_s* s, int op, int64_t* v, int64_t* out, size_t cap, si
   }
   timer.mark(1);
   timer.finish();
-  GS_HIP(hipMemcpyAsync(v, s->vtx, s->nv * 8, to_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, s->stream));
-  if (to_host) {
-    GS_HIP(hipMemcpyAsync(out, dout, s->nv * 8, hipMemcpyDeviceToHost, s->stream));
-    GS_HIP(hipStreamSynchronize(s->stream));
-  }
+  GS_HIP(ColumnCopy(s->stream, to_host).col(v, s->vtx.get(), s->nv));
+  if (to_host) GS_HIP(s->out.finish(s->stream, s->nv, out));
   return GS_OK;
 }
 
@@ -192,26 +173,18 @@ int neighborhoods_impl(gs_slices_s* s, int64_t* v, uint64_t* offset, int64_t* ne
     return GS_OK;
   }
   if (!v || !neighbor) return fail(GS_ERR_INVALID, "null arrays");
-  int64_t *dn = neighbor, *dv = val;
-  if (to_host) {
-    if (int rc = ensure_staging(s, s->entries)) return rc;
-    dn = s->o_a;
-    dv = val ? s->o_b.get() : nullptr;
-  }
+  if (to_host) GS_HIP(s->out.ensure(2, s->entries, s->stream));
+  int64_t *const dn = s->out.dev(0, neighbor, to_host), *const dv = s->out.dev(1, val, to_host);
   PhaseTimer timer = phase_timer(s, PH_GATHER, 1);
   timer.mark(0);
   GS_LAUNCH(gs::launch_slice_gather(s->spay, s->entries, s->n, s->dir, s->esrc, s->edst, s->eval, dn, dv, s->entries,
                                     s->stream));
   timer.mark(1);
   timer.finish();
-  const hipMemcpyKind kind = to_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-  GS_HIP(hipMemcpyAsync(v, s->vtx, s->nv * 8, kind, s->stream));
-  GS_HIP(hipMemcpyAsync(offset, s->off, (s->nv + 1) * 8, kind, s->stream));
-  if (to_host) {
-    GS_HIP(hipMemcpyAsync(neighbor, dn, s->entries * 8, hipMemcpyDeviceToHost, s->stream));
-    if (val) GS_HIP(hipMemcpyAsync(val, dv, s->entries * 8, hipMemcpyDeviceToHost, s->stream));
-    GS_HIP(hipStreamSynchronize(s->stream));
-  }
+  const ColumnCopy copy(s->stream, to_host);
+  GS_HIP(copy.col(v, s->vtx.get(), s->nv));
+  GS_HIP(copy.col(reinterpret_cast<unsigned long long*>(offset), s->off.get(), s->nv + 1));
+  if (to_host) GS_HIP(s->out.finish(s->stream, s->entries, neighbor, val));
   return GS_OK;
 }
 

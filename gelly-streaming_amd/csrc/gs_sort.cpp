@@ -1,7 +1,9 @@
 // gs_sort.cpp -- the host side of the radix sort (gs_sort.hpp, kernels in gs_sort_k.hip): the
-// owner of its scratch and the one loop that queues its passes, shared by the component export
-// (gs_capi.cpp), the degree exports (gs_degree.cpp), the triangle and spanner folds and the other
-// stand-alone summaries.
+// owner of its scratch, the one loop that queues its passes (sort_run: the component export of
+// gs_capi.cpp, the degree exports of gs_degree.cpp and step 3 of the triangle fold call it
+// themselves) and the two whole sorts built on it: sort_by_pair (the triangle, spanner and
+// triangle streams' folds) and sort_by_key (the window slices, the distinct and matching exports,
+// the sampling triangle estimate, the degree and triangle streams' folds).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -60,6 +62,17 @@ int sort_by_pair(SortScratch& s, const int64_t* x, const int64_t* y, uint64_t n,
   int side = 0;
   if (int rc = sort_run(s, y, n, s.hist(1), nullptr, cur, &side, st)) return rc;
   return sort_run(s, x, n, s.hist(0), nullptr, cur, &side, st);
+}
+
+int sort_by_key(SortScratch& s, const int64_t* key, uint64_t n, const bool* skip, gs::SortSrc* cur, hipStream_t st,
+                const char* what) {
+  GS_HIP(hipMemsetAsync(s.ctl, 0, gs::kSortCtlWords * 4, st));
+  GS_LAUNCH(gs::launch_sort_digits_one(key, n, s.ctl, st));
+  *cur = gs::SortSrc();  // (pay null: payload i of key i is i)
+  int side = 0;
+  if (int rc = sort_run(s, key, n, s.hist(0), skip, cur, &side, st)) return rc;
+  if (!cur->key || !cur->pay) return fail(GS_ERR_HIP, std::string(what) + ": the sort ran no pass");
+  return GS_OK;
 }
 
 }  // namespace gsi

@@ -6,8 +6,11 @@
 // flag / scan / compact idiom is gs_scan.hpp). Every launch is queued on the given stream; kernel boundaries
 // carry all ordering between workgroups (no workgroup waits on another inside a launch).
 // The host part at the end (gs_sort.cpp) owns the sort's scratch and drives its passes for
-// every caller: the component export, the degree exports, the triangle and spanner folds, the
-// window slices, the distinct and matching exports and the degree and triangle streams' folds.
+// every caller: the component export, the degree exports and step 3 of the triangle fold drive
+// sort_run themselves (they read the histograms back for sort_skip_digits); the triangle, spanner
+// and triangle streams' folds sort pairs through sort_by_pair; the window slices, the distinct and
+// matching exports, the sampling triangle estimate and the degree and triangle streams' folds
+// sort one column through sort_by_key.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -98,6 +101,12 @@ int sort_scratch_ensure(SortScratch& s, uint64_t rows, hipStream_t st);
 // skip[p] = every one of the n keys agrees on digit p (its 256-bin row of `hist`, a host copy
 // of eight rows, has one bin holding n): the pass would be an identity.
 void sort_skip_digits(const uint32_t* hist, uint64_t n, bool skip[gs::kSortPasses]);
+// The same from a host-known bound, with no histogram read back: every key is below `bound`, so
+// the digits above the bits of `bound` itself are zero in all of them. bound == 0: nothing is
+// known, no pass is skipped. Pass 0 always runs (sort_by_key needs one pass).
+inline void sort_skip_above(uint64_t bound, bool skip[gs::kSortPasses]) {
+  for (int p = 0; p < (int)gs::kSortPasses; ++p) skip[p] = bound != 0 && p > 0 && (bound >> (8 * p)) == 0;
+}
 
 // Stable radix passes on st over the digits of ids[payload] ^ kSortSignBit that `skip` (may be
 // null: none) does not mark. hist: the device address of the eight 256-bin rows of those keys.
@@ -112,5 +121,12 @@ int sort_run(SortScratch& s, const int64_t* ids, uint64_t n, const uint32_t* his
 // stay on the device). *cur names the sorted pairs, its payloads the pairs' indices. s.hist(0)
 // and s.hist(1) hold the histograms of x and y afterwards, for a caller that reads them back.
 int sort_by_pair(SortScratch& s, const int64_t* x, const int64_t* y, uint64_t n, gs::SortSrc* cur, hipStream_t st);
+
+// The n keys key[i] in stable ascending order on st: zeroes the control words, builds the digit
+// histograms of the column (launch_sort_digits_one), runs the passes `skip` (may be null: none)
+// does not mark. *cur names the sorted pairs, its payloads the keys' indices. GS_ERR_HIP
+// "<what>: the sort ran no pass" if skip marks all eight: the callers need the sorted keys.
+int sort_by_key(SortScratch& s, const int64_t* key, uint64_t n, const bool* skip, gs::SortSrc* cur, hipStream_t st,
+                const char* what);
 
 }  // namespace gsi

@@ -54,8 +54,7 @@ struct gs_spanner_s : StreamOwner {
   uint32_t arena_count = 0;
   uint32_t gen = 0;  // generations used since the stamps were last cleared
   // device staging of the host export and of a combine's source
-  uint64_t o_cap = 0;
-  DevBuf<int64_t> o_lo, o_hi;
+  OutStage out;  // two columns: lo, hi
   // gs_testing_spanner_stats: the last fold
   uint64_t stats[6] = {0, 0, 0, 0, 0, 0};
 
@@ -279,12 +278,6 @@ int fold_guard(gs_spanner_s* s, const void* src, const void* dst, size_t n) {
   return GS_OK;
 }
 
-int ensure_out(gs_spanner_s* s, uint64_t rows) {
-  GS_HIP(grow_group(s->stream, s->o_cap, rows, rows + rows / 4,
-                    [&](uint64_t c) { return alloc_each(c, s->o_lo, s->o_hi); }));
-  return GS_OK;
-}
-
 // the edges ascending by (lo, hi): the entries with x <= y, in the adjacency's order
 int export_impl(gs_spanner_s* s, int64_t* lo, int64_t* hi, size_t cap, size_t* n, bool to_host) {
   if (int rc = check_handle(s, kWhat)) return rc;
@@ -296,21 +289,13 @@ int export_impl(gs_spanner_s* s, int64_t* lo, int64_t* hi, size_t cap, size_t* n
   if (s->edges == 0) return GS_OK;
   if (!lo || !hi) return fail(GS_ERR_INVALID, "null arrays");
   if (int rc = ensure_flags(s, s->entries)) return rc;
-  int64_t *dl = lo, *dh = hi;
-  if (to_host) {
-    if (int rc = ensure_out(s, s->edges)) return rc;
-    dl = s->o_lo;
-    dh = s->o_hi;
-  }
+  if (to_host) GS_HIP(s->out.ensure(2, s->edges, s->stream));
   GS_LAUNCH(gs::launch_sp_flag_edges(s->ax[s->cur], s->ay[s->cur], s->entries, s->flags, s->blk, s->stream));
   GS_LAUNCH(gs::launch_tile_scan(s->blk, gs::sp_blocks(s->entries), s->ctl + gs::SP_ROWS, s->stream));
-  GS_LAUNCH(gs::launch_sp_compact_pairs(s->ax[s->cur], s->ay[s->cur], s->entries, s->flags, s->blk, dl, dh, s->edges,
-                                        s->stream));
-  if (to_host) {
-    GS_HIP(hipMemcpyAsync(lo, dl, s->edges * 8, hipMemcpyDeviceToHost, s->stream));
-    GS_HIP(hipMemcpyAsync(hi, dh, s->edges * 8, hipMemcpyDeviceToHost, s->stream));
-  }
-  GS_HIP(hipStreamSynchronize(s->stream));
+  GS_LAUNCH(gs::launch_sp_compact_pairs(s->ax[s->cur], s->ay[s->cur], s->entries, s->flags, s->blk,
+                                        s->out.dev(0, lo, to_host), s->out.dev(1, hi, to_host), s->edges, s->stream));
+  if (to_host) GS_HIP(s->out.finish(s->stream, s->edges, lo, hi));
+  else GS_HIP(hipStreamSynchronize(s->stream));  // (the device form waits too)
   return GS_OK;
 }
 
@@ -421,11 +406,12 @@ int gs_spanner_combine(gs_spanner into, gs_spanner from) {
   const uint64_t m = from->edges;
   if (m == 0) return GS_OK;
   // from's edges ascending by (lo, hi) in from's own staging; the fold reads them on into's stream
-  if (int rc = ensure_out(from, m)) return rc;
-  if (int rc = fold_guard(into, from->o_lo, from->o_hi, m)) return rc;
+  GS_HIP(from->out.ensure(2, m, from->stream));
+  int64_t *const lo = from->out.column[0], *const hi = from->out.column[1];
+  if (int rc = fold_guard(into, lo, hi, m)) return rc;
   size_t got = 0;
-  if (int rc = export_impl(from, from->o_lo, from->o_hi, m, &got, false)) return rc;
-  if (int rc = fold_impl(into, from->o_lo, from->o_hi, m, 1, into->k)) return rc;
+  if (int rc = export_impl(from, lo, hi, m, &got, false)) return rc;
+  if (int rc = fold_impl(into, lo, hi, m, 1, into->k)) return rc;
   GS_HIP(hipStreamSynchronize(into->stream));
   return GS_OK;
 }

@@ -39,8 +39,7 @@ struct gs_trisample_s : StreamOwner {
   DevBuf<gs::TsSeg> seg;           // [S + k_cap]
   SortScratch sort;
   // device staging of a host fold, of the host form of the states
-  uint64_t h_cap = 0;
-  DevBuf<int64_t> stage;           // [2][h_cap]
+  FoldStage stage;                 // (src, dst)
   uint64_t o_cap = 0;
   DevBuf<int64_t> o_src, o_trg, o_third;
   DevBuf<uint8_t> o_flags;
@@ -129,17 +128,12 @@ int fold_piece(gs_trisample_s* h, const int64_t* src, const int64_t* dst, uint64
   const unsigned long long* sorted = nullptr;
   if (K) {
     if (int rc = sort_scratch_ensure(h->sort, K, st)) return rc;
-    uint32_t* const sctl = h->sort.ctl;
-    GS_HIP(hipMemsetAsync(sctl, 0, gs::kSortCtlWords * 4, st));
-    GS_LAUNCH(gs::launch_sort_digits_one(h->keys, K, sctl, st));
     // the sort's key is id ^ 2^63 = instance << 32 | position: the digits above n's and S's bits are zero in all
     bool skip[gs::kSortPasses];
     for (int p = 0; p < 4; ++p) skip[p] = p > 0 && ((uint64_t)(n - 1) >> (8 * p)) == 0;
     for (int p = 4; p < (int)gs::kSortPasses; ++p) skip[p] = ((uint64_t)(S - 1) >> (8 * (p - 4))) == 0;
-    gs::SortSrc cur;  // (pay null: payload i of key i is i)
-    int side = 0;
-    if (int rc = sort_run(h->sort, h->keys, K, sctl, skip, &cur, &side, st)) return rc;
-    if (!cur.key) return fail(GS_ERR_HIP, "trisample fold: the sort ran no pass");
+    gs::SortSrc cur;
+    if (int rc = sort_by_key(h->sort, h->keys, K, skip, &cur, st, "trisample fold")) return rc;
     sorted = cur.key;
     GS_LAUNCH(gs::launch_ts_segments(sorted, K, S, n32, src, dst, stride, t0, h->third_seed, h->vertices, h->seg, h->ctl,
                                      st));
@@ -197,17 +191,9 @@ int fold_all(gs_trisample_s* h, const int64_t* src, const int64_t* dst, size_t n
   const uint64_t piece = piece_of(h);
   for (uint64_t at = 0; at < n; at += piece) {
     const uint64_t len = std::min<uint64_t>(piece, n - at);
-    const int64_t *ps = src + at * stride, *pd = dst + at * stride;
-    if (host) {
-      GS_HIP(grow_group(h->stream, h->h_cap, len, std::min(piece, len + len / 4),
-                        [&](uint64_t c) { return h->stage.alloc(2 * c); }));
-      int64_t* s0 = h->stage;
-      GS_HIP(hipMemcpyAsync(s0, ps, len * 8, hipMemcpyHostToDevice, h->stream));
-      GS_HIP(hipMemcpyAsync(s0 + h->h_cap, pd, len * 8, hipMemcpyHostToDevice, h->stream));
-      ps = s0;
-      pd = s0 + h->h_cap;
-    }
-    if (int rc = fold_piece(h, ps, pd, len, host ? 1 : stride)) return rc;
+    const int64_t* col[2] = {src + at * stride, dst + at * stride};
+    if (host) GS_HIP(h->stage.put(h->stream, len, piece, col));  // (fold_piece ends with a wait)
+    if (int rc = fold_piece(h, col[0], col[1], len, host ? 1 : stride)) return rc;
     sum[0] += h->stats[0];
     sum[1] += h->stats[1];
     sum[2] = std::max(sum[2], h->stats[2]);
@@ -232,11 +218,11 @@ int rows_impl(gs_trisample_s* h, int32_t* edges, int32_t* estimate, int32_t* bet
   *n = rows;
   if (cap < rows) return truncated(cap, rows);
   if (rows == 0) return GS_OK;
-  const hipMemcpyKind kind = to_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-  if (edges) GS_HIP(hipMemcpyAsync(edges, h->row_t, rows * 4, kind, h->stream));
-  if (estimate) GS_HIP(hipMemcpyAsync(estimate, h->row_est, rows * 4, kind, h->stream));
-  if (beta_sum) GS_HIP(hipMemcpyAsync(beta_sum, h->row_beta, rows * 4, kind, h->stream));
-  if (to_host) GS_HIP(hipStreamSynchronize(h->stream));
+  const ColumnCopy copy(h->stream, to_host);
+  GS_HIP(copy.col(edges, h->row_t.get(), rows));
+  GS_HIP(copy.col(estimate, h->row_est.get(), rows));
+  GS_HIP(copy.col(beta_sum, h->row_beta.get(), rows));
+  GS_HIP(copy.done());
   return GS_OK;
 }
 
@@ -253,12 +239,13 @@ int states_impl(gs_trisample_s* h, int64_t* src, int64_t* trg, int64_t* third, u
     return alloc_each(c, h->o_src, h->o_trg, h->o_third, h->o_flags, h->o_at);
   }));
   GS_LAUNCH(gs::launch_ts_states(h->st, S, h->o_src, h->o_trg, h->o_third, h->o_flags, h->o_at, h->stream));
-  if (src) GS_HIP(hipMemcpyAsync(src, h->o_src, (size_t)S * 8, hipMemcpyDeviceToHost, h->stream));
-  if (trg) GS_HIP(hipMemcpyAsync(trg, h->o_trg, (size_t)S * 8, hipMemcpyDeviceToHost, h->stream));
-  if (third) GS_HIP(hipMemcpyAsync(third, h->o_third, (size_t)S * 8, hipMemcpyDeviceToHost, h->stream));
-  if (flags) GS_HIP(hipMemcpyAsync(flags, h->o_flags, S, hipMemcpyDeviceToHost, h->stream));
-  if (sampled_at) GS_HIP(hipMemcpyAsync(sampled_at, h->o_at, (size_t)S * 4, hipMemcpyDeviceToHost, h->stream));
-  GS_HIP(hipStreamSynchronize(h->stream));
+  const ColumnCopy copy(h->stream, true);
+  GS_HIP(copy.col(src, h->o_src.get(), S));
+  GS_HIP(copy.col(trg, h->o_trg.get(), S));
+  GS_HIP(copy.col(third, h->o_third.get(), S));
+  GS_HIP(copy.col(flags, h->o_flags.get(), S));
+  GS_HIP(copy.col(sampled_at, h->o_at.get(), S));
+  GS_HIP(copy.done());
   return GS_OK;
 }
 

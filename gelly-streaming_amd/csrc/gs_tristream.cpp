@@ -57,17 +57,14 @@ struct gs_tristream_s : StreamOwner, VertexTable {  // (the vertex table and the
   DevBuf<gs::TrsSeg> agg, carry;
   SortScratch sort;
   // device staging of a host fold
-  uint64_t h_cap = 0;
-  DevBuf<int64_t> stage;  // [2][h_cap]
+  FoldStage stage;  // (src, dst)
   // head counts of a fold and of an export; the export's vertices and ranks; host-array staging
   uint64_t x_tiles = 0;
   DevBuf<uint32_t> x_blk;
   uint64_t v_cap = 0;
   DevBuf<int64_t> hv, hrank;
-  uint64_t o_cap = 0;
-  DevBuf<int64_t> o_a, o_b;
-  // host-known totals
-  uint64_t nv = 0;  // ids in the vertex table (every endpoint seen, a failed fold's included)
+  OutStage out;  // two columns
+  // host-known totals (nv of VertexTable: every endpoint seen, a failed fold's included)
   uint64_t vertices = 0, edges = 0, total = 0;
   int64_t triangles = 0;
   uint64_t last_n = 0, last_rec = 0, last_new = 0, last_tiles = 0;
@@ -96,19 +93,7 @@ constexpr uint64_t kTrsMinEdges = 32;
 constexpr const char* kWhat = "tristream";  // check_handle: "null tristream handle"
 
 // The vertex table grows (VertexTable::grow) and the counters with it, inside the same wait.
-int grow_vertices(gs_tristream_s* d, uint64_t cap) {
-  DevBuf<int64_t> ctr;
-  const uint64_t ranks = gs::dist_vid_cap(cap);
-  const int rc = d->grow(cap, d->nv, d->dctl, d->stream, [&](bool rebuild) -> int {
-    GS_HIP(ctr.alloc(ranks));
-    GS_HIP(hipMemsetAsync(ctr, 0, ranks * 8, d->stream));
-    if (rebuild && d->nv) GS_HIP(hipMemcpyAsync(ctr, d->counter, d->nv * 8, hipMemcpyDeviceToDevice, d->stream));
-    return GS_OK;
-  });
-  if (rc) return rc;
-  d->counter.swap(ctr);
-  return GS_OK;
-}
+int grow_vertices(gs_tristream_s* d, uint64_t cap) { return d->grow_ranked(cap, d->dctl, d->stream, d->counter); }
 
 int ensure_adj(gs_tristream_s* d, int side, uint64_t need) {
   GS_HIP(grow_group(d->stream, d->acap[side], need, std::min<uint64_t>(kTrsMaxEntries, need + need / 2),
@@ -169,36 +154,14 @@ int fold_guard(gs_tristream_s* d, const void* src, const void* dst, size_t n) {
   if (2 * (d->edges + (uint64_t)n) > kTrsMaxEntries)
     return fail(GS_ERR_CAPACITY, "tristream adjacency: " + std::to_string(d->edges) + " + " + std::to_string(n) +
                                      " pairs could pass 2^32 - 1 entries");
-  const uint64_t piece = std::min<uint64_t>(n, gs::kTrsMaxFold);
-  const uint64_t need_v = d->nv + gs::dist_worst_vertices(n);
-  if (need_v > gs::kDistMaxVertices ||
-      (gs::dist_must_grow(d->nv, gs::dist_worst_vertices(piece), d->vcap) &&
-       gs::dist_slots_for(d->nv + gs::dist_worst_vertices(piece)) > gs::kDistMaxSlots))
-    return fail(GS_ERR_CAPACITY, "tristream fold: the fold may pass 2^31 vertex table slots");
-  return GS_OK;
-}
-
-// the stable radix sort of n keys below `bound` (key[i] of row i): the digits above the bits of
-// bound - 1 are equal in all keys and skipped (bound 0: none is)
-int sort_keys(gs_tristream_s* d, const int64_t* key, uint64_t n, uint64_t bound, gs::SortSrc* cur) {
-  uint32_t* const sctl = d->sort.ctl;
-  GS_HIP(hipMemsetAsync(sctl, 0, gs::kSortCtlWords * 4, d->stream));
-  GS_LAUNCH(gs::launch_sort_digits_one(key, n, sctl, d->stream));
-  bool skip[gs::kSortPasses];
-  for (int p = 0; p < (int)gs::kSortPasses; ++p) skip[p] = bound && p > 0 && (bound >> (8 * p)) == 0;
-  *cur = gs::SortSrc();  // (pay null: payload i of row i is i)
-  int side = 0;
-  if (int rc = sort_run(d->sort, key, n, sctl, skip, cur, &side, d->stream)) return rc;
-  if (!cur->key || !cur->pay) return fail(GS_ERR_HIP, "tristream fold: the sort ran no pass");
-  return GS_OK;
+  return d->fold_guard_vertices(n, std::min<uint64_t>(n, gs::kTrsMaxFold), kWhat);
 }
 
 // 0 < n <= kTrsMaxFold device arrivals on d->stream
 int fold_piece(gs_tristream_s* d, const int64_t* src, const int64_t* dst, uint64_t n, uint64_t stride) {
   hipStream_t st = d->stream;
   const uint64_t t0 = d->total;
-  if (gs::dist_must_grow(d->nv, gs::dist_worst_vertices(n), d->vcap))
-    if (int rc = grow_vertices(d, gs::dist_slots_for(d->nv + gs::dist_worst_vertices(n)))) return rc;
+  if (int rc = d->ensure_for(n, [&](uint64_t slots) { return grow_vertices(d, slots); })) return rc;
   if (int rc = ensure_scratch(d, n)) return rc;
   if (int rc = sort_scratch_ensure(d->sort, n, st)) return rc;
   const gs::DistVTable vt = d->vtable();
@@ -242,7 +205,7 @@ int fold_piece(gs_tristream_s* d, const int64_t* src, const int64_t* dst, uint64
   if (m) {
     if (int rc = ensure_adj(d, other, merged)) return rc;
     if (int rc = ensure_head_tiles(d, merged)) return rc;
-    if (int rc = sort_keys(d, d->ny, m, 0, &cur)) return rc;
+    if (int rc = sort_by_key(d->sort, d->ny, m, nullptr, &cur, st, "tristream fold")) return rc;  // (ids: no bound)
     GS_LAUNCH(gs::launch_trs_reverse(cur.pay, d->nx, d->ny, d->nf, m, d->rx, d->ry, d->rf, st));
     gs::TrsAdjOut out;
     out.x = d->ax[other];
@@ -285,7 +248,9 @@ int fold_piece(gs_tristream_s* d, const int64_t* src, const int64_t* dst, uint64
   if (recs) {
     // 7. ranks, the stable sort by rank, the seeded segmented sum, the counters
     GS_LAUNCH(gs::launch_dist_rank(vt, d->r_v, recs, d->r_key, nullptr, st));
-    if (int rc = sort_keys(d, d->r_key, recs, d->nv, &cur)) return rc;
+    bool skip[gs::kSortPasses];  // every key is a rank below nv
+    sort_skip_above(d->nv, skip);
+    if (int rc = sort_by_key(d->sort, d->r_key, recs, skip, &cur, st, "tristream fold")) return rc;
     timer.mark(5);
     GS_LAUNCH(gs::launch_trs_seg_pass(cur.key, cur.pay, d->r_delta, recs, d->counter, ranks, d->agg, d->carry, d->r_cnt,
                                       d->ctl, st));
@@ -318,17 +283,9 @@ int fold_all(gs_tristream_s* d, const int64_t* src, const int64_t* dst, size_t n
   uint64_t sum[3] = {0, 0, 0};
   for (uint64_t at = 0; at < n; at += gs::kTrsMaxFold) {
     const uint64_t len = std::min<uint64_t>(gs::kTrsMaxFold, n - at);
-    const int64_t *ps = src + at * stride, *pd = dst + at * stride;
-    if (host) {
-      GS_HIP(grow_group(d->stream, d->h_cap, len, std::min<uint64_t>(gs::kTrsMaxFold, len + len / 4),
-                        [&](uint64_t c) { return d->stage.alloc(2 * c); }));
-      int64_t* s0 = d->stage;
-      GS_HIP(hipMemcpyAsync(s0, ps, len * 8, hipMemcpyHostToDevice, d->stream));
-      GS_HIP(hipMemcpyAsync(s0 + d->h_cap, pd, len * 8, hipMemcpyHostToDevice, d->stream));
-      ps = s0;
-      pd = s0 + d->h_cap;
-    }
-    if (int rc = fold_piece(d, ps, pd, len, host ? 1 : stride)) {
+    const int64_t* col[2] = {src + at * stride, dst + at * stride};
+    if (host) GS_HIP(d->stage.put(d->stream, len, gs::kTrsMaxFold, col));
+    if (int rc = fold_piece(d, col[0], col[1], len, host ? 1 : stride)) {
       if (at) d->kept = false;  // (the pieces before this one are folded: gs_tristream_size tells how far)
       return rc;
     }
@@ -360,10 +317,10 @@ int rows_impl(gs_tristream_s* d, uint32_t* closed, int64_t* total, size_t cap, s
   *n = rows;
   if (cap < rows) return truncated(cap, rows);
   if (rows == 0) return GS_OK;
-  const hipMemcpyKind kind = to_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-  if (closed) GS_HIP(hipMemcpyAsync(closed, d->row_closed, rows * 4, kind, d->stream));
-  if (total) GS_HIP(hipMemcpyAsync(total, d->row_total, rows * 8, kind, d->stream));
-  if (to_host) GS_HIP(hipStreamSynchronize(d->stream));
+  const ColumnCopy copy(d->stream, to_host);
+  GS_HIP(copy.col(closed, d->row_closed.get(), rows));
+  GS_HIP(copy.col(total, d->row_total.get(), rows));
+  GS_HIP(copy.done());
   return GS_OK;
 }
 
@@ -375,11 +332,11 @@ int records_impl(gs_tristream_s* d, uint32_t* arrival, int64_t* vertex, int64_t*
   *n = rows;
   if (cap < rows) return truncated(cap, rows);
   if (rows == 0) return GS_OK;
-  const hipMemcpyKind kind = to_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-  if (arrival) GS_HIP(hipMemcpyAsync(arrival, d->r_arr, rows * 4, kind, d->stream));
-  if (vertex) GS_HIP(hipMemcpyAsync(vertex, d->r_v, rows * 8, kind, d->stream));
-  if (count) GS_HIP(hipMemcpyAsync(count, d->r_cnt, rows * 8, kind, d->stream));
-  if (to_host) GS_HIP(hipStreamSynchronize(d->stream));
+  const ColumnCopy copy(d->stream, to_host);
+  GS_HIP(copy.col(arrival, d->r_arr.get(), rows));
+  GS_HIP(copy.col(vertex, d->r_v.get(), rows));
+  GS_HIP(copy.col(count, d->r_cnt.get(), rows));
+  GS_HIP(copy.done());
   return GS_OK;
 }
 
@@ -409,18 +366,10 @@ int counts_impl(gs_tristream_s* d, int64_t* vertex, int64_t* count, size_t cap, 
   *n = rows;
   if (cap < rows) return truncated(cap, rows);
   if (rows == 0) return GS_OK;
-  int64_t *da = vertex, *db = count;
-  if (to_host) {
-    GS_HIP(grow_group(st, d->o_cap, rows, rows + rows / 4, [&](uint64_t c) { return alloc_each(c, d->o_a, d->o_b); }));
-    da = vertex ? d->o_a.get() : nullptr;
-    db = count ? d->o_b.get() : nullptr;
-  }
-  GS_LAUNCH(gs::launch_trs_live_write(d->hv, d->hrank, heads, d->counter, ranks, d->x_blk, da, db, rows, st));
-  if (to_host) {
-    if (vertex) GS_HIP(hipMemcpyAsync(vertex, da, rows * 8, hipMemcpyDeviceToHost, st));
-    if (count) GS_HIP(hipMemcpyAsync(count, db, rows * 8, hipMemcpyDeviceToHost, st));
-    GS_HIP(hipStreamSynchronize(st));
-  }
+  if (to_host) GS_HIP(d->out.ensure(2, rows, st));
+  GS_LAUNCH(gs::launch_trs_live_write(d->hv, d->hrank, heads, d->counter, ranks, d->x_blk, d->out.dev(0, vertex, to_host),
+                                      d->out.dev(1, count, to_host), rows, st));
+  if (to_host) GS_HIP(d->out.finish(st, rows, vertex, count));
   return GS_OK;
 }
 

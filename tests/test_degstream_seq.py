@@ -62,7 +62,7 @@ def test_kernels_and_host_include_the_checked_header():
         host = f.read()
     assert '#include "gs_degstream.hpp"' in host and '#include "gs_vtable.hpp"' in host
     for fn in ("kDsMaxTotal", "kDsMaxFold", "ds_occurrences(", "ds_count_cap(", "launch_dist_vertices(",
-               "launch_tile_scan(", "sort_run(", "launch_sort_digits_one(", "grow_group(", "check_handle(",
+               "launch_tile_scan(", "sort_by_key(", "sort_skip_above(", "grow_group(", "check_handle(",
                "GS_LAUNCH(", ": StreamOwner, VertexTable"):
         assert fn in host, fn
     # the definition and the decomposition are made of the same rules

@@ -78,7 +78,7 @@ def test_kernels_and_host_include_the_checked_header():
         host = f.read()
     assert '#include "gs_trisample.hpp"' in host
     for fn in ("kTsChunk", "kTsTile", "kTsMaxFold", "kTsMaxSamples", "kTsMaxVertices", "kTsMaxArrivals",
-               "launch_tile_scan(", "sort_run(", "grow_group(", "check_handle(", "truncated(", "owner_create("):
+               "launch_tile_scan(", "sort_by_key(", "grow_group(", "check_handle(", "truncated(", "owner_create("):
         assert fn in host, fn
     with open(os.path.join(CSRC, "gs_trisample_seq.hpp")) as f:
         seq = f.read()

@@ -99,8 +99,8 @@ def test_kernels_and_host_include_the_checked_header():
         host = f.read()
     assert '#include "gs_tristream.hpp"' in host and '#include "gs_vtable.hpp"' in host
     for fn in ("kTrsMaxTotal", "kTrsMaxFold", "kTrsMaxRecords", "launch_dist_vertices(", "launch_dist_rank(",
-               "launch_tri_canon(", "launch_tri_flag_new(", "launch_tile_scan(", "sort_by_pair(", "sort_run(",
-               "launch_sort_digits_one(", "grow_group(", "check_handle(", "GS_LAUNCH(", ": StreamOwner, VertexTable"):
+               "launch_tri_canon(", "launch_tri_flag_new(", "launch_tile_scan(", "sort_by_pair(", "sort_by_key(",
+               "sort_skip_above(", "grow_group(", "check_handle(", "GS_LAUNCH(", ": StreamOwner, VertexTable"):
         assert fn in host, fn
     # the definition and the decomposition are made of the same rules
     with open(os.path.join(CSRC, "gs_tristream_seq.hpp")) as f:
