@@ -74,6 +74,8 @@ EXPORTED_SYMBOLS = (
     "gs_triangle_count", "gs_triangle_count_device", "gs_triangle_find_device", "gs_triangle_export_device",
     "gs_triangle_export", "gs_triangle_sync", "gs_triangle_get_stream", "gs_triangle_wait_stream",
     "gs_testing_triangle_stats", "gs_testing_triangle_bins",
+    "gs_triangle_remove", "gs_triangle_remove_device", "gs_triangle_expire", "gs_triangle_set_refresh",
+    "gs_testing_triangle_remove_stats", "gs_testing_triangle_remove_phases", "gs_testing_triangle_set_fold",
     "gs_slice_create", "gs_slice_destroy", "gs_slice_window", "gs_slice_window_device", "gs_slice_size",
     "gs_slice_reduce_device", "gs_slice_reduce", "gs_slice_neighborhoods_device", "gs_slice_neighborhoods",
     "gs_slice_sync", "gs_slice_get_stream", "gs_slice_wait_stream", "gs_testing_slice_stats",
@@ -363,6 +365,13 @@ def lib():
     L.gs_triangle_wait_stream.argtypes = [_vp, _vp]
     L.gs_testing_triangle_stats.argtypes = [_vp, ctypes.POINTER(_u64)]
     L.gs_testing_triangle_bins.argtypes = [_vp, ctypes.POINTER(_u64)]
+    L.gs_triangle_remove.argtypes = [_vp, _vp, _vp, _sz]
+    L.gs_triangle_remove_device.argtypes = [_vp, _vp, _vp, _sz, _sz]
+    L.gs_triangle_expire.argtypes = [_vp, _u64]
+    L.gs_triangle_set_refresh.argtypes = [_vp, ctypes.c_int]
+    L.gs_testing_triangle_remove_stats.argtypes = [_vp, ctypes.POINTER(_u64)]
+    L.gs_testing_triangle_remove_phases.argtypes = [_vp, ctypes.POINTER(_u64)]
+    L.gs_testing_triangle_set_fold.argtypes = [_vp, _u64]
     L.gs_slice_create.argtypes = [ctypes.POINTER(_vp), ctypes.c_int, _u64]
     L.gs_slice_destroy.argtypes = [_vp]
     L.gs_slice_window.argtypes = [_vp, _vp, _vp, _vp, _sz, ctypes.c_int]
@@ -1181,7 +1190,7 @@ class Triangles(_ResetHandle):
     or the running global and per-vertex counts of an insertion-only stream
     (example/ExactTriangleCount: `fold` after `fold`). Direction, repeated edges and self-loops
     do not change the graph. `reset`: the graph empty and every counter zero; capacity is kept.
-    Owns a gs_triangles handle."""
+    Owns a gs_triangles handle. (SlidingTriangles is this class with removal.)"""
 
     _PREFIX = "gs_triangle"
 
@@ -1260,6 +1269,56 @@ class Triangles(_ResetHandle):
         out = (_u64 * 2)()
         _check(lib().gs_testing_triangle_bins(self._h, out))
         return out[0], out[1]
+
+
+class SlidingTriangles(Triangles):
+    """Triangles whose edges also leave the graph: by name (`remove`) or by age in folds
+    (`expire`; `slide` is one step of a sliding window). The same gs_triangles handle and every
+    method of Triangles; the answers always equal those of a fresh handle that folded exactly
+    the surviving edges, and a vertex without edges is no vertex any more. `refresh=True`
+    (gs_triangle_set_refresh): an edge that a fold contains again takes that fold's age. The
+    pinned public surface of Triangles itself stays as it was, so the removal lives here."""
+
+    def __init__(self, device=0, edge_hint=1 << 20, refresh=False):
+        super().__init__(device, edge_hint)
+        if refresh:
+            _check(lib().gs_triangle_set_refresh(self._h, 1))
+
+    def remove(self, src, dst):
+        """Remove host pairs (int64 arrays) from the graph; pairs it does not hold, loops and
+        repeats change nothing."""
+        s, d = _edges(src, dst)
+        _check(lib().gs_triangle_remove(self._h, s.ctypes.data, d.ctypes.data, len(s)))
+
+    def remove_device(self, src, dst, n=None, stride=1, after=None):
+        """Remove device-resident pairs, queued on the handle's stream as fold_device queues a
+        fold. Synchronises with the host once (the number of dying edges)."""
+        if n is None:
+            n = src.numel() // (stride if stride > 1 else 1)
+        if after is not None:
+            self.wait_stream(after)
+        _check(lib().gs_triangle_remove_device(self._h, _ptr(src), _ptr(dst), int(n), int(stride)))
+
+    def expire(self, folds):
+        """Remove every edge older than the last `folds` folds (folds >= 1; a fold of no edges
+        counts as a fold)."""
+        _check(lib().gs_triangle_expire(self._h, int(folds)))
+
+    def slide(self, src, dst, panes):
+        """One step of a window that slides by a pane of host edges: fold the pane, expire what
+        is older than `panes` panes, return the triangle count. With refresh=True the graph is
+        the union of the last `panes` panes."""
+        self.fold(src, dst)
+        self.expire(panes)
+        return self.count()[0]
+
+    def remove_stats(self):
+        """gs_testing_triangle_remove_stats: the last removal (remove, remove_device, expire)."""
+        out = (_u64 * 8)()
+        _check(lib().gs_testing_triangle_remove_stats(self._h, out))
+        keys = ("edges_removed", "triangles_destroyed", "vertices_vanished", "wave_list", "workgroup_list", "steps",
+                "table_slots", "entries")
+        return dict(zip(keys, (int(x) for x in out)))
 
 
 # ---------------------------------------------------------------- window slices

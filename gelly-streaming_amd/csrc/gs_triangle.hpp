@@ -56,7 +56,15 @@ enum TriCtl : int {
   TRI_BIN2 = 8,   //               edges in the workgroup list
   TRI_STEPS = 9,  // diagnostics: sum over new edges of the shorter row length, since reset
   TRI_HOT = 10,   // diagnostics: the longest row a new edge met, since reset
-  TRI_CTL_WORDS = 16
+  // the last removal (gs_triangle_remove / _expire), zeroed when one begins
+  TRI_RNEW = 11,    // D, its dying edges
+  TRI_RBIN1 = 12,   // binned count: dying edges in the removal's wave list
+  TRI_RBIN2 = 13,   //               dying edges in the removal's workgroup list
+  TRI_RSTEPS = 14,  // sum over the dying edges of the shorter row length
+  TRI_RTRI = 15,    // triangles destroyed
+  TRI_RVAN = 16,    // vertices whose every entry dies
+  TRI_RLIVE = 17,   // surviving entries of A
+  TRI_CTL_WORDS = 24
 };
 
 struct TriAdj {
@@ -80,6 +88,21 @@ struct TriRowInfo {
 };
 
 __host__ __device__ constexpr uint64_t tri_blocks(uint64_t n) { return (n + TRIANGLE_TILE - 1) / TRIANGLE_TILE; }
+
+// Which entries of A the once-only rule treats as marked (gs_triangle_k.hip tri_walk), and
+// whether a counted triangle is added or taken away. A fold marks the entries of its own
+// number and adds; a removal marks the dying entries and adds the two's complement.
+struct TriFoldMark {
+  static constexpr bool kRemove = false;
+  const uint32_t* seq;
+  uint32_t cur;
+  __host__ __device__ bool marked(uint64_t i) const { return seq[i] == cur; }
+};
+struct TriDyingMark {
+  static constexpr bool kRemove = true;
+  const uint8_t* dead;
+  __host__ __device__ bool marked(uint64_t i) const { return dead[i] != 0; }
+};
 
 // every slot empty, link = slot << 1, aux = 0 (slots 0 .. cap)
 void launch_tri_init(const Table& t, hipStream_t st);
@@ -108,10 +131,50 @@ void launch_tri_merge(const TriAdj& A, const int64_t* nx, const int64_t* ny, con
 void launch_tri_rows(const Table& t, unsigned long long* ctl, const TriAdj& A, const int64_t* nx, const int64_t* ny,
                      uint64_t n_new, TriRowInfo* info, uint32_t* list1, uint32_t* list2, int variant,
                      hipStream_t st);
+// The same pass over the dying edges D while A still holds them. Nothing is inserted (a slot is
+// found, or kNoSlot), TRI_E and TRI_NV stay, and the lists and the steps are the removal's own
+// words (TRI_RBIN1, TRI_RBIN2, TRI_RSTEPS); TRI_STEPS / TRI_HOT / TRI_BIN1 / TRI_BIN2 keep
+// meaning folds.
+void launch_tri_rows_dying(const Table& t, unsigned long long* ctl, const TriAdj& A, const int64_t* dx,
+                           const int64_t* dy, uint64_t n_dying, TriRowInfo* info, uint32_t* list1, uint32_t* list2,
+                           int variant, hipStream_t st);
 // the intersection: every triangle closed by a new edge counted once (the once-only rule)
 void launch_tri_count(const Table& t, unsigned long long* ctl, const TriAdj& A, const int64_t* nx, const int64_t* ny,
                       uint64_t n_new, const TriRowInfo* info, const uint32_t* list1, const uint32_t* list2,
                       uint32_t seq, int variant, hipStream_t st);
+// The same walk over the dying edges D with A's dying bytes as the marked set: every triangle
+// that loses an edge is counted once, at its greatest dying edge, and taken from t(w), t(u),
+// t(v) and T by a 64-bit add of the two's complement; ctl[TRI_RTRI] += the triangles destroyed.
+void launch_tri_uncount(const Table& t, unsigned long long* ctl, const TriAdj& A, const uint8_t* dead,
+                        const int64_t* dx, const int64_t* dy, uint64_t n_dying, const TriRowInfo* info,
+                        const uint32_t* list1, const uint32_t* list2, int variant, hipStream_t st);
+// As launch_tri_flag_new, but flags the rows that ARE in A, and sets dead[] of both directed
+// entries of every flagged row (dead: A.n bytes, zero before).
+void launch_tri_flag_dying(const uint32_t* pay, const int64_t* lo, const int64_t* hi, uint64_t n, const TriAdj& A,
+                           uint8_t* flags, uint32_t* blk, uint8_t* dead, hipStream_t st);
+// dead[i] = entry i's stamp is at least `folds` folds behind `cur` (cur - seq[i] >= folds, no
+// stamp exceeds cur); flags[i] = dead[i] and x < y (D's entries, in order); blk as above
+void launch_tri_mark_old(const TriAdj& A, uint32_t cur, uint64_t folds, uint8_t* dead, uint8_t* flags,
+                         uint32_t* blk, hipStream_t st);
+// blk[b] = surviving (dead[i] == 0) entries of tile b of the n entries
+void launch_tri_live_count(const uint8_t* dead, uint64_t n, uint32_t* blk, hipStream_t st);
+// pos[i] = surviving entries before entry i (blk after launch_tile_scan): where a survivor goes
+void launch_tri_live_pos(const uint8_t* dead, uint64_t n, const uint32_t* blk, uint32_t* pos, hipStream_t st);
+// ctl[TRI_RVAN] += the rows of A without a survivor (ctl[TRI_RLIVE]: the scan's total)
+void launch_tri_vanish(const TriAdj& A, const uint8_t* dead, const uint32_t* pos, unsigned long long* ctl,
+                       hipStream_t st);
+// O[pos[i]] = A[i] for every survivor
+void launch_tri_keep(const TriAdj& A, const uint8_t* dead, const uint32_t* pos, const TriAdjOut& O, hipStream_t st);
+// After a removal of n_dying edges, O the compacted adjacency of n_live entries: TRI_E -= n_dying,
+// TRI_NV -= TRI_RVAN, and INT64_MIN's presence flag and counter cleared when it heads no row.
+void launch_tri_removed(unsigned long long* ctl, const int64_t* ox, uint64_t n_live, uint64_t n_dying,
+                        hipStream_t st);
+// Refresh: seq = cur for both directed entries of every element (lo[i], hi[i]), i < n, that is
+// no loop and in A (seq: A's stamps, writable).
+void launch_tri_restamp(const int64_t* lo, const int64_t* hi, uint64_t n, const TriAdj& A, uint32_t* seq,
+                        uint32_t cur, hipStream_t st);
+// The fold number wrapped: every stamp s becomes s - 2^31, or 0 when it is older than that.
+void launch_tri_rebase(uint32_t* seq, uint64_t n, hipStream_t st);
 // count[i] = t(v[i]) (0 when absent), found[i] (optional) = v[i] is a vertex of G
 void launch_tri_find(const Table& t, const unsigned long long* ctl, const int64_t* v, uint64_t n, int64_t* count,
                      uint8_t* found, hipStream_t st);

@@ -72,6 +72,33 @@ GS_TRI_HD bool tri_has_pair(const int64_t* x, const int64_t* y, uint64_t n, int6
   return p < n && x[p] == kx && y[p] == ky;
 }
 
+// index of the pair (kx, ky) among the n pairs ascending by (x, y), or kTriNone
+GS_TRI_HD uint64_t tri_pair_at(const int64_t* x, const int64_t* y, uint64_t n, int64_t kx, int64_t ky) {
+  const uint64_t p = tri_pair_lower(x, y, n, kx, ky);
+  return (p < n && x[p] == kx && y[p] == ky) ? p : kTriNone;
+}
+
+// ---- removal (tests/cpp/triangle_removal_sanitize.cpp checks these against brute force)
+
+// Is the stamp s at least `folds` folds behind the fold number cur (s + folds <= cur)? The age
+// is a difference of 32 bits compared in 64: nothing can wrap. A stamp past cur has age 0.
+GS_TRI_HD bool tri_is_old(uint32_t s, uint32_t cur, uint64_t folds) {
+  const uint64_t age = s <= cur ? (uint64_t)(cur - s) : 0;
+  return age >= folds;
+}
+
+// The stamp after the fold number wrapped: 2^31 lower, or 0 when it was older than that.
+GS_TRI_HD uint32_t tri_rebase(uint32_t s) { return s >= 0x80000000u ? s - 0x80000000u : 0u; }
+
+// pos[j] = survivors among the entries before j (j < n), live = survivors among all n. For
+// the row head i (i < n, x[i - 1] != x[i]): does no entry of i's row survive? One search for
+// the row's end inside [i, n); reads pos[i] and, when the row ends before n, pos[end].
+GS_TRI_HD bool tri_row_gone(const int64_t* x, uint64_t n, uint64_t i, const uint32_t* pos, uint64_t live) {
+  const uint64_t e = tri_upper(x, i, n, x[i]);
+  const uint64_t pe = e < n ? (uint64_t)pos[e] : live;
+  return pe == (uint64_t)pos[i];
+}
+
 // The predecessor test: does the edge of the directed entry (ex, ey) precede the canonical
 // edge (u, v), u < v, in the order of canonical pairs (min, max)?
 GS_TRI_HD bool tri_edge_before(int64_t ex, int64_t ey, int64_t u, int64_t v) {

@@ -1204,6 +1204,67 @@ class WindowTriangles {
   int device_;
 };
 
+// WindowTriangles over Flink's sliding time windows (SlidingEventTimeWindows.of(size, slide),
+// offset 0): an element of timestamp ts belongs to the size / slide windows that start at
+// lastStart, lastStart - slide, ... > ts - size, lastStart = ts - (ts mod slide). size must be
+// a multiple of slide (refused otherwise): panes are slide ms wide and a window is the union of
+// size / slide consecutive panes. The handle slides instead of re-folding: per pane one fold
+// (of zero elements for a pane without edges) on a handle with refresh on, then
+// gs_triangle_expire(size / slide). run() returns (count, window.maxTimestamp()) for every
+// window Flink would fire that holds at least one non-loop edge, in window order: the leading
+// partial windows and the trailing ones behind the last pane with edges included. With
+// size == slide these are WindowTriangles' rows.
+class SlidingWindowTriangles {
+ public:
+  SlidingWindowTriangles(int64_t sizeMillis, int64_t slideMillis, int device = 0)
+      : size_(sizeMillis), slide_(slideMillis), device_(device) {
+    if (slideMillis <= 0 || sizeMillis <= 0 || sizeMillis % slideMillis != 0)
+      throw std::invalid_argument("SlidingWindowTriangles: size must be a positive multiple of slide");
+  }
+
+  template <typename K, typename EV>
+  std::vector<std::pair<long, int64_t>> run(const EdgeStream<K, EV>& stream) const {
+    std::map<int64_t, std::pair<std::vector<int64_t>, std::vector<int64_t>>> panes;
+    for (size_t i = 0; i < stream.edges.size(); ++i) {
+      const int64_t ts = stream.timestamps.empty() ? 0 : stream.timestamps[i];
+      int64_t p = ts / slide_;
+      if (ts % slide_ < 0) --p;  // floor
+      auto& e = panes[p];
+      e.first.push_back((int64_t)stream.edges[i].getSource());
+      e.second.push_back((int64_t)stream.edges[i].getTarget());
+    }
+    std::vector<std::pair<long, int64_t>> out;
+    if (panes.empty()) return out;
+    const int64_t w = size_ / slide_;
+    TriangleHandle h(device_, stream.edges.size());
+    gs_check(gs_triangle_set_refresh(h.t, 1));
+    auto next = panes.begin();
+    // q: the last pane of the window [(q - w + 1) * slide, (q + 1) * slide)
+    for (int64_t q = next->first; q < panes.rbegin()->first + w; ++q) {
+      if (next != panes.end() && next->first == q) {
+        gs_check(gs_triangle_fold(h.t, next->second.first.data(), next->second.second.data(), next->second.first.size()));
+        ++next;
+      } else {
+        gs_check(gs_triangle_fold(h.t, nullptr, nullptr, 0));  // an empty pane ages the others
+      }
+      gs_check(gs_triangle_expire(h.t, (uint64_t)w));
+      uint64_t tri = 0, edges = 0, vertices = 0;
+      gs_check(gs_triangle_count(h.t, &tri, &edges, &vertices));
+      if (edges == 0) {
+        // nothing is held: the empty panes up to the next one with edges would change nothing
+        if (next != panes.end() && next->first > q + 1) q = next->first - 1;
+        continue;
+      }
+      out.emplace_back((long)tri, (q + 1) * slide_ - 1);
+    }
+    return out;
+  }
+
+ private:
+  int64_t size_, slide_;
+  int device_;
+};
+
 // ExactTriangleCount (example/ExactTriangleCount.java:52-56): buildNeighborhood,
 // IntersectNeighborhoods, SumAndEmitCounters. stream() returns every emitted tuple in order;
 // run() folds the stream in batches of `batch` edges and returns the final counter map: key -1

@@ -467,8 +467,21 @@ int gs_degree_distribution(gs_handle h, int64_t* degree, int64_t* count, size_t 
  * ExactTriangleCount (key -1 the total, the other keys the vertices). The reference
  * intersects a repeated edge again and counts its triangles twice; here it is ignored. The
  * reference's handling of self-loops (the j = i candidates of WindowTriangles.java:103-104,
- * undirected() of a loop) is not reproduced. No deletions, gs_combine, serialization or
- * multi-GPU groups.
+ * undirected() of a loop) is not reproduced. No gs_combine, serialization or multi-GPU groups.
+ *
+ * Removal. Edges leave G by name (gs_triangle_remove) or by age (gs_triangle_expire). After any
+ * sequence of fold, remove, expire and reset every answer still depends on G only and equals
+ * that of a fresh handle that folded exactly G. A vertex whose last edge is removed is no
+ * vertex any more: it is not counted, not exported, found = 0, and a new vertex again when a
+ * later fold brings it back (INT64_MIN included). G stays a set: a remove deletes the pair
+ * however often it was folded. Every edge carries a stamp, the number of the fold that added
+ * it -- or, with refresh on (gs_triangle_set_refresh), of the last fold that contained it. Fold
+ * numbers count calls: a fold of zero elements takes one too. They have 32 bits; at the wrap
+ * the stamps are rebased, so ages within the last 2^31 folds stay exact and older ones read as
+ * 2^31. A removal is not a fold: the fold number does not move. It synchronises with the host
+ * ONCE (the number of dying edges); a removal after which a vertex vanished rebuilds the vertex
+ * table at its capacity (the first such rebuild at a capacity waits once more, to allocate the
+ * second table). The table and the adjacency buffers never shrink.
  *
  * Synchronisation: a fold synchronises with the host ONCE, to learn the number of new edges
  * and grow its arrays; apart from that gs_triangle_fold_device is ordered like
@@ -482,6 +495,17 @@ int gs_degree_distribution(gs_handle h, int64_t* degree, int64_t* count, size_t 
  * gs_triangle_reset: G empty, counters zero, capacity kept.
  * gs_triangle_fold / _fold_device: n edges from HOST arrays (copied before the call
  *   returns) / DEVICE arrays, element i = src[i*stride], dst[i*stride].
+ * gs_triangle_remove / _remove_device: n pairs from HOST / DEVICE arrays, with the argument
+ *   checks and the stream behaviour of fold / fold_device. Every element names an unordered
+ *   pair; a pair of G is removed; a pair not in G, a self-loop, a repeat inside the batch or
+ *   the same pair in both directions changes nothing further.
+ * gs_triangle_expire: removes every edge whose stamp is older than the last `folds` folds
+ *   (stamp + folds <= the current fold number, computed without wrap-around); folds >= 1,
+ *   GS_ERR_INVALID otherwise. More folds than were made so far removes nothing. Asynchronous
+ *   but for the one synchronisation above.
+ * gs_triangle_set_refresh: on != 0: from the next fold on, an edge that a fold contains again
+ *   takes that fold's number (both directed entries; a pass behind the count step). Off by
+ *   default, and then a fold queues no launch for it.
  * gs_triangle_count: T, |G| and the vertex count on the host (synchronises).
  * gs_triangle_count_device: the same three words into DEVICE memory, asynchronous.
  * gs_triangle_find_device: count[i] = t(v[i]) of the DEVICE id v[i] (0 when absent);
@@ -498,6 +522,10 @@ int gs_triangle_destroy(gs_triangles t); /* NULL is GS_OK */
 int gs_triangle_reset(gs_triangles t);
 int gs_triangle_fold(gs_triangles t, const int64_t* src, const int64_t* dst, size_t n);
 int gs_triangle_fold_device(gs_triangles t, const int64_t* src, const int64_t* dst, size_t n, size_t stride);
+int gs_triangle_remove(gs_triangles t, const int64_t* src, const int64_t* dst, size_t n);
+int gs_triangle_remove_device(gs_triangles t, const int64_t* src, const int64_t* dst, size_t n, size_t stride);
+int gs_triangle_expire(gs_triangles t, uint64_t folds);
+int gs_triangle_set_refresh(gs_triangles t, int on);
 int gs_triangle_count(gs_triangles t, uint64_t* triangles, uint64_t* edges, uint64_t* vertices);
 int gs_triangle_count_device(gs_triangles t, uint64_t* out);
 int gs_triangle_find_device(gs_triangles t, const int64_t* v, size_t n, int64_t* count, uint8_t* found);

@@ -87,6 +87,27 @@ int gs_testing_triangle_stats(void* t, uint64_t* out);
  * group. Both are 0 under GS_TESTING_TRIANGLE_VARIANT 1 and after a reset. Two words. */
 int gs_testing_triangle_bins(void* t, uint64_t* out);
 
+/* The last removal of a triangle handle (`t` is a gs_triangles; gs_triangle_remove,
+ * _remove_device or _expire; synchronises): out[0] = edges removed, out[1] = triangles
+ * destroyed, out[2] = vertices vanished, out[3] = dying edges the count step gave to a wave,
+ * out[4] = to a workgroup with the longer row sampled in LDS (both 0 under
+ * GS_TESTING_TRIANGLE_VARIANT 1), out[5] = intersection steps (the sum over the dying edges of
+ * the shorter row's length, rows as they were before the removal); out[0..5] are zero when
+ * the last removal removed nothing and after a reset. out[6] = slots of the vertex table,
+ * out[7] = entries of the adjacency, both as they are now. Eight words. */
+int gs_testing_triangle_remove_stats(void* t, uint64_t* out);
+
+/* Microseconds of the last removal's phases under GS_TESTING_TRIANGLE_PROFILE 1 (`t` is a
+ * gs_triangles; no device call; zero otherwise): out[0] = mark (the dying edges, the survivors'
+ * positions and the host synchronisation), out[1] = rows and count, out[2] = compaction and the
+ * table rebuild. Three words. */
+int gs_testing_triangle_remove_phases(void* t, uint64_t* out);
+
+/* The fold number of an EMPTY triangle handle (`t` is a gs_triangles; no device call;
+ * GS_ERR_INVALID when it holds an edge or value >= 2^32) becomes `value`, so that the next fold
+ * takes value + 1: a test places it a few folds before the 32-bit wrap. */
+int gs_testing_triangle_set_fold(void* t, uint64_t value);
+
 /* Diagnostics of a slice handle (`s` is a gs_slices; synchronises): out[0] = tiles of the last
  * reduce (0: none yet, the count op reads no tile), out[1] = tiles of the current window that
  * hold no head -- carry records that hand a run on to the next tile --, out[2] = the longest
