@@ -107,7 +107,17 @@ EXPORTED_SYMBOLS = (
     "gs_tristream_rows", "gs_tristream_rows_device", "gs_tristream_records", "gs_tristream_records_device",
     "gs_tristream_size", "gs_tristream_count", "gs_tristream_counts", "gs_tristream_counts_device", "gs_tristream_sync",
     "gs_tristream_get_stream", "gs_tristream_wait_stream", "gs_testing_tristream_stats", "gs_testing_tristream_tune",
+    "gs_parse_records_device", "gs_window_bounds_device", "gs_text_create", "gs_text_destroy", "gs_text_set_window",
+    "gs_text_open", "gs_text_next", "gs_text_windows", "gs_text_position", "gs_text_sync", "gs_text_get_stream", "gs_text_wait_stream",
+    "gs_testing_text_stats",
 )
+
+TEXT_THIRD = {None: 0, "long": 1, "event": 2}  # GS_TEXT_THIRD_* (include/gs_ingest.h)
+TEXT_INT32 = 1            # GS_TEXT_INT32: Integer.parseInt endpoints
+TEXT_COMMENT_PERCENT = 2  # GS_TEXT_COMMENT_PERCENT: "%" lines give no record
+# Lines per workgroup of the comment compaction and records per workgroup of the window bounds
+# (csrc/gs_text_seq.hpp kTxtTile); TILE_SCAN_BLOCK of them per step of the tile scan.
+TEXT_TILE = 1024
 
 # Pairs per workgroup of the component export's radix-sort kernels (csrc/gs_sort.hpp kSortTile):
 # sizes around it are where a tile fills exactly.
@@ -312,6 +322,24 @@ def lib():
     L.gs_parse_set_profiling.argtypes = [ctypes.c_int]
     L.gs_parse_profile.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_u64)]
     L.gs_fold_text.argtypes = [_vp, ctypes.c_char_p, _sz, ctypes.c_int, ctypes.POINTER(_u64), ctypes.POINTER(_i64)]
+    if hasattr(L, "gs_text_create"):  # (an A/B's GS_LIB_VARIANT library of the parent commit has none of them)
+        L.gs_parse_records_device.argtypes = [_vp, _vp, _sz, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp,
+                                              _vp, _sz, ctypes.POINTER(_u64), ctypes.POINTER(_u64),
+                                              ctypes.POINTER(_i64)]
+        L.gs_window_bounds_device.argtypes = [_vp, _vp, _sz, _i64, _vp, _vp, _sz, ctypes.POINTER(_u64)]
+        L.gs_text_create.argtypes = [ctypes.POINTER(_vp), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _sz]
+        L.gs_text_destroy.argtypes = [_vp]
+        L.gs_text_set_window.argtypes = [_vp, _i64]
+        L.gs_text_open.argtypes = [_vp, _vp, _sz]
+        L.gs_text_next.argtypes = [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp),
+                                   ctypes.POINTER(_vp), ctypes.POINTER(_sz), ctypes.POINTER(_vp), ctypes.POINTER(_vp),
+                                   ctypes.POINTER(_sz), ctypes.POINTER(ctypes.c_int)]
+        L.gs_text_windows.argtypes = [_vp, _vp, _vp, _sz, ctypes.POINTER(_sz)]
+        L.gs_text_position.argtypes = [_vp, ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(_i64)]
+        L.gs_text_sync.argtypes = [_vp]
+        L.gs_text_get_stream.argtypes = [_vp, ctypes.POINTER(_vp)]
+        L.gs_text_wait_stream.argtypes = [_vp, _vp]
+        L.gs_testing_text_stats.argtypes = [ctypes.POINTER(_u64)]
     L.gs_group_unique_id.argtypes = [_vp]
     L.gs_group_create.argtypes = [ctypes.POINTER(_vp), _vp, _vp, ctypes.c_int, ctypes.c_int, _sz]
     L.gs_group_fold_device.argtypes = [_vp, _vp, _vp, _sz]
@@ -2370,6 +2398,186 @@ def parse_edges_device(text, src, dst, sep=SEP_WHITESPACE, stream=None):
     if rc not in (GS_OK, GS_ERR_PARSE, GS_ERR_TRUNCATED):
         raise GSError(rc, "gs_parse_edges_device failed")
     return n.value, bad.value
+
+
+def _text_flags(int32, comments):
+    return (TEXT_INT32 if int32 else 0) | (TEXT_COMMENT_PERCENT if comments else 0)
+
+
+def parse_records_device(text, src, dst, third_out=None, sep=SEP_WHITESPACE, third=None, int32=False, comments=False,
+                         stream=None):
+    """gs_parse_records_device: device uint8 text -> device int64 src/dst and, for third "long" /
+    "event", the int64 values / uint8 deletion bytes in `third_out`. The capacity counts lines.
+    Returns (n_lines, n_records, bad_line); as parse_edges_device, a malformed line or a short
+    output raises nothing."""
+    if third not in TEXT_THIRD:
+        raise ValueError("third must be None, 'long' or 'event'")
+    nl, nr, bad = _u64(), _u64(), _i64(-1)
+    ln = text.numel() if hasattr(text, "numel") else len(text)
+    cap = src.numel() if hasattr(src, "numel") else len(src)
+    val = _ptr(third_out) if third == "long" else None
+    dele = _ptr(third_out) if third == "event" else None
+    rc = lib().gs_parse_records_device(stream, _ptr(text), ln, int(sep), TEXT_THIRD[third], _text_flags(int32, comments),
+                                       _ptr(src), _ptr(dst), val, dele, cap, ctypes.byref(nl), ctypes.byref(nr),
+                                       ctypes.byref(bad))
+    if rc not in (GS_OK, GS_ERR_PARSE, GS_ERR_TRUNCATED):
+        raise GSError(rc, "gs_parse_records_device failed")
+    return nl.value, nr.value, bad.value
+
+
+def window_bounds_device(ts, size, first, window, n=None, stream=None):
+    """gs_window_bounds_device: the event-time windows (id = ts / size, truncating) of the device
+    int64 timestamps ts[:n]: first[w] (uint64 as int64 tensor) and window[w] for every maximal run
+    of equal ids. Returns the number of windows (it may exceed the capacity of first / window)."""
+    nw = _u64()
+    if n is None:
+        n = ts.numel()
+    cap = min(first.numel(), window.numel())
+    rc = lib().gs_window_bounds_device(stream, _ptr(ts), int(n), int(size), _ptr(first), _ptr(window), cap,
+                                       ctypes.byref(nw))
+    if rc not in (GS_OK, GS_ERR_TRUNCATED):
+        raise GSError(rc, "gs_window_bounds_device failed")
+    return nw.value
+
+
+def testing_text_stats():
+    """gs_testing_text_stats: (field-spec parses, comment compactions) of parse_records_device."""
+    out = (_u64 * 2)()
+    _check(lib().gs_testing_text_stats(out))
+    return out[0], out[1]
+
+
+class _DeviceColumn:
+    """n elements of device memory at ptr, for torch.as_tensor (the CUDA array interface)."""
+
+    def __init__(self, ptr, n, typestr):
+        self.__cuda_array_interface__ = {"shape": (int(n),), "typestr": typestr, "data": (int(ptr), False),
+                                         "version": 2, "strides": None}
+
+
+def _device_view(ptr, n, typestr, device):
+    import torch
+    dtype = {"<i8": torch.int64, "|u1": torch.uint8}[typestr]
+    if not ptr or n == 0:
+        return torch.empty(0, dtype=dtype, device="cuda:%d" % device)
+    return torch.as_tensor(_DeviceColumn(ptr, n, typestr), device="cuda:%d" % device)
+
+
+class TextReader(_Handle):
+    """A gs_text reader: host text (bytes) in, chunks of device columns out, for any handle's
+    fold_device. third: None, "long" (a Long.parseLong value or timestamp) or "event" ('+' /
+    anything else: the deletion byte); int32: Integer.parseInt endpoints; comments: "%" lines
+    give no record (include/gs_ingest.h states the rules). The tensors a chunk yields are views
+    of the reader's columns: they hold until the chunk after the next is asked for."""
+
+    _PREFIX = "gs_text"
+
+    def __init__(self, device=0, sep=SEP_WHITESPACE, third=None, int32=False, comments=False, chunk_bytes=0):
+        if third not in TEXT_THIRD:
+            raise ValueError("third must be None, 'long' or 'event'")
+        self._h = None
+        self.device = device
+        self.third = third
+        self.sep = sep
+        h = _vp()
+        _check(lib().gs_text_create(ctypes.byref(h), device, int(sep), TEXT_THIRD[third], _text_flags(int32, comments),
+                                    int(chunk_bytes)))
+        self._h = h
+
+    def position(self):
+        """(lines, records, bad_line) since the last open; bad_line -1 unless a malformed line ended it."""
+        nl, nr, bad = _u64(), _u64(), _i64(-1)
+        self._call("position", ctypes.byref(nl), ctypes.byref(nr), ctypes.byref(bad))
+        return nl.value, nr.value, bad.value
+
+    def _next(self):
+        p = [_vp() for _ in range(6)]
+        n, nw, last = _sz(), _sz(), ctypes.c_int()
+        self._call("next", ctypes.byref(p[0]), ctypes.byref(p[1]), ctypes.byref(p[2]), ctypes.byref(p[3]),
+                   ctypes.byref(n), ctypes.byref(p[4]), ctypes.byref(p[5]), ctypes.byref(nw), ctypes.byref(last))
+        return [x.value for x in p], n.value, nw.value, bool(last.value)
+
+    def _chunks(self, text, window):
+        text = bytes(text)  # (kept alive until the last chunk)
+        self._call("set_window", int(window))
+        self._call("open", text, len(text))
+        last = False
+        while not last:
+            p, n, nw, last = self._next()
+            src = _device_view(p[0], n, "<i8", self.device)
+            dst = _device_view(p[1], n, "<i8", self.device)
+            third = None
+            if self.third == "long":
+                third = _device_view(p[2], n, "<i8", self.device)
+            elif self.third == "event":
+                third = _device_view(p[3], n, "|u1", self.device)
+            yield src, dst, third, n, _device_view(p[4], nw, "<i8", self.device), _device_view(p[5], nw, "<i8",
+                                                                                               self.device)
+
+    def chunks(self, text):
+        """A generator of (src, dst, third, n): the records of one chunk as device tensors (third:
+        int64 values, uint8 deletion bytes, or None). The chunk is complete on the reader's stream
+        and the host has waited for it. A malformed line raises GSError(GS_ERR_PARSE) when its chunk
+        is reached; position() then names its line."""
+        for src, dst, third, n, _, _ in self._chunks(text, 0):
+            yield src, dst, third, n
+
+    def windows(self, text, size):
+        """A generator of (window_id, src, dst, val, n), one per whole event-time window (third
+        "long": the timestamps; id = ts / size, truncating), in stream order."""
+        if self.third != "long":
+            raise ValueError("windows need a reader with third='long' (the timestamp)")
+        if int(size) <= 0:
+            raise ValueError("a window size is > 0")
+        for src, dst, val, n, first, window in self._chunks(text, int(size)):
+            f = first.cpu().tolist() + [n]
+            for k, w in enumerate(window.cpu().tolist()):
+                a, b = f[k], f[k + 1]
+                yield w, src[a:b], dst[a:b], val[a:b], b - a
+
+    def _fold_kind(self, target):
+        """How fold_into hands a chunk to `target`: "plain", "deletions" or "val"; ValueError for a
+        target this reader's third field does not fit."""
+        name = type(target).__name__
+        if isinstance(target, (Degrees, DegreeStream)):
+            if self.third == "long":
+                raise ValueError("%s takes an 'event' reader (deletions) or one without a third field" % name)
+            return "deletions" if self.third == "event" else "plain"
+        if isinstance(target, Matching):
+            if self.third != "long":
+                raise ValueError("Matching needs a reader with third='long' (the weight)")
+            return "val"
+        if isinstance(target, (Summary, Triangles, TriangleStream, Distinct, Spanner, TriangleSampler)):
+            if self.third is not None:
+                raise ValueError("%s takes a reader without a third field" % name)
+            return "plain"
+        raise ValueError("fold_into: no fold for a %s" % name)
+
+    def fold_into(self, target, text, each=None):
+        """Fold every chunk of `text` into `target` with its fold_device, in order; each(n), if
+        given, runs after each chunk's fold (a stream handle's rows can be read there). The
+        target's stream waits for the reader's before a fold, and the reader's for the target's
+        before the next chunk overwrites columns a fold may still read. Returns the record count.
+        Degrees / DegreeStream take an "event" reader (deletions) or one without a third field,
+        Matching a "long" one (the weight), every other handle one without a third field; a
+        mismatch raises ValueError before anything is folded."""
+        kind = self._fold_kind(target)
+        total = 0
+        own = self.stream
+        for src, dst, third, n in self.chunks(text):
+            if n:
+                target.wait_stream(own)
+                if kind == "deletions":
+                    target.fold_device(src, dst, n=n, deletions=third)
+                elif kind == "val":
+                    target.fold_device(src, dst, third, n=n)
+                else:
+                    target.fold_device(src, dst, n=n)
+                self.wait_stream(target.stream)
+            total += n
+            if each is not None:
+                each(n)
+        return total
 
 
 def parse_set_profiling(on):

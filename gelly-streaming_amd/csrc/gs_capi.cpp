@@ -1977,9 +1977,8 @@ int gs_capacity_stats(gs_handle h, uint64_t* waits, uint64_t* syncs, double* wai
 }
 
 // ---- text ingest (include/gs_ingest.h) ----
-namespace {
-constexpr size_t kTextChunk = 16u << 20;  // bytes of text per parse + fold
-
+extern "C++" {
+namespace gsi {
 // Copy into pinned staging with a few threads (one core's memcpy is far below PCIe).
 void staged_copy(char* dst, const char* src, size_t n) {
   const int nt = n >= (4u << 20) ? 8 : 1;
@@ -1995,15 +1994,16 @@ void staged_copy(char* dst, const char* src, size_t n) {
   for (auto& x : th) x.join();
 }
 
-// End of the chunk that starts at off: after the last '\n' within kTextChunk bytes
+// End of the chunk that starts at off: after the last '\n' within `chunk` bytes
 // (the whole rest when it fits); 0 = a single line longer than a chunk.
-size_t chunk_end(const char* text, size_t len, size_t off) {
-  if (len - off <= kTextChunk) return len;
-  size_t end = off + kTextChunk;
+size_t chunk_end(const char* text, size_t len, size_t off, size_t chunk) {
+  if (len - off <= chunk) return len;
+  size_t end = off + chunk;
   while (end > off && text[end - 1] != '\n') --end;
   return end == off ? 0 : end;
 }
-}  // namespace
+}  // namespace gsi
+}  // extern "C++"
 
 int gs_fold_text(gs_handle h, const char* text, size_t len, int sep, uint64_t* n_edges, int64_t* bad_line) {
   if (int rc = check(h)) return rc;
@@ -2040,7 +2040,7 @@ int gs_fold_text(gs_handle h, const char* text, size_t len, int sep, uint64_t* n
     return GS_OK;
   };
   if (len == 0) return GS_OK;
-  size_t end = chunk_end(text, len, 0);
+  size_t end = chunk_end(text, len, 0, kTextChunk);
   if (!end) return fail(GS_ERR_INVALID, "a line is longer than the 16 MiB ingest chunk");
   staged_copy(h->text.h_text, text, end);
   if (int rc = enqueue(0, end)) return rc;
@@ -2048,7 +2048,7 @@ int gs_fold_text(gs_handle h, const char* text, size_t len, int sep, uint64_t* n
   for (int b = 0;; b ^= 1) {
     // host: the next chunk into the other pinned buffer (its previous H2D is done:
     // that chunk's event was waited for in the previous iteration)
-    const size_t noff = end, nend = noff < len ? chunk_end(text, len, noff) : noff;
+    const size_t noff = end, nend = noff < len ? chunk_end(text, len, noff, kTextChunk) : noff;
     if (noff < len && !nend) return fail(GS_ERR_INVALID, "a line is longer than the 16 MiB ingest chunk");
     if (noff < len) staged_copy(h->text.h_text + (size_t)(b ^ 1) * kTextChunk, text + noff, nend - noff);
     GS_HIP(hipEventSynchronize(h->text.ev[b]));

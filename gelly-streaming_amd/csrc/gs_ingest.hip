@@ -14,6 +14,11 @@
 //                   parses them with the Java split/parseLong rules: SWAR from LDS words
 //                   (parse_line_swar), or one byte per step for long lines / fields;
 //                   malformed lines -> atomicMin(bad).
+//   k_txt_parse<M>: the one-pass parse (k_parse_fused: the same parse_tile) with a third field,
+//                   int32 endpoints and '%' comment lines (gs_text_seq.hpp; include/gs_ingest.h's
+//                   gs_parse_records_device), one instantiation per mode; k_txt_count /
+//                   k_txt_compact / k_txt_windows: the compaction of comment rows and the bounds
+//                   of event-time windows (flag, launch_tile_scan, rank and write)
 // RMAT-26 text (684 MB, 2^24 lines): k_count_lines 120-133 us (5.4 TB/s); k_parse 771 us
 // with a per-character parse of compacted line starts, 592 us with the SWAR parse, 370 us
 // with lines parsed by the thread whose 32-byte segment they start in (no start list),
@@ -21,14 +26,20 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "gs_ingest.h"
+#include "gs_grow.hpp"
 #include "gs_ingest.hpp"
+#include "gs_scan.hpp"
+#include "gs_sort.hpp"
+#include "gs_text_seq.hpp"
 
 namespace gs {
 
@@ -250,6 +261,66 @@ __device__ __forceinline__ int parse_line_swar(const uint8_t* L, int s, int e, i
   return 1;
 }
 
+// The field-spec form of parse_line_swar (MODE = txt_mode(third, flags) != 0, gs_text_seq.hpp):
+// fields 0 and 1 as there, then the int32 range, then the third field. A LONG field takes a
+// third 24-byte window and digits_value; an EVENT field is one or two bytes, and only an empty
+// one walks on to see whether anything but separators follows. Returns kTxtRecord, kTxtBad, or
+// -1 (a field of more than 23 bytes: the caller takes the per-character path). v = the LONG
+// value or the EVENT byte. Comment lines never come here (parse_at tests them first).
+//
+// Every window stays inside the staged lds[0 .. kLds0 + kTile + kOver): with s the line's start
+// and e its end, 0 <= s < kTile and s <= e < kTile + 192 (the '\n' lies in the start's 64-byte
+// segment or the next two). lds_win24(L, o) reads L[o & ~3 .. (o & ~3) + 28). The forward windows
+// start at s, q = p1 + 1 <= e and r = p2 + 1 <= e, so they end below kTile + 192 + 28 <= kTile +
+// kOver. digits_value reads the window that ends at p1, p2 or p3, each in [s + 1, e]: it starts
+// at or above s + 1 - 24 - 3 >= -26 >= -kLds0 and ends below e + 4.
+template <int SEP, int MODE>
+__device__ __forceinline__ int txt_line_swar(const uint8_t* L, int s, int e, int64_t& a, int64_t& b, int64_t& v) {
+  constexpr int kThird = txt_mode_third(MODE);
+  if (e > s && L[e - 1] == '\r') --e;  // a '\r' right before the line end is dropped
+  uint32_t w[6];
+  lds_win24(L, s, w);
+  const uint32_t c0 = w[0] & 0xFFu;
+  const bool sg0 = c0 == '+' || c0 == '-';
+  const int f0 = first_nondigit(w, sg0);
+  if (f0 >= 24) return -1;
+  const int p1 = s + f0, n0 = f0 - (sg0 ? 1 : 0);
+  if (n0 <= 0 || p1 >= e || !sep_byte<SEP>(L[p1])) return kTxtBad;
+  const int q = p1 + 1;
+  lds_win24(L, q, w);
+  const uint32_t c1 = w[0] & 0xFFu;
+  const bool sg1 = q < e && (c1 == '+' || c1 == '-');
+  const int f1 = first_nondigit(w, sg1);
+  if (f1 >= 24) return -1;
+  const int p2 = min(q + f1, e), n1 = p2 - q - (sg1 ? 1 : 0);
+  if (n1 <= 0 || (p2 < e && !sep_byte<SEP>(L[p2]))) return kTxtBad;
+  if (!digits_value(L, p1, n0, c0 == '-', a)) return kTxtBad;
+  if (!digits_value(L, p2, n1, sg1 && c1 == '-', b)) return kTxtBad;
+  if (txt_mode_int32(MODE) && !(txt_int32_ok(a) && txt_int32_ok(b))) return kTxtBad;
+  if (kThird == kTxtNone) return kTxtRecord;
+  const int r = p2 + 1;  // field 2 starts here if it exists
+  if (r >= e) return kTxtBad;  // no separator after field 1, or nothing after it
+  if (kThird == kTxtLong) {
+    lds_win24(L, r, w);
+    const uint32_t c2 = w[0] & 0xFFu;
+    const bool sg2 = c2 == '+' || c2 == '-';
+    const int f2 = first_nondigit(w, sg2);
+    if (f2 >= 24) return -1;
+    const int p3 = min(r + f2, e), n2 = p3 - r - (sg2 ? 1 : 0);
+    if (n2 <= 0 || (p3 < e && !sep_byte<SEP>(L[p3]))) return kTxtBad;
+    return digits_value(L, p3, n2, c2 == '-', v) ? kTxtRecord : kTxtBad;
+  }
+  const uint32_t c2 = L[r];
+  if (!sep_byte<SEP>(c2)) {
+    v = (c2 == '+' && (r + 1 >= e || sep_byte<SEP>(L[r + 1]))) ? 0 : 1;
+    return kTxtRecord;
+  }
+  v = 1;  // an empty field 2, if anything but separators follows
+  for (int k = r + 1; k < e; ++k)
+    if (!sep_byte<SEP>(L[k])) return kTxtRecord;
+  return kTxtBad;
+}
+
 // '\n' mask (bit j: byte 32 q + j) of the 32-byte LDS segment q of the tile, with every
 // byte at or past the text's end `vend` (tile-relative, when the tile holds it) counted
 // as the end of the last line: bit vend set, bits above it cleared
@@ -284,13 +355,16 @@ __device__ __forceinline__ uint32_t chunk_nl_mask(const uint8_t* L, uint32_t c, 
   return nl;
 }
 
-template <bool FUSED>
+// MODE = txt_mode(third, flags) of gs_text_seq.hpp; 0 is the two-field parse. Staging, '\n'
+// masks, line numbers and the look-back are one code for every MODE: only parse_at and emit
+// read it.
+template <bool FUSED, int MODE = 0>
 __device__ __forceinline__ void parse_tile(const uint8_t* __restrict__ text, uint64_t len, int sep,
                                            const uint64_t* __restrict__ tile_pre, int64_t* __restrict__ src,
                                            int64_t* __restrict__ dst, uint64_t cap,
                                            unsigned long long* __restrict__ bad, bool aligned, uint64_t tile,
                                            unsigned long long* __restrict__ status, unsigned long long* __restrict__ pstat,
-                                           unsigned long long lb_timeout);
+                                           unsigned long long lb_timeout, const TxtCols tx = TxtCols{});
 
 // Single pass (GS_PARSE_FUSED, default): no k_count_lines pass and no scan. Every block
 // counts its tile's '\n' from the masks it builds anyway and finds the count before its
@@ -479,13 +553,13 @@ __global__ __launch_bounds__(256) void k_parse(const uint8_t* __restrict__ text,
   parse_tile<false>(text, len, sep, tile_pre, src, dst, cap, bad, aligned, tile0 + blockIdx.x, nullptr, nullptr, 0ull);
 }
 
-template <bool FUSED>
+template <bool FUSED, int MODE>
 __device__ __forceinline__ void parse_tile(const uint8_t* __restrict__ text, uint64_t len, int sep,
                                            const uint64_t* __restrict__ tile_pre, int64_t* __restrict__ src,
                                            int64_t* __restrict__ dst, uint64_t cap,
                                            unsigned long long* __restrict__ bad, bool aligned, uint64_t tile,
                                            unsigned long long* __restrict__ status, unsigned long long* __restrict__ pstat,
-                                           unsigned long long lb_timeout) {
+                                           unsigned long long lb_timeout, const TxtCols tx) {
   constexpr uint32_t kSeg = kTile / 256;  // bytes per thread in the line-start scan
   constexpr uint32_t kExtra = 2;          // '\n' masks past the tile: lines that cross its end
   constexpr uint32_t kSlots = (kTile + kOver + 4095) / 4096;
@@ -613,8 +687,10 @@ __device__ __forceinline__ void parse_tile(const uint8_t* __restrict__ text, uin
 #if GS_PARSE_BRANCHLESS
   const uint64_t nx1 = nlm[threadIdx.x + 1], nx2 = nlm[threadIdx.x + 2];  // the next two segments' '\n' masks
 #endif
-  // one line starting at segment byte j: (a, d) and whether it is well formed
-  auto parse_at = [&](uint32_t j, int64_t& a, int64_t& d) -> bool {
+  // one line starting at segment byte j: (a, d), for MODE != 0 the third field's v, and what the
+  // line gives (kTxtBad = 0, kTxtRecord = 1, and kTxtSkip for a comment line)
+  using Ok = std::conditional_t<MODE == 0, bool, int>;  // (the two-field parse keeps its bool)
+  auto parse_at = [&](uint32_t j, int64_t& a, int64_t& d, int64_t& v) -> Ok {
     const int so = (int)(seg + j);
     // the line's '\n': the first one at or after its start, within this segment or
     // the next two (longer lines take the per-character path)
@@ -645,6 +721,30 @@ __device__ __forceinline__ void parse_tile(const uint8_t* __restrict__ text, uin
     a = 0;
     d = 0;
     int r = -1;
+    if constexpr (MODE != 0) {
+      v = 0;
+      // (the first byte of a line is staged: so < kTile; only a '%' line asks the rule function)
+      if (txt_mode_comment(MODE) && L[so] == '%' && txt_is_comment([&](uint64_t p) { return b.at(p); }, q, sep))
+        return kTxtSkip;
+      if (e >= 0)
+        r = sep == GS_SEP_TAB ? txt_line_swar<GS_SEP_TAB, MODE>(L, so, e, a, d, v)
+                              : txt_line_swar<GS_SEP_WHITESPACE, MODE>(L, so, e, a, d, v);
+      if (r >= 0) return r;
+      // a long line or field: one byte per step, the rules of gs_text_seq.hpp on parse_long
+      if (parse_long(b, q, sep, a) != kFieldSep) return kTxtBad;
+      ++q;
+      const int e1 = parse_long(b, q, sep, d);
+      if (e1 == kFieldBad) return kTxtBad;
+      if (txt_mode_int32(MODE) && !(txt_int32_ok(a) && txt_int32_ok(d))) return kTxtBad;
+      if (txt_mode_third(MODE) == kTxtNone) return kTxtRecord;
+      if (e1 != kFieldSep) return kTxtBad;  // no separator after field 1: no field 2
+      ++q;
+      if (txt_mode_third(MODE) == kTxtLong) return parse_long(b, q, sep, v) != kFieldBad ? kTxtRecord : kTxtBad;
+      uint8_t del = 0;
+      const bool has = txt_event_field([&](uint64_t p) { return b.at(p); }, q, sep, &del);
+      v = del;
+      return has ? kTxtRecord : kTxtBad;
+    }
 #if GS_PARSE_BRANCHLESS
     const int ee = e >= 0 ? e : so + 1;  // (no '\n' in reach: the result is discarded, r = -1)
     r = sep == GS_SEP_TAB ? parse_line_swar_bf<GS_SEP_TAB>(L, so, ee, a, d)
@@ -666,12 +766,22 @@ __device__ __forceinline__ void parse_tile(const uint8_t* __restrict__ text, uin
     }
     return ok;
   };
-  auto emit = [&](uint64_t line, bool ok, int64_t a, int64_t d) {
+  uint32_t nskip = 0;  // (MODE with comments) the comment lines this thread met
+  auto emit = [&](uint64_t line, Ok ok, int64_t a, int64_t d, int64_t v) {
+    if constexpr (txt_mode_comment(MODE)) {  // a skip byte per line: the compaction's flags
+      if (line < cap) tx.skip[line] = ok == kTxtSkip ? 1 : 0;
+      if (ok == kTxtSkip) {
+        ++nskip;
+        return;
+      }
+    }
     if (!ok) {
       atomicMin(bad, (unsigned long long)line);
     } else if (line < cap) {
       src[line] = a;
       dst[line] = d;
+      if constexpr (txt_mode_third(MODE) == kTxtLong) tx.val[line] = v;
+      if constexpr (txt_mode_third(MODE) == kTxtEvent) tx.del[line] = (uint8_t)v;
     }
   };
   uint64_t line;
@@ -679,19 +789,19 @@ __device__ __forceinline__ void parse_tile(const uint8_t* __restrict__ text, uin
     // a thread's first two lines (nearly always all of them) are parsed into registers
     // BEFORE the look-back, so that the predecessors' counts are published by the time
     // wave 0 reads them, and only the stores wait for the tile's line numbers
-    int64_t a0 = 0, d0 = 0, a1 = 0, d1 = 0;
-    bool ok0 = true, ok1 = true;
+    int64_t a0 = 0, d0 = 0, a1 = 0, d1 = 0, v0 = 0, v1 = 0;
+    Ok ok0 = true, ok1 = true;
     uint32_t k = 0;
     if (mine) {
       const uint32_t j = __ffsll((unsigned long long)mine) - 1;
       mine &= mine - 1;
-      ok0 = parse_at(j, a0, d0);
+      ok0 = parse_at(j, a0, d0, v0);
       k = 1;
     }
     if (mine) {
       const uint32_t j = __ffsll((unsigned long long)mine) - 1;
       mine &= mine - 1;
-      ok1 = parse_at(j, a1, d1);
+      ok1 = parse_at(j, a1, d1, v1);
       k = 2;
     }
     __shared__ unsigned long long pre_sh;
@@ -711,8 +821,8 @@ __device__ __forceinline__ void parse_tile(const uint8_t* __restrict__ text, uin
     }
     __syncthreads();
     line = pre_sh + line_off;
-    if (k >= 1) emit(line, ok0, a0, d0);
-    if (k >= 2) emit(line + 1, ok1, a1, d1);
+    if (k >= 1) emit(line, ok0, a0, d0, v0);
+    if (k >= 2) emit(line + 1, ok1, a1, d1, v1);
     line += k;
   } else {
     line = tile_pre[tile] + line_off;
@@ -720,11 +830,140 @@ __device__ __forceinline__ void parse_tile(const uint8_t* __restrict__ text, uin
   while (mine) {
     const uint32_t j = __ffsll((unsigned long long)mine) - 1;
     mine &= mine - 1;
-    int64_t a, d;
-    const bool ok = parse_at(j, a, d);
-    emit(line, ok, a, d);
+    int64_t a, d, v = 0;
+    const Ok ok = parse_at(j, a, d, v);
+    emit(line, ok, a, d, v);
     ++line;
   }
+  if constexpr (txt_mode_comment(MODE)) {  // one atomic per wave that saw a comment line
+    if (__ballot(nskip != 0)) {
+      const uint32_t tot = __builtin_amdgcn_readlane(wave_incl_sum(nskip), 63);
+      if (lane == 0) atomicAdd(tx.nskip, (unsigned long long)tot);
+    }
+  }
+}
+
+// The field-spec parse: k_parse_fused with the third field, the int32 range and the comment lines
+// of MODE (one instantiation each; the line loop holds no branch on them).
+template <int MODE>
+__global__ __launch_bounds__(256) void k_txt_parse(const uint8_t* __restrict__ text, uint64_t len, int sep,
+                                                   int64_t* __restrict__ src, int64_t* __restrict__ dst, uint64_t cap,
+                                                   unsigned long long* __restrict__ bad, bool aligned,
+                                                   unsigned long long* __restrict__ status,
+                                                   unsigned long long* __restrict__ pstat, unsigned long long lb_timeout,
+                                                   const TxtCols x) {
+  parse_tile<true, MODE>(text, len, sep, nullptr, src, dst, cap, bad, aligned, blockIdx.x, status, pstat, lb_timeout, x);
+}
+
+using TxtParseKernel = void (*)(const uint8_t*, uint64_t, int, int64_t*, int64_t*, uint64_t, unsigned long long*, bool,
+                                unsigned long long*, unsigned long long*, unsigned long long, const TxtCols);
+static TxtParseKernel txt_parse_kernel(int mode) {
+  switch (mode) {
+#define GS_TXT_MODE(m) \
+  case m:              \
+    return k_txt_parse<m>;
+    GS_TXT_MODE(1) GS_TXT_MODE(2) GS_TXT_MODE(4) GS_TXT_MODE(5) GS_TXT_MODE(6) GS_TXT_MODE(8) GS_TXT_MODE(9)
+    GS_TXT_MODE(10) GS_TXT_MODE(12) GS_TXT_MODE(13) GS_TXT_MODE(14)
+#undef GS_TXT_MODE
+    default:
+      return nullptr;  // (0 is k_parse_fused; 3, 7, 11, 15 name no third field)
+  }
+}
+
+// ---- the two compactions behind the parse: comment rows out, window bounds. Flag, count per
+// tile (block_count_to), launch_tile_scan, rank inside the tile (block_excl_scan), write. A thread
+// owns kTxtPer consecutive rows, so (tile base, rank) order is row order.
+struct TxtKeepRow {  // row i is a record (no comment line)
+  const uint8_t* skip;
+  __device__ __forceinline__ bool operator()(uint64_t i) const { return skip[i] == 0; }
+};
+struct TxtOpensWindow {  // record i is the first of a window
+  const int64_t* ts;
+  int64_t size;
+  __device__ __forceinline__ bool operator()(uint64_t i) const { return txt_window_opens(ts, i, size); }
+};
+
+template <class Flag>
+__device__ __forceinline__ uint32_t txt_flags(const Flag& f, uint64_t n, bool (&keep)[kTxtPer]) {
+  const uint64_t i0 = txt_row_first(blockIdx.x, threadIdx.x);
+  uint32_t cnt = 0;
+#pragma unroll
+  for (uint32_t k = 0; k < kTxtPer; ++k) {
+    keep[k] = i0 + k < n && f(i0 + k);
+    cnt += keep[k] ? 1u : 0u;
+  }
+  return cnt;
+}
+
+template <class Flag>
+__global__ __launch_bounds__(kTxtBS) void k_txt_count(const Flag f, uint64_t n, uint32_t* __restrict__ tb) {
+  __shared__ uint32_t total;
+  bool keep[kTxtPer];
+  block_count_to<kTxtBS>(txt_flags(f, n, keep), &total, tb + blockIdx.x);
+}
+
+// the records of the kept lines, in order, into the o columns (at most cap rows)
+__global__ __launch_bounds__(kTxtBS) void k_txt_compact(const TxtKeepRow f, uint64_t n, const uint32_t* __restrict__ tb,
+                                                        const int64_t* __restrict__ src, const int64_t* __restrict__ dst,
+                                                        const int64_t* __restrict__ val, const uint8_t* __restrict__ del,
+                                                        int64_t* __restrict__ osrc, int64_t* __restrict__ odst,
+                                                        int64_t* __restrict__ oval, uint8_t* __restrict__ odel,
+                                                        uint64_t cap) {
+  __shared__ uint32_t wsum[kTxtBS / 64];
+  bool keep[kTxtPer];
+  const uint32_t cnt = txt_flags(f, n, keep);
+  uint64_t row = (uint64_t)tb[blockIdx.x] + block_excl_scan<kTxtBS>(cnt, wsum);
+  const uint64_t i0 = txt_row_first(blockIdx.x, threadIdx.x);
+#pragma unroll
+  for (uint32_t k = 0; k < kTxtPer; ++k) {
+    if (!keep[k]) continue;
+    if (row < cap) {
+      osrc[row] = src[i0 + k];
+      odst[row] = dst[i0 + k];
+      if (val) oval[row] = val[i0 + k];
+      if (del) odel[row] = del[i0 + k];
+    }
+    ++row;
+  }
+}
+
+__global__ __launch_bounds__(kTxtBS) void k_txt_windows(const TxtOpensWindow f, uint64_t n,
+                                                        const uint32_t* __restrict__ tb, uint64_t* __restrict__ first,
+                                                        int64_t* __restrict__ window, uint64_t cap) {
+  __shared__ uint32_t wsum[kTxtBS / 64];
+  bool keep[kTxtPer];
+  const uint32_t cnt = txt_flags(f, n, keep);
+  uint64_t row = (uint64_t)tb[blockIdx.x] + block_excl_scan<kTxtBS>(cnt, wsum);
+  const uint64_t i0 = txt_row_first(blockIdx.x, threadIdx.x);
+#pragma unroll
+  for (uint32_t k = 0; k < kTxtPer; ++k) {
+    if (!keep[k]) continue;
+    if (row < cap) {
+      first[row] = i0 + k;
+      window[row] = txt_window_of(f.ts[i0 + k], f.size);
+    }
+    ++row;
+  }
+}
+
+void launch_txt_compact(const uint8_t* skip, uint64_t n, uint32_t* tb, unsigned long long* total, const int64_t* src,
+                        const int64_t* dst, const int64_t* val, const uint8_t* del, int64_t* osrc, int64_t* odst,
+                        int64_t* oval, uint8_t* odel, uint64_t cap, hipStream_t st) {
+  const uint64_t nt = txt_tiles(n);
+  const TxtKeepRow f{skip};
+  hipLaunchKernelGGL(k_txt_count<TxtKeepRow>, dim3((unsigned)nt), dim3(kTxtBS), 0, st, f, n, tb);
+  launch_tile_scan(tb, nt, total, st);
+  hipLaunchKernelGGL(k_txt_compact, dim3((unsigned)nt), dim3(kTxtBS), 0, st, f, n, tb, src, dst, val, del, osrc, odst,
+                     oval, odel, cap);
+}
+
+void launch_txt_windows(const int64_t* ts, uint64_t n, int64_t size, uint32_t* tb, unsigned long long* total,
+                        uint64_t* first, int64_t* window, uint64_t cap, hipStream_t st) {
+  const uint64_t nt = txt_tiles(n);
+  const TxtOpensWindow f{ts, size};
+  hipLaunchKernelGGL(k_txt_count<TxtOpensWindow>, dim3((unsigned)nt), dim3(kTxtBS), 0, st, f, n, tb);
+  launch_tile_scan(tb, nt, total, st);
+  hipLaunchKernelGGL(k_txt_windows, dim3((unsigned)nt), dim3(kTxtBS), 0, st, f, n, tb, first, window, cap);
 }
 
 // Exclusive scan of the tiles' '\n' counts (the two-pass path): one block walks the tiles in
@@ -809,7 +1048,10 @@ __global__ __launch_bounds__(256) void k_parse_finish(unsigned long long* agg, u
 
 int parse_text_enqueue(hipStream_t st, const char* text, size_t len, int sep, int64_t* src, int64_t* dst, size_t cap,
                        ParseScratch& s, unsigned long long* host_res, unsigned long long seq, bool fused,
-                       hipEvent_t kev0, hipEvent_t kev1) {
+                       hipEvent_t kev0, hipEvent_t kev1, int mode, const TxtCols* cols) {
+  if (mode != 0 && (!fused || !cols || !txt_parse_kernel(mode))) return -1;
+  // (a mode with comment lines counts them into res[2]: zero before the parse)
+  if (mode != 0 && hipMemsetAsync(s.res + 2, 0, 8, st) != hipSuccess) return -1;
   if (len == 0) return hipMemsetAsync(s.res, 0xFF, 16, st) == hipSuccess &&
                         hipMemsetAsync(s.res, 0, 8, st) == hipSuccess ? 0 : -1;
   const uint64_t tiles = (len + kTile - 1) / kTile;
@@ -834,8 +1076,15 @@ int parse_text_enqueue(hipStream_t st, const char* text, size_t len, int sep, in
     // how long a look-back waits before it counts the '\n' before its tile itself (~50 ms;
     // tests shorten it with GS_TESTING_PARSE_LB_TIMEOUT_US, 0: at once)
     const unsigned long long lb_timeout = 100ull * (unsigned long long)gsi::testing_value(GS_TESTING_PARSE_LB_TIMEOUT_US, 50000);
-    hipLaunchKernelGGL(k_parse_fused, dim3((unsigned)tiles), dim3(256), 0, st, t, (uint64_t)len, sep, src, dst,
-                       (uint64_t)cap, s.bad, aligned, agg, pre, lb_timeout);
+    if (mode == 0) {
+      hipLaunchKernelGGL(k_parse_fused, dim3((unsigned)tiles), dim3(256), 0, st, t, (uint64_t)len, sep, src, dst,
+                         (uint64_t)cap, s.bad, aligned, agg, pre, lb_timeout);
+    } else {
+      TxtCols x = *cols;
+      x.nskip = reinterpret_cast<unsigned long long*>(s.res + 2);
+      hipLaunchKernelGGL(txt_parse_kernel(mode), dim3((unsigned)tiles), dim3(256), 0, st, t, (uint64_t)len, sep, src, dst,
+                         (uint64_t)cap, s.bad, aligned, agg, pre, lb_timeout, x);
+    }
     if (kev1 && hipEventRecord(kev1, st) != hipSuccess) return -1;
 #ifdef GS_LB_STATS
     if (tiles > 4096 && tiles <= kLbsTiles) {  // the large parses only: per-tile figures, summarised
@@ -892,6 +1141,74 @@ int parse_text(hipStream_t st, const char* text, size_t len, int sep, int64_t* s
   if (hipStreamSynchronize(st) != hipSuccess) return -1;
   *n_lines = res[0];
   *bad_line = res[1] == ~0ull ? -1 : (int64_t)res[1];
+  return 0;
+}
+
+// the tile counts of a compaction over n rows
+static hipError_t txt_grow_tiles(hipStream_t st, TxtScratch& x, uint64_t n) {
+  return gsi::grow_group(st, x.tile_rows, n, n + n / 4, [&](uint64_t c) { return x.tb.alloc(txt_tiles(c) + 1); });
+}
+
+int parse_records(hipStream_t st, const char* text, size_t len, int sep, int third, int flags, int64_t* src,
+                  int64_t* dst, int64_t* val, uint8_t* del, size_t cap, ParseScratch& s, TxtScratch& x, TxtResult* out,
+                  hipEvent_t kev0, hipEvent_t kev1) {
+  *out = TxtResult();
+  if (len == 0) return 0;
+  const int mode = txt_mode(third, flags);
+  const bool comments = (flags & kTxtComment) != 0;
+  TxtCols cols;
+  cols.val = third == kTxtLong ? val : nullptr;
+  cols.del = third == kTxtEvent ? del : nullptr;
+  if (comments) {  // a skip byte per line that has a row
+    if (gsi::grow_group(st, x.lines, std::max<uint64_t>(cap, 1), std::max<uint64_t>(cap, 1),
+                        [&](uint64_t c) { return x.skip.alloc(c); }) != hipSuccess)
+      return -1;
+    cols.skip = x.skip;
+  }
+  if (parse_text_enqueue(st, text, len, sep, src, dst, cap, s, nullptr, 0, true, kev0, kev1, mode, &cols)) return -1;
+  uint64_t res[3] = {0, ~0ull, 0};  // {lines, first malformed line, comment lines}
+  if (hipMemcpyAsync(res, s.res, mode ? 24 : 16, hipMemcpyDeviceToHost, st) != hipSuccess) return -1;
+  if (hipStreamSynchronize(st) != hipSuccess) return -1;
+  out->lines = res[0];
+  out->bad_line = res[1] == ~0ull ? -1 : (int64_t)res[1];
+  out->records = res[0] - res[2];
+  const uint64_t rows = std::min<uint64_t>(res[0], cap);
+  if (res[2] == 0 || rows == 0) return 0;
+  // comment lines: the rows of the other lines move down, in order (out of place, then back)
+  if (rows > kTxtMaxRows) return -1;
+  if (!x.total && x.total.alloc(1) != hipSuccess) return -1;
+  if (txt_grow_tiles(st, x, rows) != hipSuccess ||
+      gsi::grow_group(st, x.rows, rows, rows + rows / 4,
+                      [&](uint64_t c) { return gsi::alloc_each(c, x.src, x.dst, x.val, x.del); }) != hipSuccess)
+    return -1;
+  launch_txt_compact(x.skip, rows, x.tb, x.total, src, dst, cols.val, cols.del, x.src, x.dst, x.val, x.del, rows, st);
+  if (hipGetLastError() != hipSuccess) return -1;
+  ++x.compactions;
+  unsigned long long kept = 0;
+  if (hipMemcpyAsync(&kept, x.total, 8, hipMemcpyDeviceToHost, st) != hipSuccess) return -1;
+  if (hipStreamSynchronize(st) != hipSuccess || kept > rows) return -1;
+  const auto back = [&](void* to, const void* from, size_t bytes) {
+    return !to || hipMemcpyAsync(to, from, bytes, hipMemcpyDeviceToDevice, st) == hipSuccess;
+  };
+  if (!back(src, x.src, kept * 8) || !back(dst, x.dst, kept * 8) || !back(cols.val, x.val, kept * 8) ||
+      !back(cols.del, x.del, kept))
+    return -1;
+  return hipStreamSynchronize(st) == hipSuccess ? 0 : -1;
+}
+
+int window_bounds(hipStream_t st, const int64_t* ts, size_t n, int64_t size, uint64_t* first, int64_t* window,
+                  size_t cap, TxtScratch& x, uint64_t* n_windows) {
+  *n_windows = 0;
+  if (n == 0) return 0;
+  if (n > kTxtMaxRows || size <= 0) return -1;
+  if (!x.total && x.total.alloc(1) != hipSuccess) return -1;
+  if (txt_grow_tiles(st, x, n) != hipSuccess) return -1;
+  launch_txt_windows(ts, n, size, x.tb, x.total, first, window, cap, st);
+  if (hipGetLastError() != hipSuccess) return -1;
+  unsigned long long w = 0;
+  if (hipMemcpyAsync(&w, x.total, 8, hipMemcpyDeviceToHost, st) != hipSuccess) return -1;
+  if (hipStreamSynchronize(st) != hipSuccess) return -1;
+  *n_windows = w;
   return 0;
 }
 
@@ -1031,6 +1348,76 @@ extern "C" int gs_parse_edges_device(void* stream, const char* text, size_t len,
   }
   if (*bad_line >= 0) return GS_ERR_PARSE;
   if (*n_lines > cap) return GS_ERR_TRUNCATED;
+  return GS_OK;
+}
+
+namespace {
+std::atomic<uint64_t> g_txt_parses{0}, g_txt_compactions{0};  // gs_testing_text_stats
+}
+
+// The field-spec parse on the calling thread's parse cache. Its other scratch lives for the call
+// and is allocated only where it is used: nothing without GS_TEXT_COMMENT_PERCENT (no allocation,
+// no free: the call costs the parse and one copy of its three result words), the skip bytes with
+// it, and the count word, tile counts and compaction columns only for a text that holds a comment
+// line.
+extern "C" int gs_parse_records_device(void* stream, const char* text, size_t len, int sep, int third, int flags,
+                                       int64_t* src, int64_t* dst, int64_t* val, uint8_t* del, size_t cap,
+                                       uint64_t* n_lines, uint64_t* n_records, int64_t* bad_line) {
+  if (!n_lines || !n_records || !bad_line || (len && !text)) return GS_ERR_INVALID;
+  if (!gs::txt_args_ok(sep, third, flags)) return GS_ERR_INVALID;
+  if (cap && (!src || !dst || (third == GS_TEXT_THIRD_LONG && !val) || (third == GS_TEXT_THIRD_EVENT && !del)))
+    return GS_ERR_INVALID;
+  *n_records = 0;
+  if (third == GS_TEXT_THIRD_NONE && flags == 0) {  // the two-field parse itself
+    const int rc = gs_parse_edges_device(stream, text, len, sep, src, dst, cap, n_lines, bad_line);
+    *n_records = *n_lines;
+    return rc;
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  *n_lines = 0;
+  *bad_line = -1;
+  if (len == 0) return GS_OK;
+  if (parse_cache_ready(st, len)) return GS_ERR_HIP;
+  ParseCache& c = t_parse;
+  gs::TxtScratch x;
+  gs::TxtResult r;
+  if (gs::parse_records(st, text, len, sep, third, flags, src, dst, val, del, cap, c.s, x, &r, c.prof ? c.kev[0] : nullptr,
+                        c.prof ? c.kev[1] : nullptr))
+    return GS_ERR_HIP;
+  ++g_txt_parses;
+  g_txt_compactions += x.compactions;
+  *n_lines = r.lines;
+  *n_records = r.records;
+  *bad_line = r.bad_line;
+  if (c.prof) {
+    float ms = 0.f;
+    if (hipEventSynchronize(c.kev[1]) != hipSuccess || hipEventElapsedTime(&ms, c.kev[0], c.kev[1]) != hipSuccess)
+      return GS_ERR_HIP;
+    c.prof_us += 1e3 * (double)ms;
+    ++c.prof_n;
+  }
+  if (r.bad_line >= 0) return GS_ERR_PARSE;
+  if (r.lines > cap) return GS_ERR_TRUNCATED;
+  return GS_OK;
+}
+
+extern "C" int gs_window_bounds_device(void* stream, const int64_t* ts, size_t n, int64_t size, uint64_t* first,
+                                       int64_t* window, size_t cap, uint64_t* n_windows) {
+  if (!n_windows || size <= 0 || (n && !ts) || (cap && (!first || !window))) return GS_ERR_INVALID;
+  *n_windows = 0;
+  if (n == 0) return GS_OK;
+  if (n > gs::kTxtMaxRows) return GS_ERR_CAPACITY;
+  gs::TxtScratch x;
+  if (gs::window_bounds(static_cast<hipStream_t>(stream), ts, n, size, first, window, cap, x, n_windows))
+    return GS_ERR_HIP;
+  return *n_windows > cap ? GS_ERR_TRUNCATED : GS_OK;
+}
+
+// gs_testing.h: field-spec parses of gs_parse_records_device and the comment compactions they ran
+extern "C" int gs_testing_text_stats(uint64_t* out) {
+  if (!out) return GS_ERR_INVALID;
+  out[0] = g_txt_parses;
+  out[1] = g_txt_compactions;
   return GS_OK;
 }
 

@@ -268,6 +268,12 @@ struct CombineSync {
   DevBuf<unsigned long long> cnt;  // device: exported rows (u64) + failure flag (u32 at word 1)
   Event ready, used;
 };
+// Text ingest (gs_fold_text, the gs_text reader; defined in gs_capi.cpp): a copy into pinned
+// staging with a few threads, and the end of the chunk of at most `chunk` bytes that starts at
+// off -- after its last '\n', the whole rest when it fits, 0 for a line longer than a chunk.
+constexpr size_t kTextChunk = 16u << 20;  // bytes of text per parse + fold
+void staged_copy(char* dst, const char* src, size_t n);
+size_t chunk_end(const char* text, size_t len, size_t off, size_t chunk);
 struct TextIngest {  // pinned + device text chunks, parse results, parsed edges, scratch
   HostBuf<char> h_text;
   HostBuf<uint64_t> h_res;

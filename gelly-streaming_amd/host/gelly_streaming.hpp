@@ -46,6 +46,7 @@
 #include <utility>
 #include <vector>
 
+#include "gs_ingest.h"
 #include "gs_summary.h"
 
 namespace gelly {
@@ -1164,6 +1165,53 @@ struct TriangleHandle {
   TriangleHandle& operator=(const TriangleHandle&) = delete;
 };
 
+// The text reader (gs_ingest.h, the gs_text_* section): host text in, chunks of device columns
+// out. next() returns false once the text's last chunk has been delivered; the arrays of a chunk
+// hold until the chunk after the next is asked for.
+class TextReader {
+ public:
+  struct Chunk {
+    const int64_t* src = nullptr;
+    const int64_t* dst = nullptr;
+    const int64_t* val = nullptr;   // third = GS_TEXT_THIRD_LONG
+    const uint8_t* del = nullptr;   // third = GS_TEXT_THIRD_EVENT
+    size_t n = 0;
+    const uint64_t* first = nullptr;  // window mode: the first record and the id of every whole window
+    const int64_t* window = nullptr;
+    size_t n_windows = 0;
+  };
+  explicit TextReader(int device = 0, int sep = GS_SEP_WHITESPACE, int third = GS_TEXT_THIRD_NONE, int flags = 0,
+                      size_t chunk_bytes = 0) {
+    gs_check(gs_text_create(&t_, device, sep, third, flags, chunk_bytes));
+  }
+  ~TextReader() { gs_text_destroy(t_); }
+  TextReader(const TextReader&) = delete;
+  TextReader& operator=(const TextReader&) = delete;
+  void setWindow(int64_t size) { gs_check(gs_text_set_window(t_, size)); }
+  void open(const char* text, size_t len) {
+    gs_check(gs_text_open(t_, text, len));
+    done_ = false;
+  }
+  bool next(Chunk* c) {
+    if (done_) return false;
+    int last = 0;
+    gs_check(gs_text_next(t_, &c->src, &c->dst, &c->val, &c->del, &c->n, &c->first, &c->window, &c->n_windows, &last));
+    done_ = last != 0;
+    return true;
+  }
+  void* stream() const {
+    void* s = nullptr;
+    gs_check(gs_text_get_stream(t_, &s));
+    return s;
+  }
+  void waitStream(void* s) { gs_check(gs_text_wait_stream(t_, s)); }
+  gs_text handle() const { return t_; }
+
+ private:
+  gs_text t_ = nullptr;
+  bool done_ = true;
+};
+
 // WindowTriangles (example/WindowTriangles.java:60-65): slice(windowTime, ALL), candidate
 // edges per neighbourhood, count per window. run() returns (count, window.maxTimestamp())
 // for every tumbling window that holds at least one non-loop edge, in window order. On
@@ -1195,6 +1243,45 @@ class WindowTriangles {
       if (edges == 0) continue;  // only self-loops
       const int64_t maxTimestamp = window_ > 0 ? kv.first * window_ + window_ - 1 : std::numeric_limits<int64_t>::max();
       out.emplace_back((long)tri, maxTimestamp);
+    }
+    return out;
+  }
+
+  // The reference driver's text form (WindowTriangles.java:178-186: "src trg timestamp" lines,
+  // split + Long.parseLong x 3) read on the device: whole windows from a TextReader, then per
+  // window reset, fold, count. A window here is a maximal run of consecutive lines with equal
+  // ts / windowMillis (truncating): rows come in stream order, and on an ascending stream of
+  // non-negative timestamps, the reference's input, they are run()'s rows. A malformed line
+  // throws (GS_ERR_PARSE) after the windows of the chunks before it.
+  std::vector<std::pair<long, int64_t>> runText(const char* text, size_t len, int sep = GS_SEP_WHITESPACE,
+                                                size_t chunk_bytes = 0) const {
+    if (window_ <= 0) throw std::invalid_argument("WindowTriangles::runText: the window size must be positive");
+    std::vector<std::pair<long, int64_t>> out;
+    TextReader reader(device_, sep, GS_TEXT_THIRD_LONG, 0, chunk_bytes);
+    reader.setWindow(window_);
+    reader.open(text, len);
+    TriangleHandle h(device_, 1024);
+    void* hs = nullptr;
+    gs_check(gs_triangle_get_stream(h.t, &hs));
+    TextReader::Chunk c;
+    std::vector<uint64_t> first;
+    std::vector<int64_t> ids;
+    while (reader.next(&c)) {
+      if (c.n_windows == 0) continue;
+      first.resize(c.n_windows + 1);
+      ids.resize(c.n_windows);
+      size_t got = 0;
+      gs_check(gs_text_windows(reader.handle(), first.data(), ids.data(), c.n_windows, &got));
+      first[c.n_windows] = c.n;
+      for (size_t w = 0; w < c.n_windows; ++w) {
+        gs_check(gs_triangle_reset(h.t));
+        gs_check(gs_triangle_fold_device(h.t, c.src + first[w], c.dst + first[w], first[w + 1] - first[w], 1));
+        uint64_t tri = 0, edges = 0, vertices = 0;
+        gs_check(gs_triangle_count(h.t, &tri, &edges, &vertices));
+        if (edges == 0) continue;  // only self-loops
+        out.emplace_back((long)tri, ids[w] * window_ + window_ - 1);
+      }
+      reader.waitStream(hs);  // the next chunk after these folds
     }
     return out;
   }

@@ -222,6 +222,11 @@ int gs_testing_tristream_stats(void* d, uint64_t* out);
  * Returns GS_OK or GS_ERR_INVALID. */
 int gs_testing_tristream_tune(void* d, int what, int64_t value);
 
+/* The field-spec text parse (include/gs_ingest.h; process-wide, no device call): out[0] = parses
+ * that gs_parse_records_device ran with a third field or a flag, out[1] = comment compactions
+ * among them (a text without a comment line runs none). Two words. */
+int gs_testing_text_stats(uint64_t* out);
+
 /* Per-handle controls of the hot index's build (`h` is a gs_handle of a connected-components
  * summary; not knobs of gs_testing_set): what = 0 the sketch's rows (1 or 2), what = 1 the
  * sketch's counters per row and per id the index can hold, as a log2 (0..6), what = 2 the folds
